@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — image-text pairs/s, forward+backward, of the LPI retrieval hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line: value / ms_per_step / median_ms_per_step / step_mfma_frac, the
+config, and (N > 1) the collectives' times from those K steps.  Everything that takes runs of its own — the roofline pass, the launch count, the
+other precisions / workloads / loops, the parity block, the collectives' self-checks and the CPU baseline — runs with --full only (the
+--no-roofline / --no-extras / --no-cpu-baseline switches still thin a --full run out); without --full those keys are null or absent.
+--dump-outputs DIR writes what the timed path handed its caller in the LAST timed step (rank 0: features, prompt stacks, losses, the factor
+gradients and the factors after the SGD update) as DIR/<name>.npy in float32, before any other work; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 N > 1 works as typed: when the process was not started by torch.distributed.run (no WORLD_SIZE in the environment) it starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py <same arguments>` as a CHILD process before anything touches the
@@ -17,13 +25,15 @@ contrastive + alignment losses -> dgrad backward through all 24 blocks to the pr
 The JSON line carries, besides the driver's contract keys:
   value / ms_per_step : from the wall clock around EXACTLY K steps (barrier + synchronize on both sides, MAX over ranks);
   median_ms_per_step  : median of the K per-step durations (HIP events recorded after every step inside that same region);
+  step_mfma_frac: whole-step fraction of the dense MFMA peak from SURVEY's 89.68 GFLOP/pair — model-FLOP utilisation (all kernels, not just GEMMs);
+  collectives  : (N > 1) mean microseconds of the feature all-gather and the factor-gradient all-reduce per step (the self-checks beside them: --full);
+and with --full:
   roofline     : the dominant kernel (the 256x256 GEMM, MFMA bound): executed FLOPs of its launches / their duration, bracketed by
                  HIP events on the launch stream in an instrumented pass after the timed region; which kernel a launch went to is
                  reported by the library (lpi_gemm_last_kernel), not re-derived here; each launch counts with the
                  median of five instrumented steps; `traffic` / `mfma_util` come from a committed rocprofv3 --pmc summary
                  (profiles/r*_pmc*.json) of the SAME workload (model / batch / depth), dtype, tuning and library build — else null;
-  step_mfma_frac: whole-step fraction of the same peak from SURVEY's 89.68 GFLOP/pair — model-FLOP utilisation (all kernels, not just GEMMs);
-  hw_flop_frac : the same with the FLOPs the kernels actually execute (dead text rows, the pooled last block, the prompt-row backward of the
+  hw_flop_frac : step_mfma_frac with the FLOPs the kernels actually execute (dead text rows, the pooled last block, the prompt-row backward of the
                  first block are skipped exactly, so this is lower);
   parity_mode  : (N = 1) the f32-operand mode that meets the 1e-4 parity bar, same workload, 20 steps, its own roofline block (157.3 TF peak);
   vit_l14      : (N = 1) BASELINE.json configs[4]'s per-GPU workload (ViT-L/14, 512 pairs, depth 12, r 8, bf16);
@@ -37,7 +47,6 @@ The JSON line carries, besides the driver's contract keys:
   plugin_step  : (N = 1) the reference's real caller loop — SPrompts.train_epoch (methods/sprompt.py:290-334) built from configs/lpi/coco_lpi.json, fed by a
                  DataLoader over a synthetic Coco that yields HOST f32 images and caption STRINGS: H2D copy, tokenisation, forward, losses, backward, SGD
                  step; pairs/s from the wall clock around K loop iterations, its ratio to the bare step (`value`) and the split of a step;
-  collectives  : (N > 1) mean microseconds of the feature all-gather and the factor-gradient all-reduce per step;
   cpu_baseline : the oracle (oracle/lpi_oracle.py, "port") timed on this host's cores on a bounded bs=8 sample, thread count swept.
 """
 import argparse
@@ -59,8 +68,12 @@ GEMM_KERNEL_NAMES = {0: "k128", 1: "k256", 2: "k256", 3: "k256x128", 4: "few_row
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline pass, launch count, other precisions / workloads / loops, parity, the "
+                         "collectives' self-checks, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--depth", type=int, default=3)
@@ -96,7 +109,10 @@ def parse_args():
     ap.add_argument("--cpu-baseline-bs256", action="store_true", help="also time ONE bs=256 oracle step on the host (~70 s; needs 200 GiB of host memory and 32 CPUs)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="N > 1 ranks on ONE GPU with a gloo group (messages staged through the host): exercises the multi-rank path on a 1-GPU box")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def engine_options(a):
@@ -358,16 +374,16 @@ class Workload:
         a = self.a
         if self.fwd_only:
             with torch.no_grad():
-                forward_loss(self.enc, self.images, self.ids, self.fac, a.depth, self.exchange.gather if self.exchange else None,
-                             overlap_towers=self.overlap, vision_lanes=a.vision_lanes, text_lanes=a.text_lanes, lockstep=not a.no_lockstep)
-        else:
-            train_step(self.enc, self.images, self.ids, self.fac, a.depth, self.exchange, overlap_towers=self.overlap,
-                       vision_lanes=a.vision_lanes, text_lanes=a.text_lanes, lockstep=not a.no_lockstep,
-                       flat_grad=self.flat_grad, grad_views=self.grad_views)
-            self.opt.step()
+                return forward_loss(self.enc, self.images, self.ids, self.fac, a.depth, self.exchange.gather if self.exchange else None,
+                                    overlap_towers=self.overlap, vision_lanes=a.vision_lanes, text_lanes=a.text_lanes, lockstep=not a.no_lockstep)
+        out = train_step(self.enc, self.images, self.ids, self.fac, a.depth, self.exchange, overlap_towers=self.overlap,
+                         vision_lanes=a.vision_lanes, text_lanes=a.text_lanes, lockstep=not a.no_lockstep,
+                         flat_grad=self.flat_grad, grad_views=self.grad_views)
+        self.opt.step()
+        return out
 
     def run(self, steps, warmup, sync):
-        """-> (seconds for exactly `steps` steps, per-step milliseconds from HIP events)."""
+        """-> (seconds for exactly `steps` steps, per-step milliseconds from HIP events); the last step's return value is kept in self.last."""
         import torch
         for _ in range(warmup):
             self.step()
@@ -376,12 +392,26 @@ class Workload:
         t0 = time.perf_counter()
         ev[0].record()
         for i in range(steps):
-            self.step()
+            out = self.step()
             ev[i + 1].record()
         sync()
         el = time.perf_counter() - t0
+        self.last = out
         per = [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
         return el, per
+
+    def outputs(self):
+        """What the caller of the timed path holds after the last timed step of run(): the step's outputs (features, prompt stacks, losses) and, for a
+        training step, the factor gradients and the factors after the SGD update."""
+        from lpi_amd.synth import PROMPT_NAMES
+        if self.fwd_only:
+            losses, img_f, txt_f, vis, txt = self.last
+            res = dict(losses or {}, img_f=img_f, txt_f=txt_f, vis_prompt=vis, txt_prompt=txt)
+        else:
+            res = dict(self.last)
+            res.update({"grad." + k: self.fac[k].grad for k in PROMPT_NAMES})
+        res.update({"param." + k: self.fac[k] for k in PROMPT_NAMES})
+        return res
 
     def gemm_roofline(self, nprof=5):
         """Instrumented pass: HIP events around every GEMM launch; the library says which kernel each launch used.  An event pair also spans any time
@@ -821,6 +851,23 @@ def packed_ids_host_cost(B, dev, n=20):
     return round(1e6 * (time.perf_counter() - t0) / n, 1)
 
 
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """arrays: name -> tensor.  Writes out_dir/<name>.npy in float32 (float64 stays float64).  Should they exceed `budget` bytes in all, every array
+    above its even share is cut to a fixed sample of its elements (seeded, sorted flat indices: the same places in every run)."""
+    import numpy as np
+    import torch
+    host = {k: (v.detach().double() if v.dtype == torch.float64 else v.detach().float()).cpu().numpy() for k, v in arrays.items()}
+    if sum(x.nbytes for x in host.values()) > budget:
+        share = budget // len(host)
+        for k, x in host.items():
+            if x.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+                host[k] = x.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+
+
 def main():
     a = parse_args()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -871,6 +918,8 @@ def main():
     el = rank_max(el)
     pairs_s = world * B * a.steps / el
     median_ms = rank_max(float(np.median(per)))
+    if a.dump_outputs and rank == 0:      # before anything else runs a step: the last TIMED step's outputs
+        dump_outputs(a.dump_outputs, wl.outputs())
     collectives = None
     if exchange is not None:
         torch.cuda.synchronize()
@@ -896,7 +945,7 @@ def main():
         exchange.timing = None
         # the same step WITHOUT the exchange on every rank at once (each rank its own contrastive matrix, no collective): what the collectives and the
         # larger loss matrix cost the job — a self-check beside the driver's own N = 1 run, not a scaling claim
-        if not a.fwd_only:
+        if a.full and not a.fwd_only:
             wl.exchange = None
             el0, _ = wl.run(max(4, a.steps // 2), 2, sync)
             el0 = rank_max(el0)
@@ -920,19 +969,21 @@ def main():
                                                     "job_per_gpu_ratio": round(pairs_s / world / v1, 4),
                                                     "note": "rank 0 stepping alone (exchange = None), the other ranks idle at a barrier: compare with the N = 1 line"}
 
-    roofline = None if a.no_roofline else wl.gemm_roofline()
-    from lpi_amd import _lib as _L
-    torch.cuda.synchronize()
-    n0 = _L.launch_count()
-    wl.step()
-    torch.cuda.synchronize()
-    launches_per_step = _L.launch_count() - n0      # library launches of one steady-state step (no other kernel runs in it: tests/test_round4_gpu.py)
+    roofline = launches_per_step = None
+    if a.full:
+        roofline = None if a.no_roofline else wl.gemm_roofline()
+        from lpi_amd import _lib as _L
+        torch.cuda.synchronize()
+        n0 = _L.launch_count()
+        wl.step()
+        torch.cuda.synchronize()
+        launches_per_step = _L.launch_count() - n0      # library launches of one steady-state step (no other kernel runs in it: tests/test_round4_gpu.py)
 
     hw_gflop = None
     if roofline is not None and not a.fwd_only:
         hw_gflop = wl.gemm_gflop_all + attention_gflop(cfg, B, 16, wl.text_rows, False, wl.text_shared)
     extras = {}
-    if world == 1 and not a.no_extras and not a.fwd_only and a.dtype == "bf16":
+    if a.full and world == 1 and not a.no_extras and not a.fwd_only and a.dtype == "bf16":
         del wl.opt
         # the same workload in the parity mode (f32 operands: meets the 1e-4 bar, roofline vs the 157.3 TF f32 MFMA peak) ...
         extras["parity_mode"] = run_record(a, dev, rank, sync, "f32", False, 20, 3)
@@ -1006,7 +1057,7 @@ def main():
         out.update(extras)
         if collectives is not None:
             out["collectives"] = collectives
-        out["cpu_baseline"] = cpu_baseline(cfg, a.depth, bs256=a.cpu_baseline_bs256) if (world == 1 and not a.no_cpu_baseline) else None
+        out["cpu_baseline"] = cpu_baseline(cfg, a.depth, bs256=a.cpu_baseline_bs256) if (a.full and world == 1 and not a.no_cpu_baseline) else None
     line = json.dumps(out) if rank == 0 else None
     try:
         if exchange is not None:

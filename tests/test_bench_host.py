@@ -1,7 +1,10 @@
-"""Host-side pieces of bench.py that need no GPU: the per-rank CPU affinity the launcher sets before any GPU call."""
+"""Host-side pieces of bench.py that need no GPU: the per-rank CPU affinity the launcher sets before any GPU call, the --steps / --warmup
+checks and the writer behind --dump-outputs."""
 import os
 import subprocess
 import sys
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -77,3 +80,45 @@ def test_gpu_numa_nodes_from_a_sysfs_tree(tmp_path, monkeypatch):
     other.mkdir()
     _fake_sysfs(other, [(128, -1), (129, -1)])
     assert bench.gpu_numa_nodes(str(other)) == [-1, -1]
+
+
+def test_steps_and_warmup_are_checked(monkeypatch):
+    sys.path.insert(0, REPO)
+    import bench
+    for argv in (["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.parse_args()
+        assert e.value.code == 2, argv
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.dump_outputs, a.full) == (7, 0, "d", False)
+
+
+def test_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path):
+    """Every array lands as <name>.npy in float32 (float64 stays float64); over the budget, the arrays above their even share are cut to the same
+    sample in every call, the small ones are written whole, and the total stays within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"img_f": torch.randn(300, 512, generator=g).bfloat16(), "grad.w": torch.randn(1000, 300, generator=g),
+              "loss": torch.tensor(1.25), "f64": torch.randn(7, generator=g, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        x = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert x.dtype == (np.float64 if k == "f64" else np.float32) and x.shape == tuple(v.shape), k
+        assert np.array_equal(x, v.double().numpy() if k == "f64" else v.float().numpy()), k
+    budget = 1 << 19
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= budget
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == y.dtype and np.array_equal(x, y), f
+    big = np.load(tmp_path / "a" / "grad.w.npy")
+    assert big.ndim == 1 and 0 < big.size < 1000 * 300 and np.isin(big, arrays["grad.w"].numpy().ravel()).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "loss.npy"), np.float32(1.25))

@@ -381,7 +381,7 @@ def test_bench_vit_l14_four_ranks_on_one_gpu():
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--share-gpu", "--model", "ViT-L/14", "--batch", "8", "--depth", "12",
-                        "--rank", "8", "--prompt-layers", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-extras"],
+                        "--rank", "8", "--prompt-layers", "12", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline", "--no-extras"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])

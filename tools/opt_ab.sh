@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/optab
 mkdir -p "$O"
 reps=$1; shift
-A="--steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-extras"
+A="--full --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-extras"
 for rep in $(seq 1 $reps); do
   i=0
   for cfg in "$@"; do

@@ -7,7 +7,7 @@ cfgs=("$@")
 for rep in $(seq 1 $reps); do
   for cfg in "${cfgs[@]}"; do
     e=""; [ "$cfg" != "-" ] && e="$cfg"
-    env $e timeout -k 10 300 python3 "$R/bench.py" --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+    env $e timeout -k 10 300 python3 "$R/bench.py" --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); f=r['roofline']
 print('%30s: %.3f ms  %.0f pairs/s   GEMM %.1f TF frac %.4f  %.3f ms/step over %d launches' % ('$cfg', r['ms_per_step'], r['value'], f['achieved'], f['frac'], f['gemm_ms_per_step'], f['launches_per_step']), flush=True)"
