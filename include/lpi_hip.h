@@ -579,6 +579,36 @@ int lpi_interact_bwd(int N, int Dv, int Dt, int R, int Lyr, int layer, const flo
  * `images.cuda()` copy of methods/sprompt.py:166-167, 301.  HOST pointers, no stream: dst[i * bytes_each ..] = srcs[i][0 .. bytes_each) for i < n on
  * `threads` host threads (dst: the pinned staging buffer the H2D DMA reads; 154 MB of f32 pixels per 256-pair step).  lpi_amd/pipeline.py. */
 int lpi_host_gather(void* dst, const void* const* srcs, int n, long bytes_each, int threads);
+/* The ragged form (images of different sizes, pixel_format='decoded'): dst = srcs[0][0 .. bytes[0]) ++ srcs[1][0 .. bytes[1]) ++ ... packed without gaps,
+ * on `threads` host threads.  bytes[i] >= 0.  Returns 0 or LPI_EINVAL. */
+int lpi_host_gather_v(void* dst, const void* const* srcs, const long* bytes, int n, int threads);
+
+/* ---- decoded pixels on the GPU (imageops.hip)      replaces: the host's crop / Resize (bilinear) / CenterCrop / RandomHorizontalFlip of the training and
+ * evaluation transforms (lpi_amd/retrieval/utils/data.py) and the HWC -> CHW copy of pixel_format='u8'.
+ * One descriptor per image: LPI_RESAMPLE_DESC int64 values {src_offset, w, h, x0, y0, x1, y1, rw, rh, ox, oy, flip}: the image is the w x h x 3 (HWC,
+ * RGB) uint8 block at byte src_offset of `src`; its output is crop((x0, y0, x1, y1)).resize((rw, rh), BILINEAR), the window [ox, ox+S) x [oy, oy+S) of
+ * that, mirrored left-right if flip = 1.
+ * EXACTNESS: out is Pillow 12's ImagingResample for 8-bit channels, byte for byte: per axis scale = in/out (in = the CROP's size: the filter clamps at
+ * the crop's edges), filterscale = support = max(scale, 1), center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)
+ * (center + support + 0.5), in) - xmin, taps tri((x + xmin - center + 0.5) * (1 / filterscale)) summed in tap order and divided by their sum, in double
+ * without FMA contraction, converted to 22-bit fixed point as (int)(+-0.5 + k * 2^22); the horizontal pass is rounded to a uint8 intermediate
+ * (clamp((2^21 + sum) >> 22, 0, 255)), then the vertical pass on it the same way — or vertical first, then horizontal, where Pillow's Image.resize
+ * takes that order: crop height > 100 * crop width and rh < crop height.
+ * Limits: 1 <= B <= 65535, 1 <= S <= LPI_RESAMPLE_MAX_SIZE, 1 <= w, h, rw, rh <= LPI_RESAMPLE_MAX_SIDE; the box non-empty inside the image, the window
+ * inside the resized image, flip 0 or 1: anything else is LPI_EINVAL, returned before any launch. */
+#define LPI_RESAMPLE_DESC 12
+#define LPI_RESAMPLE_MAX_SIZE 1024
+#define LPI_RESAMPLE_MAX_SIDE (1L << 24)
+/* *bytes = the workspace lpi_image_resample_u8 needs for these B HOST descriptors: the descriptor table (B * LPI_RESAMPLE_DESC * 8 bytes, rounded up to
+ * 256) + B * S * (4 + KX + KY) * 4 bytes, KX / KY the largest per-image tap count ceil(max(crop / resized, 1)) * 2 + 1 of each axis.  0 or LPI_EINVAL
+ * (invalid descriptors, as above). */
+int lpi_image_resample_workspace(int B, int S, const long* desc, long* bytes);
+/* out[B,3,S,S] uint8 (CHW, contiguous) from the ragged sources in `src` (device, src_bytes bytes), on `stream`.  desc: the HOST descriptor table
+ * [B][LPI_RESAMPLE_DESC], validated here (also against src_bytes) and then copied by this call into the head of the workspace, from where the kernels
+ * read it (pageable desc: free to change once the call returns; pinned desc: unchanged until the stream has passed the copy).  ws: device workspace of
+ * ws_bytes >= lpi_image_resample_workspace's.  One copy and two launches (tap tables, then the resample; a third for images resampled
+ * vertical-first). */
+int lpi_image_resample_u8(int B, int S, const long* desc, const void* src, long src_bytes, void* ws, long ws_bytes, void* out, void* stream);
 
 void* lpi_bpe_create(const char* merges_utf8, long nbytes);
 void lpi_bpe_destroy(void* handle);

@@ -42,3 +42,36 @@ extern "C" int lpi_host_gather(void* dst, const void* const* srcs, int n, long b
     for (auto& th : pool) th.join();
     return 0;
 }
+
+// The ragged form (pixel_format='decoded': images of different sizes): dst = srcs[0][0 .. bytes[0]) ++ srcs[1][0 .. bytes[1]) ++ ..., packed without gaps,
+// on `threads` host threads.  Same rules as lpi_host_gather; rows of 0 bytes are allowed.  Returns 0, or LPI_EINVAL.
+extern "C" int lpi_host_gather_v(void* dst, const void* const* srcs, const long* bytes, int n, int threads) {
+    if (!dst || !srcs || !bytes || n <= 0) return LPI_EINVAL;
+    std::vector<long> row_off(n + 1, 0), unit_off(n + 1, 0);      // byte offset of row i in dst; first work unit of row i
+    for (int i = 0; i < n; ++i) {
+        if (bytes[i] < 0 || (bytes[i] > 0 && !srcs[i])) return LPI_EINVAL;
+        row_off[i + 1] = row_off[i] + bytes[i];
+        unit_off[i + 1] = unit_off[i] + (bytes[i] + CHUNK - 1) / CHUNK;
+    }
+    const long units = unit_off[n];
+    std::atomic<long> next{0};
+    auto work = [&]() {
+        int i = 0;
+        for (;;) {
+            const long u = next.fetch_add(1, std::memory_order_relaxed);
+            if (u >= units) return;
+            while (unit_off[i + 1] <= u) ++i;           // units are claimed in increasing order: the row index only moves forward
+            const long off = (u - unit_off[i]) * CHUNK;
+            const long len = (off + CHUNK <= bytes[i]) ? CHUNK : bytes[i] - off;
+            std::memcpy(static_cast<char*>(dst) + row_off[i] + off, static_cast<const char*>(srcs[i]) + off, (size_t)len);
+        }
+    };
+    int nt = threads < 1 ? 1 : (threads > 64 ? 64 : threads);
+    if ((long)nt > units) nt = units > 0 ? (int)units : 1;
+    std::vector<std::thread> pool;
+    pool.reserve(nt - 1);
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return 0;
+}

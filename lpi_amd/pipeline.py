@@ -12,7 +12,10 @@ step.  At 22 ms per step on an MI355X both would sit on the critical path (a pag
 and the training loop only makes its stream wait for that event (no host synchronisation anywhere).  A device slot is reused once the step that read it
 has been enqueued and its completion event recorded; a staging slot once its copy has finished.  ``images`` stay f32 as the reference's loader
 delivers them (bit-identical input to the f32 patchify kernel) — or uint8 when the dataset hands over decoded pixels (``pixel_format='u8'``: the
-loader's ToTensor + Normalize run inside lpi_patchify_u8, bit for bit, and the copy moves a quarter of the bytes).
+loader's ToTensor + Normalize run inside lpi_patchify_u8, bit for bit, and the copy moves a quarter of the bytes).  With ``pixel_format='decoded'`` the
+loader hands over a DecodedBatch (the decoded images at their own sizes + the transforms' geometry): step 2 packs the ragged images into a pinned byte
+slot (lpi_host_gather_v), step 4 copies them and runs lpi_image_resample_u8 (which copies the checked descriptors itself) on the side stream into a
+uint8 device slot, so the batch handed out is the one 'u8' gives, byte for byte.
 
 Python threads are enough: every heavy part (memcpy, BPE, hipMemcpyAsync) runs in native code with the GIL released; the main thread needs ~4 ms of
 host time per step to enqueue it (profiles/r04: tools/host_ahead.py).
@@ -27,6 +30,7 @@ import time
 import torch
 
 from . import _lib
+from .retrieval.utils.data import DecodedBatch
 
 
 class DeviceBatch:
@@ -39,7 +43,7 @@ class BatchPipeline:
     """Iterate ``loader`` with device-resident batches prepared ``depth`` steps ahead.
 
     loader       any iterable of (images, captions, ...) with images a HOST f32 tensor [B,3,R,R] or a list of B [3,R,R] tensors
-                 (utils.data.collate_keep_images), captions a list of strings or a tensor of token ids;
+                 (utils.data.collate_keep_images), or a utils.data.DecodedBatch (collate_decoded), captions a list of strings or a tensor of token ids;
     prepare_text callable(captions) -> object with .to(device) (engine.PackedIds) or a tensor: runs in the producer thread;
     depth        device / staging slots (>= 2);  threads: host threads of the gather.
     """
@@ -58,6 +62,7 @@ class BatchPipeline:
         self._copied = [None] * self.depth      # event: H2D of the staging slot finished (recorded on the side stream)
         self._done = [None] * self.depth        # event: the step that read the device slot is complete (recorded on the consumer's stream)
         self._retired = []                      # slot buffers replaced by larger ones
+        self._dec = [dict() for _ in range(self.depth)]     # DecodedBatch slots: flat byte buffers that grow by capacity (host / dev / desc / ws / out)
         self._free = threading.Semaphore(self.depth)
         self._q = queue.Queue()
         self._stop = threading.Event()
@@ -90,6 +95,37 @@ class BatchPipeline:
             raise _lib.LpiError(f"lpi_host_gather failed with code {rc}")
         return n
 
+    def _dec_buffer(self, slot, key, nbytes, **kw):
+        """Flat uint8 buffer `key` of DecodedBatch slot `slot` with room for nbytes (grown by a quarter over the need: ragged batches vary)."""
+        buf = self._dec[slot].get(key)
+        if buf is None or buf.numel() < nbytes:
+            if buf is not None:
+                self._retired.append(buf)       # a launch in flight may still read it
+            buf = self._dec[slot][key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, **kw)
+        return buf
+
+    def _stage_decoded(self, slot, images):
+        """Host half of a DecodedBatch: descriptors (validated), the ragged gather into the pinned byte slot."""
+        from . import imageops
+        desc, nbytes = imageops.descriptors(images)
+        ws_bytes = imageops.workspace_bytes(desc, images.size)
+        total = int(nbytes.sum())
+        host = self._dec_buffer(slot, "host", total, pin_memory=True)
+        imageops.gather(images, host, nbytes, self.threads)
+        return desc, total, ws_bytes
+
+    def _issue_decoded(self, slot, images, desc, total, ws_bytes):
+        """Device half, on the side stream: H2D of the bytes, lpi_image_resample_u8 (which copies the validated descriptors into its workspace) into the
+        uint8 output slot."""
+        from . import imageops
+        B, S = len(images), int(images.size)
+        src = self._dec_buffer(slot, "dev", total, device=self.device)
+        ws = self._dec_buffer(slot, "ws", ws_bytes, device=self.device)
+        out = self._dec_buffer(slot, "out", B * 3 * S * S, device=self.device)
+        src[:total].copy_(self._dec[slot]["host"][:total], non_blocking=True)
+        imageops.launch(desc, src, total, ws, ws_bytes, out, S, self.side)
+        return out[:B * 3 * S * S].view(B, 3, S, S)
+
     def _produce(self):
         q, free, stop = self._q, self._free, self._stop      # this pass's hand-over state (a later pass replaces the attributes)
         try:
@@ -108,14 +144,19 @@ class BatchPipeline:
                     if stop.is_set():
                         return
                 slot = index % self.depth
+                decoded = isinstance(images, DecodedBatch)
                 B = images.shape[0] if torch.is_tensor(images) else len(images)
-                one = images[0]
-                shape = (B,) + tuple(one.shape)
                 if self._copied[slot] is not None:
                     self._copied[slot].synchronize()          # the staging slot's previous copy has left the host buffer
-                stage, dev = self._slot_buffers(slot, shape, torch.uint8 if one.dtype == torch.uint8 else torch.float32)
-                t2 = time.perf_counter()
-                self._gather(images, stage)
+                if decoded:
+                    t2 = time.perf_counter()
+                    dec = self._stage_decoded(slot, images)
+                else:
+                    one = images[0]
+                    shape = (B,) + tuple(one.shape)
+                    stage, dev = self._slot_buffers(slot, shape, torch.uint8 if one.dtype == torch.uint8 else torch.float32)
+                    t2 = time.perf_counter()
+                    self._gather(images, stage)
                 t3 = time.perf_counter()
                 text = captions
                 if self.prepare_text is not None:
@@ -128,7 +169,10 @@ class BatchPipeline:
                     e0 = torch.cuda.Event(enable_timing=True) if self.timing else None
                     if e0 is not None:
                         e0.record(self.side)
-                    dev[:B].copy_(stage[:B], non_blocking=True)
+                    if decoded:
+                        dev = self._issue_decoded(slot, images, *dec)        # the kernel runs before `cp` is recorded
+                    else:
+                        dev[:B].copy_(stage[:B], non_blocking=True)
                     if torch.is_tensor(text):
                         text = text.pin_memory().to(self.device, non_blocking=True) if not text.is_cuda else text
                     elif hasattr(text, "to"):

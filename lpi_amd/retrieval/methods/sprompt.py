@@ -117,7 +117,8 @@ class SPrompts(BaseLearner):
         if impl == "coco":          # sprompt.py:163-170
             from lpi_amd.retrieval.utils.data import Coco, CocoEval
             # pixel_format = 'u8': the datasets hand over the decoded uint8 pixels and ToTensor + Normalize run inside the im2col kernel (lpi_patchify_u8:
-            # bit for bit the f32 pipeline, a quarter of the host-to-device bytes)
+            # bit for bit the f32 pipeline, a quarter of the host-to-device bytes); 'decoded': the decoded images at their own sizes + the transforms'
+            # geometry, the crop / resize / flip then run on the GPU too (lpi_image_resample_u8: bit for bit the 'u8' batch)
             pf = self.args.get('pixel_format', 'f32')
             return (Coco(image_root=self.args['image_root'], ann_file=self.args['annotation_train_root'], tasks=[i], pixel_format=pf),
                     CocoEval(image_root=self.args['image_root'], ann_file=self.args['annotation_val_root'], tasks=np.arange(0, i + 1),
@@ -144,20 +145,31 @@ class SPrompts(BaseLearner):
             if _dist_world() > 1:
                 from torch.utils.data.distributed import DistributedSampler
                 sampler = DistributedSampler(train_dataset, shuffle=True, drop_last=True)
-            # single-process loading: the images stay a list and the pipeline gathers them straight into pinned memory (one copy); with worker
-            # processes the batch arrives stacked in shared memory and the pipeline's gather is its pinning copy (no pin_memory thread needed)
-            from lpi_amd.retrieval.utils.data import collate_keep_images
-            self.train_loader = DataLoader(train_dataset, batch_size=self.batch_size, shuffle=sampler is None, sampler=sampler,
-                                           num_workers=self.num_workers, drop_last=sampler is not None,
-                                           collate_fn=collate_keep_images if self.num_workers == 0 else None,
-                                           persistent_workers=self.num_workers > 0)
-            self.test_loader = DataLoader(test_dataset, batch_size=128, shuffle=False, num_workers=self.num_workers, pin_memory=True)
+            self.train_loader, self.test_loader = self._loaders(train_dataset, test_dataset, sampler)
             final_res[i] = self._train(self.train_loader, self.test_loader)
         self.final_res = final_res
         if _dist_rank() == 0:       # every rank holds the same keys and evaluates the same test set: one writer
             os.makedirs('./res', exist_ok=True)
             # the evaluation-transform choice travels with the numbers (utils/data.py CocoEval: 'center' | 'reference')
             self.save_dict({**final_res, 'eval_transform': self.args.get('eval_transform', 'center')}, f'./res/{datetime.now()}.json')
+
+    def _loaders(self, train_dataset, test_dataset, sampler=None):
+        """The task's training and evaluation DataLoaders.  Single-process loading: the images stay a list and the pipeline gathers them straight into
+        pinned memory (one copy); with worker processes the batch arrives stacked in shared memory and the pipeline's gather is its pinning copy (no
+        pin_memory thread needed).  A dataset that yields DecodedImage items (pixel_format = 'decoded': the decoded images at their own sizes;
+        lpi_image_resample_u8 crops / resizes / flips them on the GPU, lpi_amd.imageops) is collated into a DecodedBatch, at any worker count — decided
+        per dataset, since the synthetic evaluation set has no decoded form and keeps its f32 images."""
+        from lpi_amd.retrieval.utils.data import collate_decoded, collate_keep_images
+
+        def decoded(ds):
+            return getattr(ds, 'pixel_format', 'f32') == 'decoded'
+        train_loader = DataLoader(train_dataset, batch_size=self.batch_size, shuffle=sampler is None, sampler=sampler,
+                                  num_workers=self.num_workers, drop_last=sampler is not None,
+                                  collate_fn=collate_decoded if decoded(train_dataset) else (collate_keep_images if self.num_workers == 0 else None),
+                                  persistent_workers=self.num_workers > 0)
+        test_loader = DataLoader(test_dataset, batch_size=128, shuffle=False, num_workers=self.num_workers, pin_memory=True,
+                                 collate_fn=collate_decoded if decoded(test_dataset) else None)
+        return train_loader, test_loader
 
     def state_dict(self):
         """What a continual run carries from task to task besides the frozen backbone (the reference's BaseLearner.save_checkpoint,
@@ -230,9 +242,13 @@ class SPrompts(BaseLearner):
 
         def plain():
             from types import SimpleNamespace
+            from lpi_amd.imageops import resample_decoded
+            from lpi_amd.retrieval.utils.data import DecodedBatch
             for item in train_loader:
                 images, captions = item[0], item[1]
-                if not torch.is_tensor(images):
+                if isinstance(images, DecodedBatch):
+                    images = resample_decoded(images, device=self._device)
+                elif not torch.is_tensor(images):
                     images = torch.stack(list(images))
                 yield SimpleNamespace(images=images.to(self._device, non_blocking=True), text=captions if torch.is_tensor(captions) else list(captions))
         return plain()
@@ -311,10 +327,14 @@ class SPrompts(BaseLearner):
         impl = self.args.get("kmeans_impl", "hip")
         if impl not in ("hip", "sklearn"):
             raise ValueError(f"unknown kmeans_impl {impl!r} (hip | sklearn)")
+        from lpi_amd.imageops import resample_decoded
+        from lpi_amd.retrieval.utils.data import DecodedBatch
         vf, tf = [], []
         for item in dataloader:
             inputs, captions = item[0], item[1]
-            if not torch.is_tensor(inputs):
+            if isinstance(inputs, DecodedBatch):
+                inputs = resample_decoded(inputs, device=self._device)
+            elif not torch.is_tensor(inputs):
                 inputs = torch.stack(list(inputs))
             with torch.no_grad():
                 v = self._network.extract_vector(inputs.to(self._device))
@@ -354,8 +374,10 @@ class SPrompts(BaseLearner):
         num_text = len(texts)
         text_bs = 256
         image_feats, category_i = [], []
+        from lpi_amd.imageops import resample_decoded
+        from lpi_amd.retrieval.utils.data import DecodedBatch
         for image, img_id, category in data_loader:
-            image = image.to(self._device)
+            image = resample_decoded(image, device=self._device) if isinstance(image, DecodedBatch) else image.to(self._device)
             selection = self.get_visual_task_id(image)
             image_feats.append(self._network.visual_interface(image, selection))
             category_i.extend(int(z) for z in category)

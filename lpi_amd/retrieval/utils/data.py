@@ -37,14 +37,15 @@ class SyntheticCoco(Dataset):
     COCO-like words (lpi_amd.synth_bpe.captions) — the item then has exactly the reference's structure (utils/data.py:376-382: f32 image, str, 0, task) and
     the step tokenises it like PromptLearner.forward does.
     pixel_format = 'u8': items carry uint8 CHW pixels (uniform bytes) and ToTensor + Normalize run on the GPU (lpi_patchify_u8).
+    pixel_format = 'decoded': items carry a DecodedImage: seeded uniform-byte HWC images of random size (64..900 px a side) and train_crop_params for a
+    `resolution` output (the crop / resize / flip then run on the GPU: lpi_amd.imageops).
     image_pool = K > 0: the K distinct images are generated once and item i returns pool image i % K (a VIEW: the collate / pipeline copies it) — an
     item costs nothing, so that a throughput measurement of the training loop times the loop and not numpy's generator (150 k normals per image)."""
 
     def __init__(self, n, tasks, resolution=224, seed=0, captions="ids", image_pool=0, pixel_format="f32"):
         if captions not in ("ids", "strings"):
             raise ValueError(f"captions must be 'ids' or 'strings', not {captions!r}")
-        if pixel_format not in ("f32", "u8"):
-            raise ValueError(f"pixel_format must be 'f32' or 'u8', not {pixel_format!r}")
+        _check_pixel_format(pixel_format)
         self.pixel_format = pixel_format
         self.n, self.tasks, self.res = n, list(tasks), resolution
         self.seed = seed
@@ -55,7 +56,9 @@ class SyntheticCoco(Dataset):
             from lpi_amd.synth_bpe import captions as make
             self.ids, self.captions = None, make(n, seed=synth.TOKEN_SEED + 17 * seed)
         k = min(int(image_pool), n) if image_pool else 0
-        if pixel_format == "u8":          # uniform bytes: "decoded pixels"; pixel_format='f32' of the same dataset = their ToTensor + Normalize
+        if pixel_format == "decoded":     # image i: its own seeded size and bytes (image i % K of a pool of K, made once)
+            self.pool = [self._decoded(j) for j in range(k)] if k else None
+        elif pixel_format == "u8":          # uniform bytes: "decoded pixels"; pixel_format='f32' of the same dataset = their ToTensor + Normalize
             k = k or n
             self.pool = torch.from_numpy(synth._rng(synth.IMAGE_SEED + seed, f"u8pool{k}").integers(0, 256, (k, 3, resolution, resolution), dtype=np.uint8))
         else:
@@ -64,8 +67,16 @@ class SyntheticCoco(Dataset):
     def __len__(self):
         return self.n
 
+    def _decoded(self, j):
+        rng = synth._rng(synth.IMAGE_SEED + self.seed, f"decoded{j}")
+        w, h = (int(v) for v in rng.integers(64, 901, 2))
+        return torch.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
+
     def __getitem__(self, i):
-        if self.pool is not None:
+        if self.pixel_format == "decoded":
+            px = self.pool[i % len(self.pool)] if self.pool is not None else self._decoded(i)
+            img = DecodedImage(px, train_crop_params(int(px.shape[1]), int(px.shape[0]), self.res), self.res)
+        elif self.pool is not None:
             img = self.pool[i % self.pool.shape[0]]
         else:
             img = torch.from_numpy(synth.normal(synth.IMAGE_SEED + self.seed, f"img{i}", (3, self.res, self.res)))
@@ -79,6 +90,64 @@ def collate_keep_images(batch):
     from torch.utils.data import default_collate
     cols = list(zip(*batch))
     return [list(cols[0])] + [default_collate(list(c)) for c in cols[1:]]
+
+
+class DecodedImage:
+    """An item's image in pixel_format='decoded': the decoded RGB pixels at their original size (``pixels``: HWC uint8, np.array(img.convert("RGB"))
+    as a tensor, not copied to CHW) and the transform's geometry (``params``: the DESCRIPTOR_FIELDS tuple of train_crop_params / test_crop_params)
+    for an S x S output (``size``).  lpi_amd.imageops.resample_decoded runs the crop / bilinear resize / flip on the GPU."""
+    __slots__ = ("pixels", "params", "size")
+
+    def __init__(self, pixels, params, size):
+        if not torch.is_tensor(pixels) or pixels.dtype != torch.uint8 or pixels.dim() != 3 or pixels.shape[2] != 3:
+            raise ValueError("DecodedImage.pixels must be an HWC uint8 tensor with 3 channels")
+        h, w = int(pixels.shape[0]), int(pixels.shape[1])
+        self.pixels, self.size = pixels, int(size)
+        x0, y0, x1, y1, rw, rh, ox, oy, flip = params
+        self.params = resample_descriptor(w, h, (x0, y0, x1, y1), (rw, rh), (ox, oy), flip, size)
+
+    def __reduce__(self):
+        return (DecodedImage, (self.pixels, self.params, self.size))
+
+
+class DecodedBatch:
+    """A batch of DecodedImage: ``pixels`` a list of B HWC uint8 tensors (ragged), ``params`` the [B, 9] int64 descriptor table, ``size`` S."""
+    __slots__ = ("pixels", "params", "size")
+
+    def __init__(self, pixels, params, size):
+        self.pixels, self.params, self.size = list(pixels), params, int(size)
+
+    def __len__(self):
+        return len(self.pixels)
+
+    def __reduce__(self):
+        return (DecodedBatch, (self.pixels, self.params, self.size))
+
+    def pin_memory(self, device=None):
+        return DecodedBatch([p.pin_memory() for p in self.pixels], self.params.pin_memory(), self.size)
+
+
+def collate_decoded(batch):
+    """Collate of pixel_format='decoded' items ``(DecodedImage, ...)``: the images become one DecodedBatch (no pixel is copied), every other field goes
+    through default_collate.  Works in worker processes (the batch pickles, its tensors travel in shared memory) and with pin_memory=True."""
+    from torch.utils.data import default_collate
+    cols = list(zip(*batch))
+    imgs = cols[0]
+    if not all(isinstance(d, DecodedImage) for d in imgs):
+        raise ValueError("collate_decoded takes items whose first field is a DecodedImage (pixel_format='decoded')")
+    size = imgs[0].size
+    if any(d.size != size for d in imgs):
+        raise ValueError("collate_decoded: the items of one batch must share the output size S")
+    params = torch.tensor([d.params for d in imgs], dtype=torch.int64).view(len(imgs), len(DESCRIPTOR_FIELDS))
+    return [DecodedBatch([d.pixels for d in imgs], params, size)] + [default_collate(list(c)) for c in cols[1:]]
+
+
+PIXEL_FORMATS = ("f32", "u8", "decoded")
+
+
+def _check_pixel_format(pixel_format):
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format must be 'f32', 'u8' or 'decoded', not {pixel_format!r}")
 
 
 class SyntheticCocoEval(Dataset):
@@ -150,11 +219,10 @@ def _to_normalised_tensor(img):
     return (a - mean) / std
 
 
-def train_transform(img, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), pixel_format="f32"):
-    """RandomResizedCrop(size) + RandomHorizontalFlip + ToTensor + Normalize (utils/data.py:193-204), torch RNG: a crop of random area
-    (scale x image area) and log-uniform aspect ratio, ten attempts, else the largest centred crop inside the ratio bounds; bilinear."""
-    Image = _pil()
-    w, h = img.size
+def train_crop_params(w, h, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """The random draws of train_transform (RandomResizedCrop + RandomHorizontalFlip, torch RNG, in this order): a crop of random area (scale x image
+    area) and log-uniform aspect ratio, ten attempts, else the largest centred crop inside the ratio bounds; then the flip's torch.rand(1).
+    Returns the descriptor of the image (see resample_descriptor): crop box, resized to (size, size), window at (0, 0), flip flag."""
     area = w * h
     box = None
     for _ in range(10):
@@ -177,23 +245,68 @@ def train_transform(img, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.
             cw, ch = w, h
         left, top = (w - cw) // 2, (h - ch) // 2
         box = (left, top, left + cw, top + ch)
-    img = img.crop(box).resize((size, size), Image.BILINEAR)
-    if float(torch.rand(1)) < 0.5:
-        img = img.transpose(Image.FLIP_LEFT_RIGHT)
-    return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img)
+    flip = float(torch.rand(1)) < 0.5
+    return resample_descriptor(w, h, box, (size, size), (0, 0), flip, size)
 
 
-def test_transform(img, resize=256, size=224, pixel_format="f32"):
-    """Resize(256) (shorter side, bilinear) + CenterCrop(224) + ToTensor + Normalize (utils/data.py:197-204)."""
-    Image = _pil()
-    w, h = img.size
+def test_crop_params(w, h, resize=256, size=224):
+    """The geometry of test_transform (Resize(resize) of the shorter side + CenterCrop(size)): the whole image resized to (nw, nh), the window at the
+    centre-crop origin, no flip.  No random draws."""
     if w <= h:
         nw, nh = resize, int(resize * h / w)
     else:
         nw, nh = int(resize * w / h), resize
-    img = img.resize((nw, nh), Image.BILINEAR)
     left, top = int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
-    img = img.crop((left, top, left + size, top + size))
+    return resample_descriptor(w, h, (0, 0, w, h), (nw, nh), (left, top), False, size)
+
+
+# one image's geometry, the row of a DecodedBatch's descriptor table: crop(box).resize((rw, rh), BILINEAR), the window [ox, ox+S) x [oy, oy+S), mirrored if flip
+DESCRIPTOR_FIELDS = ("x0", "y0", "x1", "y1", "rw", "rh", "ox", "oy", "flip")
+
+
+def resample_descriptor(w, h, box, resized, origin, flip, size):
+    """Validated descriptor tuple (DESCRIPTOR_FIELDS) of a w x h image; ValueError when the box leaves the image, a size is not positive, or the S x S
+    window leaves the resized image."""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    rw, rh = (int(v) for v in resized)
+    ox, oy = (int(v) for v in origin)
+    size, w, h = int(size), int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError(f"image size must be positive, not {w} x {h}")
+    if size < 1:
+        raise ValueError(f"output size S must be >= 1, not {size}")
+    if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):
+        raise ValueError(f"crop box {(x0, y0, x1, y1)} is empty or leaves the {w} x {h} image")
+    if rw < 1 or rh < 1:
+        raise ValueError(f"resized size must be positive, not {rw} x {rh}")
+    if not (0 <= ox and ox + size <= rw and 0 <= oy and oy + size <= rh):
+        raise ValueError(f"the {size} x {size} window at {(ox, oy)} leaves the {rw} x {rh} resized image")
+    return (x0, y0, x1, y1, rw, rh, ox, oy, int(bool(flip)))
+
+
+def apply_descriptor(img, desc, size):
+    """The descriptor applied with Pillow: the PIL image the transforms produce (the GPU kernel lpi_image_resample_u8 reproduces it byte for byte)."""
+    Image = _pil()
+    x0, y0, x1, y1, rw, rh, ox, oy, flip = desc
+    img = img.crop((x0, y0, x1, y1)).resize((rw, rh), Image.BILINEAR)
+    if (ox, oy, rw, rh) != (0, 0, size, size):
+        img = img.crop((ox, oy, ox + size, oy + size))
+    if flip:
+        img = img.transpose(Image.FLIP_LEFT_RIGHT)
+    return img
+
+
+def train_transform(img, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), pixel_format="f32"):
+    """RandomResizedCrop(size) + RandomHorizontalFlip + ToTensor + Normalize (utils/data.py:193-204), torch RNG (train_crop_params); bilinear."""
+    w, h = img.size
+    img = apply_descriptor(img, train_crop_params(w, h, size, scale, ratio), size)
+    return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img)
+
+
+def test_transform(img, resize=256, size=224, pixel_format="f32"):
+    """Resize(256) (shorter side, bilinear) + CenterCrop(224) + ToTensor + Normalize (utils/data.py:197-204; test_crop_params)."""
+    w, h = img.size
+    img = apply_descriptor(img, test_crop_params(w, h, resize, size), size)
     return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img)
 
 
@@ -203,15 +316,32 @@ def _load(image_root, name, transform):
         return transform(im.convert("RGB"))
 
 
+def decoded_transform(form, size=224, resize=256):
+    """The transform of pixel_format='decoded': PIL image -> DecodedImage(HWC pixels, descriptor of form 'train' (train_crop_params: the random draws
+    happen here, in the order of train_transform) or 'center' (test_crop_params))."""
+    if form not in ("train", "center"):
+        raise ValueError(f"form must be 'train' or 'center', not {form!r}")
+
+    def transform(img):
+        w, h = img.size
+        desc = train_crop_params(w, h, size) if form == "train" else test_crop_params(w, h, resize, size)
+        # np.asarray of a PIL image is a read-only view of a bytes object: np.array takes a writable copy (0.1 ms for 640 x 480)
+        return DecodedImage(torch.from_numpy(np.array(img if img.mode == "RGB" else img.convert("RGB"), dtype=np.uint8)), desc, size)
+    return transform
+
+
 class Coco(Dataset):
     """Training pairs of the given tasks (utils/data.py:308-382): item = (image, prompt + pre_caption(caption), 0, task)."""
 
-    def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, prompt='', tasks=(0,), replay_list=(), pixel_format="f32"):
+    def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, prompt='', tasks=(0,), replay_list=(), pixel_format="f32",
+                 size=224):
         _pil()
-        if pixel_format not in ("f32", "u8"):
-            raise ValueError(f"pixel_format must be 'f32' or 'u8', not {pixel_format!r}")
+        _check_pixel_format(pixel_format)
         if transform is None and pixel_format == "u8":
             transform = lambda im: train_transform(im, pixel_format="u8")  # noqa: E731
+        if transform is None and pixel_format == "decoded":      # size: the S of the decoded path's output (the default transforms' 224)
+            transform = decoded_transform("train", size)
+        self.pixel_format = pixel_format
         with open(ann_file, 'r') as f:
             records = json.load(f)
         cats = {TASK_CATEGORIES[int(t)] for t in tasks}
@@ -238,13 +368,17 @@ class CocoEval(Dataset):
     """Evaluation images of tasks 0..t with every caption of every image in the lookup tables the scoring loop reads
     (utils/data.py:186-306; sprompt.py:433-548): text, text_cat, image, txt2img, img2txt; item = (image, image index, task)."""
 
-    def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, tasks=(0,), eval_transform='center', pixel_format="f32"):
+    def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, tasks=(0,), eval_transform='center', pixel_format="f32",
+                 size=224, resize=256):
         _pil()
-        if pixel_format not in ("f32", "u8"):
-            raise ValueError(f"pixel_format must be 'f32' or 'u8', not {pixel_format!r}")
+        _check_pixel_format(pixel_format)
         if transform is None and pixel_format == "u8":
             base = test_transform if eval_transform == 'center' else train_transform
             transform = lambda im: base(im, pixel_format="u8")  # noqa: E731
+        if transform is None and pixel_format == "decoded" and eval_transform in ('center', 'reference'):
+            # size / resize: the S and Resize of the decoded path (the default transforms' 224 / 256); 'reference' takes the training form
+            transform = decoded_transform("center" if eval_transform == 'center' else "train", size, resize)
+        self.pixel_format = pixel_format
         with open(ann_file, 'r') as f:
             records = json.load(f)
         cats = {TASK_CATEGORIES[int(t)] for t in tasks}

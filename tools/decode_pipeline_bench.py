@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""pixel_format='u8' against 'decoded' on real COCO-format JPEGs (seeded synthetic 640 x 480 q90 images written to a temporary folder):
+
+  1. host ms per item of the datasets (decode + transform + hand-over), train (Coco) and eval (CocoEval, Resize(256) + CenterCrop(224)), one process;
+  2. lpi_image_resample_u8 for a 256-image batch of those items: HIP events around the call (descriptor copy + launches), warm-up, median of 30;
+  3. the plugin loop (SPrompts.train_epoch, ViT-B/16 bf16, 256 pairs, BatchPipeline) over the folder: pairs/s with num_workers 0 / 8 / 14, in steady
+     state: the untimed warm-up is longer than the DataLoader's prefetch queue (prefetch_factor 2 x workers batches), so the timed steps wait for
+     batches the workers make while they are timed.
+
+usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--out FILE.json]
+Prints one JSON object (and writes it to --out)."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from torch.utils.data import DataLoader  # noqa: E402
+
+from lpi_amd import imageops  # noqa: E402
+from lpi_amd.retrieval.utils import data as D  # noqa: E402
+
+
+def write_folder(root, n_files, n_train, n_val):
+    from PIL import Image
+    rng = np.random.default_rng(0)
+    for i in range(n_files):
+        # smooth-ish content (a JPEG of uniform noise decodes slower than a photo): low-resolution noise upsampled, plus a little grain
+        base = rng.integers(0, 256, (30, 40, 3), dtype=np.uint8)
+        im = Image.fromarray(base).resize((640, 480), Image.BILINEAR)
+        a = np.asarray(im).astype(np.int16) + rng.integers(-8, 9, (480, 640, 3))
+        Image.fromarray(np.clip(a, 0, 255).astype(np.uint8)).save(os.path.join(root, f"im{i}.jpg"), quality=90)
+    train = [{"image": f"im{i % n_files}.jpg", "caption": f"a photo of a thing number {i}", "category": 11, "image_id": f"coco_{i}"} for i in range(n_train)]
+    val = [{"image": f"im{i % n_files}.jpg", "caption": [f"first caption {i}", f"second caption {i}"], "category": 11, "image_id": i} for i in range(n_val)]
+    json.dump(train, open(os.path.join(root, "train.json"), "w"))
+    json.dump(val, open(os.path.join(root, "val.json"), "w"))
+
+
+def host_ms(ds, n):
+    torch.manual_seed(0)
+    ds[0]
+    t0 = time.perf_counter()
+    for i in range(n):
+        ds[i % len(ds)]
+    return 1e3 * (time.perf_counter() - t0) / n
+
+
+def kernel_us(ds, dev, reps=30, warm=5):
+    torch.manual_seed(0)
+    batch = D.collate_decoded([ds[i % len(ds)] for i in range(256)])[0]
+    desc, nbytes = imageops.descriptors(batch)
+    ws_bytes = imageops.workspace_bytes(desc, batch.size)
+    stage = torch.empty(int(nbytes.sum()), dtype=torch.uint8, pin_memory=True)
+    imageops.gather(batch, stage, nbytes, 8)
+    src = stage.to(dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((256, 3, batch.size, batch.size), dtype=torch.uint8, device=dev)
+    s = torch.cuda.current_stream(dev)
+    times = []
+    for r in range(warm + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        imageops.launch(desc, src, int(nbytes.sum()), ws, ws_bytes, out, batch.size, s)
+        e1.record(s)
+        e1.synchronize()
+        if r >= warm:
+            times.append(1e3 * e0.elapsed_time(e1))
+    return {"median_us": round(float(np.median(times)), 1), "p10_p90_us": [round(float(np.percentile(times, q)), 1) for q in (10, 90)],
+            "source_MB": round(float(nbytes.sum()) / 1e6, 1), "reps": reps, "warmup": warm}
+
+
+def loop_pairs_per_s(root, pf, workers, steps, warm, dev):
+    from lpi_amd.retrieval.methods.sprompt import SPrompts
+    args = json.load(open(os.path.join(REPO, "lpi_amd", "retrieval", "configs", "lpi", "coco_lpi.json")))
+    args.update(device=[dev], compute_dtype="bf16", honor_prompt_depth=True, prompt_depth=3, batch_size=256, epochs=1, num_workers=workers,
+                pixel_format=pf)
+    m = SPrompts(args)
+    m._network.update_fc(0)
+    ds = D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf)
+    collate = D.collate_decoded if pf == "decoded" else (D.collate_keep_images if workers == 0 else None)
+    loader = DataLoader(ds, batch_size=256, shuffle=False, num_workers=workers, collate_fn=collate, persistent_workers=False)
+    opt, _ = m._setup_training()
+    t = {}
+
+    def on_step(i, b, o):
+        if i == warm - 1:
+            torch.cuda.synchronize()
+            t[0] = time.perf_counter()
+        if i == warm + steps - 1:
+            torch.cuda.synchronize()
+            t[1] = time.perf_counter()
+            return True
+        return False
+    m.train_epoch(loader, opt, 0, None, on_step)
+    del m
+    return {"pairs_per_s": round(256 * steps / (t[1] - t[0]), 1), "timed_steps": steps, "warmup_steps": warm,
+            "prefetch_queue_batches": 2 * workers if workers else 0}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=16)
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps; at least prefetch_factor (2) x workers + 2 whatever this says")
+    ap.add_argument("--workers", default="0,8,14")
+    ap.add_argument("--host-items", type=int, default=200)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from lpi_amd.synth_bpe import ensure_vocab
+    ensure_vocab()
+    dev = torch.device("cuda:0")
+    rec = {"tool": "tools/decode_pipeline_bench.py", "source": "640 x 480 q90 JPEG", "batch": 256, "host_threads": torch.get_num_threads()}
+    with tempfile.TemporaryDirectory() as root:
+        workers = [int(x) for x in a.workers.split(",")]
+        warm = {w: max(a.warmup, 2 * w + 2) for w in workers}
+        write_folder(root, a.images, 256 * (a.steps + max(warm.values()) + 1), 256)
+        tr = {pf: D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf) for pf in ("u8", "decoded")}
+        ev = {pf: D.CocoEval(image_root=root, ann_file=os.path.join(root, "val.json"), tasks=[0], pixel_format=pf) for pf in ("u8", "decoded")}
+        rec["host_ms_per_item"] = {f"{form}_{pf}": round(host_ms(ds[pf], a.host_items), 3) for form, ds in (("train", tr), ("eval", ev))
+                                   for pf in ("u8", "decoded")}
+        for form in ("train", "eval"):
+            u, d = rec["host_ms_per_item"][f"{form}_u8"], rec["host_ms_per_item"][f"{form}_decoded"]
+            rec[f"host_saving_{form}"] = round(1.0 - d / u, 3)
+        rec["kernel_256"] = {"train": kernel_us(tr["decoded"], dev), "eval": kernel_us(ev["decoded"], dev)}
+        rec["loop_pairs_per_s"] = {}
+        for w in workers:
+            for pf in ("u8", "decoded"):
+                rec["loop_pairs_per_s"][f"{pf}_workers{w}"] = loop_pairs_per_s(root, pf, w, a.steps, warm[w], dev)
+                print(json.dumps({f"{pf}_workers{w}": rec["loop_pairs_per_s"][f"{pf}_workers{w}"]}), flush=True)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
