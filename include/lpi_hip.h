@@ -610,6 +610,32 @@ int lpi_image_resample_workspace(int B, int S, const long* desc, long* bytes);
  * vertical-first). */
 int lpi_image_resample_u8(int B, int S, const long* desc, const void* src, long src_bytes, void* ws, long ws_bytes, void* out, void* stream);
 
+/* ---- baseline JPEG decoding on the GPU (jpeg.hip)      replaces: Image.open(f).convert("RGB") of the data transforms (pixel_format='jpeg',
+ * lpi_amd/imageops.py).  The output of every file is np.asarray(Image.open(f).convert("RGB")) under Pillow 12 (libjpeg-turbo: islow IDCT, fancy
+ * upsampling, its YCbCr tables), byte for byte.
+ * THE ENVELOPE (decided from the headers, here only): SOF0 / SOF1, 8-bit samples, Huffman coding, one scan holding every component in the
+ * frame's order (Ss 0, Se 63, Ah = Al = 0); 1 component, or 3 that libjpeg reads as YCbCr (a JFIF APP0, or no Adobe APP14 and ids other than 'R','G','B') with luma sampling 1x1,
+ * 2x1 or 2x2 and chroma 1x1; any DQT precision, up to 4 tables of each kind, restart intervals; at most LPI_JPEG_MAX_PIXELS pixels and
+ * LPI_JPEG_MAX_SCAN_BYTES bytes from the scan's start to the end of the file.  Anything else is the host's (Pillow's). */
+#define LPI_JPEG_INFO 8
+#define LPI_JPEG_MAX_PIXELS (1L << 28)
+#define LPI_JPEG_MAX_SCAN_BYTES (1L << 27)
+/* Host only (no GPU call): info[LPI_JPEG_INFO] = {inside the envelope (1) or not (0), width, height, components, luma H, luma V, restart interval,
+ * offset of the entropy-coded data}.  A file that does not start with SOI is {0, 0, 0, ...}.  0, or LPI_EINVAL for a structural error of the headers
+ * (truncated, a bad segment length, a scan that names an undefined table, a bad Huffman table, ...). */
+int lpi_jpeg_info(const void* data, long nbytes, long* info);
+/* *bytes = the device workspace lpi_jpeg_decode_u8 needs for the B files packed in the HOST buffer `host` (file i = bytes [offsets[i], offsets[i+1])).
+ * 0, or LPI_EINVAL (a file outside the envelope or with a structural error). */
+int lpi_jpeg_decode_workspace(int B, const void* host, const long* offsets, long* bytes);
+/* Decodes the B files on `stream`: file i is bytes [offsets[i], offsets[i+1]) of both `host` (parsed here, before any launch) and `src` (its device
+ * copy, src_bytes bytes); its h x w x 3 RGB output is written at byte out_off[i] (HOST array) of `out` (device, out_bytes).  status: device int[B],
+ * 0 when image i decoded exactly its MCUs, else a nonzero mask (1 premature end of data, 2 invalid Huffman code, 4 coefficient index past 63, 8 block
+ * count mismatch, 16 restart markers missing or out of order): the caller then decodes that file on the host.  ws: device workspace of ws_bytes >=
+ * lpi_jpeg_decode_workspace's; this call copies the descriptors and tables into it.  One copy, one clear and four launches.  LPI_EINVAL before any launch
+ * for a file outside the envelope, a structural error, an output outside `out`, or a workspace too small. */
+int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out, long out_bytes,
+                       int* status, void* ws, long ws_bytes, void* stream);
+
 void* lpi_bpe_create(const char* merges_utf8, long nbytes);
 void lpi_bpe_destroy(void* handle);
 int lpi_bpe_encode(void* handle, const char* text_utf8, int32_t* ids, int max_ids);

@@ -1,0 +1,914 @@
+// Baseline JPEG files -> packed HWC RGB uint8 pixels on the GPU (pixel_format='jpeg', lpi_amd/imageops.py), byte for byte what Pillow 12
+// (libjpeg-turbo, default settings) gives for np.asarray(Image.open(f).convert("RGB")).  tests/jpeg_restate.py restates every step in numpy.
+//
+// The host parses the headers (parse_headers: the one place that decides the envelope), builds one JDesc per image and copies the table into the
+// workspace; four launches then do the rest:
+//   unstuff_kernel   one workgroup per image: the entropy-coded bytes without the 0xFF00 stuffing, split at the RSTn markers, up to the first other
+//                    marker (rounds of 4096 bytes, a block-wide scan per round).  Out: the unstuffed bytes and the end of every restart interval.
+//   huff_kernel      one workgroup per image: Huffman decoding.  Every restart interval (segment) is cut into k chunks.  A chunk's decoder state at
+//                    a symbol boundary is (bit position, next coefficient index, block within the MCU).  The first chunk of a segment starts from the
+//                    exact state; the others start speculatively at their first bit and run to their end.  Then each chunk re-decodes from its
+//                    predecessor's exit state, until no exit state changes (self-synchronising decoding, Weissenberger & Schmidt): at most k
+//                    rounds.  Block counts and DC sums per chunk give each chunk its first block and its DC predictors; a final pass writes the
+//                    quantised coefficients.  A segment whose chunks do not add up to its MCUs, an invalid code, a coefficient index past 63, or
+//                    a read past the segment's end sets the image's status: the caller then decodes that file on the host.
+//   idct_kernel      one thread per 8x8 block: jidctint.c's islow IDCT with its range limit -> the component's sample plane.
+//   color_kernel     one thread per output pixel: jdsample.c's fancy upsampling of the chroma planes (2x1, 2x2; plain replication for chroma
+//                    planes at most 2 samples wide), jdcolor.c's YCbCr -> RGB tables; grayscale replicated into R, G, B.
+//
+// Bounds: every loop runs over counts the host validated (rounds over the entropy bytes, symbols at most one per bit of a chunk, sync rounds at
+// most k + 1); the bit reader reads only its own image's unstuffed bytes and returns zeros past its segment's end.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;             // threads of the per-image workgroups of unstuff_kernel
+constexpr int HT = 1024;            // threads of huff_kernel's per-image workgroups: up to HT chunks per image
+constexpr int ROUND = NT * 16;      // entropy bytes per round of unstuff_kernel
+constexpr int MIN_CHUNK = 64;       // bytes: shortest chunk the speculative decoder splits a segment into
+constexpr int LUT_BITS = 9;
+
+enum { ST_EOD = 1, ST_CODE = 2, ST_INDEX = 4, ST_COUNT = 8, ST_RST = 16 };
+
+struct HuffSpec {
+    uint8_t bits[16];
+    uint8_t vals[256];
+};
+
+// One image (device copy in the workspace's head).  Offsets: src_* into the caller's device bytes, out into the caller's output, ws_* into the
+// workspace.
+struct JDesc {
+    long src_ent, src_end;          // entropy-coded bytes [src_ent, src_end) of the file
+    long out;                       // first byte of the h x w x 3 output
+    long ws_unst, unst_cap;         // unstuffed bytes (capacity: src_end - src_ent + 16)
+    long ws_seg;                    // int32 end (unstuffed byte) of every segment
+    long ws_coef[3];                // int16 [blocks][64] of each frame component
+    long ws_plane[3];               // uint8 sample plane of each frame component
+    int w, h, nc, mcux, mcuy, ri, nseg, bpm;
+    int bw[3], bh[3];               // block grid of each frame component
+    int blk_comp[10];               // scan component of block b of an MCU
+    int blk_dx[10], blk_dy[10];     // its position inside the MCU's share of that component
+    int scomp[3];                   // frame component of scan component s
+    int hs, vs;                     // luma sampling (1,1), (2,1), (2,2); 1,1 for grayscale
+    int dw, dh;                     // chroma downsampled size
+    int k;                          // chunks per segment
+    uint16_t qt[3][64];             // dequantisation table of each frame component, natural order
+    HuffSpec dc[3], ac[3];          // tables of each scan component
+};
+
+__device__ __constant__ int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const int kZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ------------------------------------------------------------------------------------------------------------------------------ host parser
+struct Header {
+    int w = 0, h = 0, nc = 0, prec = 0;
+    int cid[4] = {}, ch[4] = {}, cv[4] = {}, ctq[4] = {};
+    int ns = 0, sc[4] = {}, std_[4] = {}, sta[4] = {};
+    int ri = 0;
+    bool jfif = false, adobe = false, sof = false;
+    bool qdef[4] = {}, hdef[2][4] = {};
+    uint16_t qt[4][64] = {};
+    HuffSpec hs[2][4] = {};
+    long ent = 0;
+    bool gpu = false;       // inside the envelope
+};
+
+inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+bool huff_ok(const HuffSpec& t, int count, bool dc) {
+    long code = 0;
+    for (int l = 0; l < 16; ++l) {
+        code += t.bits[l];
+        if (code >= (1L << (l + 1))) return false;     // jpeg_make_d_derived_tbl: the all-ones code is not a code
+        code <<= 1;
+    }
+    if (dc)
+        for (int i = 0; i < count; ++i)
+            if (t.vals[i] > 15) return false;
+    return true;
+}
+
+// 0: parsed (hd.gpu says whether the GPU decodes it); LPI_EINVAL: a structural error in the headers.  A file without SOI is parsed as "host".
+int parse_headers(const uint8_t* d, long n, Header& hd) {
+    hd = Header();
+    if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 0;
+    long p = 2;
+    for (int guard = 0; guard < (1 << 20); ++guard) {
+        while (p + 1 < n && d[p] == 0xFF && d[p + 1] == 0xFF) ++p;
+        if (p + 4 > n || d[p] != 0xFF) return LPI_EINVAL;
+        const int m = d[p + 1];
+        if (m == 0xD8 || m == 0xD9 || (m >= 0xD0 && m <= 0xD7) || m == 0x01 || m == 0x00) return LPI_EINVAL;
+        const long L = rd16(d + p + 2);
+        if (L < 2 || p + 2 + L > n) return LPI_EINVAL;
+        const uint8_t* s = d + p + 4;
+        const long sl = L - 2;
+        p += 2 + L;
+        if (m == 0xC0 || m == 0xC1) {
+            if (hd.sof || sl < 6) return LPI_EINVAL;
+            hd.prec = s[0];
+            hd.h = rd16(s + 1);
+            hd.w = rd16(s + 3);
+            hd.nc = s[5];
+            if (hd.nc < 1 || hd.nc > 4 || sl != 6 + 3 * hd.nc || hd.w == 0) return LPI_EINVAL;
+            for (int i = 0; i < hd.nc; ++i) {
+                hd.cid[i] = s[6 + 3 * i];
+                hd.ch[i] = s[7 + 3 * i] >> 4;
+                hd.cv[i] = s[7 + 3 * i] & 15;
+                hd.ctq[i] = s[8 + 3 * i];
+                if (hd.ch[i] < 1 || hd.ch[i] > 4 || hd.cv[i] < 1 || hd.cv[i] > 4 || hd.ctq[i] > 3) return LPI_EINVAL;
+            }
+            hd.sof = true;
+        } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            if (sl >= 6) {                                      // progressive, lossless, arithmetic-coded, hierarchical: the host decodes
+                hd.h = rd16(s + 1);
+                hd.w = rd16(s + 3);
+                hd.nc = s[5];
+            }
+            return 0;
+        } else if (m == 0xCC) {
+            return 0;                                           // arithmetic conditioning tables
+        } else if (m == 0xC4) {
+            long q = 0;
+            while (q < sl) {
+                if (q + 17 > sl) return LPI_EINVAL;
+                const int tc = s[q] >> 4, th = s[q] & 15;
+                int cnt = 0;
+                for (int l = 0; l < 16; ++l) cnt += s[q + 1 + l];
+                if (tc > 1 || th > 3 || cnt > 256 || q + 17 + cnt > sl) return LPI_EINVAL;
+                HuffSpec& t = hd.hs[tc][th];
+                std::memset(&t, 0, sizeof(t));
+                std::memcpy(t.bits, s + q + 1, 16);
+                std::memcpy(t.vals, s + q + 17, (size_t)cnt);
+                if (!huff_ok(t, cnt, tc == 0)) return LPI_EINVAL;
+                hd.hdef[tc][th] = true;
+                q += 17 + cnt;
+            }
+        } else if (m == 0xDB) {
+            long q = 0;
+            while (q < sl) {
+                const int pq = s[q] >> 4, tq = s[q] & 15;
+                const long size = 64L * (pq + 1);
+                if (pq > 1 || tq > 3 || q + 1 + size > sl) return LPI_EINVAL;
+                for (int i = 0; i < 64; ++i) hd.qt[tq][kZigzagHost[i]] = (uint16_t)(pq ? rd16(s + q + 1 + 2 * i) : s[q + 1 + i]);
+                hd.qdef[tq] = true;
+                q += 1 + size;
+            }
+        } else if (m == 0xDD) {
+            if (sl != 2) return LPI_EINVAL;
+            hd.ri = rd16(s);
+        } else if (m == 0xE0) {
+            if (sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) hd.jfif = true;
+        } else if (m == 0xEE) {
+            if (sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) hd.adobe = true;
+        } else if (m == 0xDA) {
+            if (!hd.sof || sl < 1) return LPI_EINVAL;
+            hd.ns = s[0];
+            if (hd.ns < 1 || hd.ns > 4 || sl != 4 + 2 * hd.ns) return LPI_EINVAL;
+            for (int i = 0; i < hd.ns; ++i) {
+                int f = -1;
+                for (int c = 0; c < hd.nc; ++c)
+                    if (hd.cid[c] == s[1 + 2 * i]) f = c;
+                if (f < 0) return LPI_EINVAL;
+                for (int j = 0; j < i; ++j)
+                    if (hd.sc[j] == f) return LPI_EINVAL;
+                hd.sc[i] = f;
+                hd.std_[i] = s[2 + 2 * i] >> 4;
+                hd.sta[i] = s[2 + 2 * i] & 15;
+                if (hd.std_[i] > 3 || hd.sta[i] > 3 || !hd.hdef[0][hd.std_[i]] || !hd.hdef[1][hd.sta[i]]) return LPI_EINVAL;
+            }
+            for (int c = 0; c < hd.nc; ++c)
+                if (!hd.qdef[hd.ctq[c]]) return LPI_EINVAL;
+            hd.ent = p;
+            const int ss = s[1 + 2 * hd.ns], se = s[2 + 2 * hd.ns], ahal = s[3 + 2 * hd.ns];
+            bool ok = hd.ns == hd.nc && ss == 0 && se == 63 && ahal == 0 && hd.prec == 8 && hd.h > 0;
+            // libjpeg-turbo's get_sos looks a scan component up among the frame components whose slot in the SCAN's list is still empty: a
+            // full scan in any order but the frame's ends in JERR_BAD_COMPONENT_ID, so such files are Pillow's (its exception)
+            for (int i = 0; i < hd.ns; ++i) ok = ok && hd.sc[i] == i;
+            if (hd.nc == 3) {
+                ok = ok && (hd.jfif || !hd.adobe) && (hd.jfif || !(hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'));
+                const bool luma = (hd.ch[0] == 1 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 2);
+                ok = ok && luma && hd.ch[1] == 1 && hd.cv[1] == 1 && hd.ch[2] == 1 && hd.cv[2] == 1;
+            } else {
+                ok = ok && hd.nc == 1;
+            }
+            // sizes the decoder's workspace and its int bit positions take: larger files are the host's too
+            ok = ok && (long)hd.w * hd.h <= LPI_JPEG_MAX_PIXELS && n - hd.ent <= LPI_JPEG_MAX_SCAN_BYTES;
+            hd.gpu = ok;
+            return 0;
+        }
+        // APPn, COM, DNL and anything else with a length: skipped
+    }
+    return LPI_EINVAL;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ plan
+inline long align256(long v) { return (v + 255) / 256 * 256; }
+inline long desc_bytes(int B) { return align256((long)B * (long)sizeof(JDesc)); }
+
+// Fills the descriptors (their ws_* offsets from ws_base on) and returns the workspace bytes, or LPI_EINVAL.  zero_lo / zero_hi: the coefficient
+// range the caller clears before huff_kernel.
+int plan(int B, const uint8_t* host, const long* offsets, std::vector<JDesc>* descs, long* bytes, long* zero_lo, long* zero_hi) {
+    if (B < 1 || B > 65535 || !host || !offsets) return LPI_EINVAL;
+    if (descs) descs->assign(B, JDesc());
+    long ws = desc_bytes(B);
+    std::vector<Header> hds(B);
+    std::vector<long> coef_blocks(B);
+    for (int i = 0; i < B; ++i) {
+        if (offsets[i] < 0 || offsets[i + 1] < offsets[i] + 4) return LPI_EINVAL;
+        Header& hd = hds[i];
+        if (parse_headers(host + offsets[i], offsets[i + 1] - offsets[i], hd) != 0 || !hd.gpu) return LPI_EINVAL;
+        const long ent_len = offsets[i + 1] - offsets[i] - hd.ent;
+        if (ent_len < 0) return LPI_EINVAL;
+        ws += align256(ent_len + 16);
+        const int hm = hd.nc == 1 ? 1 : hd.ch[0], vm = hd.nc == 1 ? 1 : hd.cv[0];
+        const long mcux = (hd.w + 8 * hm - 1) / (8 * hm), mcuy = (hd.h + 8 * vm - 1) / (8 * vm);
+        const long nmcu = mcux * mcuy;
+        const long nseg = hd.ri ? (nmcu + hd.ri - 1) / hd.ri : 1;
+        ws += align256(nseg * 4);
+        coef_blocks[i] = nmcu * (hd.nc == 1 ? 1 : hm * vm + 2);
+    }
+    const long coef_lo = ws;
+    for (int i = 0; i < B; ++i) ws += align256(coef_blocks[i] * 128);
+    const long coef_hi = ws;
+    for (int i = 0; i < B; ++i) ws += align256(coef_blocks[i] * 64);
+    if (zero_lo) *zero_lo = coef_lo;
+    if (zero_hi) *zero_hi = coef_hi;
+    *bytes = ws;
+    if (!descs) return 0;
+    // second walk: the offsets
+    long at = desc_bytes(B), at_coef = coef_lo, at_plane = coef_hi;
+    for (int i = 0; i < B; ++i) {
+        const Header& hd = hds[i];
+        JDesc& j = (*descs)[i];
+        j.src_ent = offsets[i] + hd.ent;
+        j.src_end = offsets[i + 1];
+        j.w = hd.w;
+        j.h = hd.h;
+        j.nc = hd.nc;
+        j.hs = hd.nc == 1 ? 1 : hd.ch[0];
+        j.vs = hd.nc == 1 ? 1 : hd.cv[0];
+        j.mcux = (hd.w + 8 * j.hs - 1) / (8 * j.hs);
+        j.mcuy = (hd.h + 8 * j.vs - 1) / (8 * j.vs);
+        const long nmcu = (long)j.mcux * j.mcuy;
+        j.ri = hd.ri ? hd.ri : (int)std::min(nmcu, (long)0x7fffffff);
+        j.nseg = (int)((nmcu + j.ri - 1) / j.ri);
+        j.dw = (hd.w + j.hs - 1) / j.hs;
+        j.dh = (hd.h + j.vs - 1) / j.vs;
+        const long ent_len = j.src_end - j.src_ent;
+        j.ws_unst = at;
+        j.unst_cap = ent_len + 16;
+        at += align256(ent_len + 16);
+        j.ws_seg = at;
+        at += align256((long)j.nseg * 4);
+        int b = 0;
+        for (int s = 0; s < hd.ns; ++s) {
+            const int f = hd.sc[s];
+            const int H = hd.nc == 1 ? 1 : hd.ch[f], V = hd.nc == 1 ? 1 : hd.cv[f];
+            j.scomp[s] = f;
+            j.dc[s] = hd.hs[0][hd.std_[s]];
+            j.ac[s] = hd.hs[1][hd.sta[s]];
+            for (int y = 0; y < V; ++y)
+                for (int x = 0; x < H; ++x) {
+                    j.blk_comp[b] = s;
+                    j.blk_dx[b] = x;
+                    j.blk_dy[b] = y;
+                    ++b;
+                }
+        }
+        j.bpm = b;
+        for (int c = 0; c < hd.nc; ++c) {
+            const int H = hd.nc == 1 ? 1 : hd.ch[c], V = hd.nc == 1 ? 1 : hd.cv[c];
+            j.bw[c] = j.mcux * H;
+            j.bh[c] = j.mcuy * V;
+            std::memcpy(j.qt[c], hd.qt[hd.ctq[c]], sizeof(j.qt[c]));
+            j.ws_coef[c] = at_coef;
+            at_coef += (long)j.bw[c] * j.bh[c] * 128;
+            j.ws_plane[c] = at_plane;
+            at_plane += (long)j.bw[c] * j.bh[c] * 64;
+        }
+        at_coef = coef_lo + (at_coef - coef_lo + 255) / 256 * 256;     // the per-image blocks as counted above
+        at_plane = coef_hi + (at_plane - coef_hi + 255) / 256 * 256;
+        // chunks per segment: at least MIN_CHUNK bytes each on average, at most HT chunks per image (one per thread); 1 when segments are many
+        long k = j.nseg <= HT / 2 ? HT / j.nseg : 1;
+        const long by_len = ent_len / ((long)j.nseg * MIN_CHUNK);
+        if (k > by_len) k = by_len;
+        j.k = (int)(k < 1 ? 1 : k);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ kernels
+__device__ inline int block_excl_scan(int v, int* sh, int& total) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int o = 1; o < NT; o <<= 1) {
+        const int a = t >= o ? sh[t - o] : 0;
+        __syncthreads();
+        sh[t] += a;
+        __syncthreads();
+    }
+    total = sh[NT - 1];
+    const int r = sh[t] - v;
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(NT) void unstuff_kernel(const JDesc* __restrict__ descs, const uint8_t* __restrict__ src, uint8_t* __restrict__ ws,
+                                                     int* __restrict__ status) {
+    __shared__ int sh[NT];
+    __shared__ long s_end;
+    const JDesc& d = descs[blockIdx.x];
+    const int t = threadIdx.x;
+    uint8_t* un = ws + d.ws_unst;
+    int* seg = reinterpret_cast<int*>(ws + d.ws_seg);
+    const long lo = d.src_ent, hi = d.src_end;
+    long emitted = 0;
+    int nrst = 0, flags = 0;
+    if (t == 0) s_end = hi;
+    __syncthreads();
+    for (long base = lo; base < hi; base += ROUND) {
+        const long i0 = base + 16L * t;
+        // 1: the first marker other than RSTn in this round
+        long my_end = hi;
+        for (int q = 0; q < 16; ++q) {
+            const long i = i0 + q;
+            if (i >= hi) break;
+            if (src[i] != 0xFF) continue;
+            if (i + 1 >= hi) { my_end = i; break; }
+            const int nx = src[i + 1];
+            if (nx != 0x00 && nx != 0xFF && !(nx >= 0xD0 && nx <= 0xD7)) { my_end = i; break; }
+        }
+        if (my_end < hi) atomicMin((unsigned long long*)&s_end, (unsigned long long)my_end);
+        __syncthreads();
+        const long e = s_end;
+        // 2: counts and offsets of the data bytes and RSTn markers before e
+        int ne = 0, nr = 0;
+        for (int q = 0; q < 16; ++q) {
+            const long i = i0 + q;
+            if (i >= e) break;
+            const int b = src[i];
+            const int prev = i > lo ? src[i - 1] : 0;
+            if (b != 0xFF) ne += prev != 0xFF;
+            else {
+                const int nx = src[i + 1];           // i + 1 < e <= hi: a lone trailing 0xFF is an end
+                ne += nx == 0x00;
+                nr += nx >= 0xD0 && nx <= 0xD7;
+            }
+        }
+        int tot_e = 0, tot_r = 0;
+        const int oe = block_excl_scan(ne, sh, tot_e);
+        const int orr = block_excl_scan(nr, sh, tot_r);
+        // 3: write
+        long w = emitted + oe;
+        int r = nrst + orr;
+        for (int q = 0; q < 16; ++q) {
+            const long i = i0 + q;
+            if (i >= e) break;
+            const int b = src[i];
+            const int prev = i > lo ? src[i - 1] : 0;
+            if (b != 0xFF) {
+                if (prev != 0xFF) un[w++] = (uint8_t)b;
+            } else {
+                const int nx = src[i + 1];
+                if (nx == 0x00) un[w++] = 0xFF;
+                else if (nx >= 0xD0 && nx <= 0xD7) {
+                    if (nx != 0xD0 + (r & 7) || r >= d.nseg - 1) flags |= ST_RST;
+                    else seg[r] = (int)w;
+                    ++r;
+                }
+            }
+        }
+        emitted += tot_e;
+        nrst += tot_r;
+        if (e < base + ROUND) break;
+    }
+    if (t == 0) {
+        if (nrst != d.nseg - 1) flags |= ST_RST;
+        seg[d.nseg - 1] = (int)emitted;
+        for (int q = 0; q < 16; ++q) un[emitted + q] = 0;      // the reader's tail: inside unst_cap (emitted <= entropy bytes)
+    }
+    __syncthreads();
+    sh[t] = flags;
+    __syncthreads();
+    if (t == 0) {
+        int f = 0;
+        for (int q = 0; q < NT; ++q) f |= sh[q];
+        status[blockIdx.x] = f;
+    }
+}
+
+struct Lut {
+    uint16_t lut[1 << LUT_BITS];    // (length << 8) | symbol of codes up to LUT_BITS long; 0: longer
+    int maxcode[17];                // largest code of each length (-1: none)
+    int valoff[17];                 // vals index = code + valoff[length]
+    uint8_t vals[256];
+};
+
+struct DecState {
+    int p, z, b;
+};
+
+// Bit reader over one segment's unstuffed bytes [0, E) (bits), zeros past E.
+struct Reader {
+    const uint8_t* un;
+    long cap;          // bytes that may be read
+    int E;
+    int wbyte;
+    uint64_t win;
+    __device__ void fill(int p) {
+        wbyte = (p >> 5) << 2;
+        uint64_t v = 0;
+        if ((long)wbyte + 8 <= cap) {
+            const uint32_t a = *reinterpret_cast<const uint32_t*>(un + wbyte), c = *reinterpret_cast<const uint32_t*>(un + wbyte + 4);
+            v = ((uint64_t)__builtin_bswap32(a) << 32) | __builtin_bswap32(c);
+        }
+        const long keep = (long)E - (long)wbyte * 8;
+        if (keep <= 0) v = 0;
+        else if (keep < 64) v &= ~0ull << (64 - keep);
+        win = v;
+    }
+    __device__ uint32_t peek32(int p) {
+        if (p - wbyte * 8 > 32 || p < wbyte * 8) fill(p);
+        return (uint32_t)((win << (p - wbyte * 8)) >> 32);
+    }
+};
+
+__device__ inline int extend(int v, int s) { return s && v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
+
+// Where block b of an MCU goes: its scan component, and the position of its 8x8 block inside the MCU's share of that component (huff_kernel's LDS)
+struct BlkInfo {
+    int sc, dx, dy, H, V, bw;
+    long coef;          // workspace byte offset of the component's coefficient blocks
+};
+
+// Decodes symbols from st until `want` blocks are complete or, for stop_bit >= 0, the first symbol boundary at or after stop_bit.  Returns the
+// blocks completed; dcs: the DC differences summed per scan component.  ws != nullptr: writes the coefficients of blocks first + 0, 1, ...
+// (blocks past `limit` are not written) with the DC predictors pred.  Invalid data: flags, and a deterministic way on (the state stays a function of
+// the bits, which is all the synchronisation needs).
+__device__ int decode_run(const BlkInfo* __restrict__ bi, int bpm, int mcux, const int* __restrict__ zz, const Lut* __restrict__ dl,
+                          const Lut* __restrict__ al, Reader& rd, DecState& st, int stop_bit, int want, int* dcs, int* flags, uint8_t* ws, long first,
+                          long limit, int* pred) {
+    int nb = 0;
+    int sc = bi[st.b].sc;
+    auto locate = [&](long g) -> int16_t* {            // the coefficients of block g (the current block st.b), or nullptr
+        if (!ws || g >= limit) return nullptr;
+        const BlkInfo& q = bi[st.b];
+        const long m = g / bpm;
+        const long bx = (m % mcux) * q.H + q.dx, by = (m / mcux) * q.V + q.dy;
+        return reinterpret_cast<int16_t*>(ws + q.coef) + (by * q.bw + bx) * 64;
+    };
+    int16_t* bp = st.z > 0 ? locate(first) : nullptr;    // a block the previous chunk began
+    const int maxsym = (stop_bit >= 0 ? stop_bit - st.p : rd.E - st.p) + 64;     // every symbol takes at least one bit
+    for (int it = 0; it < maxsym; ++it) {
+        if (nb >= want || (stop_bit >= 0 && st.p >= stop_bit)) break;
+        if (stop_bit < 0 && st.p > rd.E) break;
+        const uint32_t w32 = rd.peek32(st.p);
+        const Lut& L = st.z == 0 ? dl[sc] : al[sc];
+        const uint32_t w16 = w32 >> 16;
+        int len = 0, sym = 0;
+        const int e = L.lut[w16 >> (16 - LUT_BITS)];
+        if (e) {
+            len = e >> 8;
+            sym = e & 255;
+        } else {
+            for (int l = LUT_BITS + 1; l <= 16; ++l) {
+                const int code = (int)(w16 >> (16 - l));
+                if (code <= L.maxcode[l]) {
+                    len = l;
+                    sym = L.vals[(code + L.valoff[l]) & 255];
+                    break;
+                }
+            }
+        }
+        if (!len) {                                  // invalid code
+            *flags |= ST_CODE;
+            st.p += 1;
+            continue;
+        }
+        const int s = sym & 15;
+        const int v = s ? extend((int)((w32 << len) >> (32 - s)), s) : 0;
+        st.p += len + s;
+        bool done = false;
+        if (st.z == 0) {
+            dcs[sc] += v;
+            bp = locate(first + nb);
+            if (bp) {
+                pred[sc] += v;
+                bp[0] = (int16_t)pred[sc];
+            }
+            st.z = 1;
+        } else {
+            const int r = sym >> 4;
+            if (s) {
+                st.z += r;
+                if (st.z > 63) {
+                    *flags |= ST_INDEX;
+                    done = true;
+                } else {
+                    if (bp) bp[zz[st.z]] = (int16_t)v;
+                    ++st.z;
+                    done = st.z > 63;
+                }
+            } else if (r == 15) {
+                st.z += 16;
+                done = st.z > 63;
+            } else {
+                done = true;
+            }
+        }
+        if (done) {
+            st.z = 0;
+            st.b = st.b + 1 == bpm ? 0 : st.b + 1;
+            sc = bi[st.b].sc;
+            ++nb;
+        }
+    }
+    return nb;
+}
+
+__global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ descs, uint8_t* __restrict__ ws, int* __restrict__ status) {
+    __shared__ Lut luts[6];
+    __shared__ BlkInfo s_bi[10];
+    __shared__ int s_zz[64];
+    __shared__ int s_ep[HT], s_ez[HT], s_eb[HT];        // exit state of each chunk
+    __shared__ int s_np[HT], s_nz[HT], s_nb[HT];        // entry state of each chunk
+    __shared__ int s_cnt[HT], s_dc[HT][3];              // blocks and DC sums from entry to exit; after the scan: those of the chunks before
+    __shared__ int s_need[HT];
+    __shared__ int s_any, s_flags;
+    const JDesc& d = descs[blockIdx.x];
+    const int t = threadIdx.x;
+    if (status[blockIdx.x] != 0) return;         // restart markers out of order: the segment table is not valid (uniform: before any barrier)
+    const uint8_t* un = ws + d.ws_unst;
+    const int* seg = reinterpret_cast<const int*>(ws + d.ws_seg);
+    const int ns = d.nc, bpm = d.bpm, mcux = d.mcux;
+
+    // tables
+    if (t < 2 * ns) {
+        const HuffSpec& hs = t < ns ? d.dc[t] : d.ac[t - ns];
+        Lut& L = luts[t < ns ? t : 3 + t - ns];
+        int code = 0, k = 0;
+        L.maxcode[0] = -1;
+        L.valoff[0] = 0;
+        for (int l = 1; l <= 16; ++l) {
+            const int n = hs.bits[l - 1];
+            L.valoff[l] = k - code;
+            code += n;
+            k += n;
+            L.maxcode[l] = n ? code - 1 : -1;
+            code <<= 1;
+        }
+        for (int q = 0; q < 256; ++q) L.vals[q] = hs.vals[q];
+    }
+    if (t < bpm) {
+        const int sc = d.blk_comp[t], f = d.scomp[sc];
+        const bool luma = d.nc == 3 && f == 0;
+        s_bi[t] = BlkInfo{sc, d.blk_dx[t], d.blk_dy[t], luma ? d.hs : 1, luma ? d.vs : 1, d.bw[f], d.ws_coef[f]};
+    }
+    if (t < 64) s_zz[t] = kZigzag[t];
+    if (t == 0) s_flags = 0;
+    __syncthreads();
+    for (int q = t; q < 2 * ns * (1 << LUT_BITS); q += HT) {
+        const int tb = q >> LUT_BITS, e = q & ((1 << LUT_BITS) - 1);
+        Lut& L = luts[tb < ns ? tb : 3 + tb - ns];
+        uint16_t v = 0;
+        for (int l = 1; l <= LUT_BITS; ++l) {
+            const int code = e >> (LUT_BITS - l);
+            if (code <= L.maxcode[l]) {
+                v = (uint16_t)((l << 8) | L.vals[(code + L.valoff[l]) & 255]);
+                break;
+            }
+        }
+        L.lut[e] = v;
+    }
+    __syncthreads();
+    const Lut* dl = luts;
+    const Lut* al = luts + 3;
+    int flags = 0;
+    const int k = d.k;
+    const long nmcu = (long)mcux * d.mcuy;
+    const long cap = d.unst_cap;
+
+    if (k == 1) {
+        // every segment is one chunk with an exact start: each thread decodes whole segments
+        for (int s = t; s < d.nseg; s += HT) {
+            const int s0 = s ? seg[s - 1] : 0, s1 = seg[s];
+            if (s0 > s1) { flags |= ST_RST; continue; }
+            Reader rd{un, cap, s1 * 8, -1000, 0};
+            DecState st{s0 * 8, 0, 0};
+            const long m0 = (long)s * d.ri, m1 = m0 + d.ri < nmcu ? m0 + d.ri : nmcu;
+            const long want = (m1 - m0) * bpm;
+            int dcs[3] = {0, 0, 0}, pred[3] = {0, 0, 0}, f = 0;
+            const int nb = decode_run(s_bi, bpm, mcux, s_zz, dl, al, rd, st, -1, (int)want, dcs, &f, ws, m0 * bpm, m1 * bpm, pred);
+            flags |= f;
+            if (nb != want || st.p > rd.E) flags |= ST_EOD;
+        }
+    } else {
+        const int nch = d.nseg * k;          // <= HT
+        const int s = t / k, j = t % k;
+        const bool mine = t < nch;
+        int c0 = 0, c1 = 0, E = 0;
+        s_cnt[t] = 0;
+        s_dc[t][0] = s_dc[t][1] = s_dc[t][2] = 0;
+        if (mine) {
+            const int s0 = s ? seg[s - 1] : 0, s1 = seg[s];
+            const int len = s1 > s0 ? s1 - s0 : 0;
+            const int L = (len + k - 1) / k;
+            c0 = s0 + j * L < s1 ? s0 + j * L : s1;
+            c1 = j == k - 1 ? s1 : (s0 + (j + 1) * L < s1 ? s0 + (j + 1) * L : s1);
+            E = s1 * 8;
+            if (s0 > s1) flags |= ST_RST;
+            s_np[t] = c0 * 8;
+            s_nz[t] = 0;
+            s_nb[t] = 0;
+            s_ep[t] = -1;
+            s_need[t] = 1;
+        }
+        // self-synchronisation: at most k rounds (each one makes one more chunk of every segment exact)
+        bool converged = false;
+        for (int round = 0; round <= k; ++round) {
+            if (t == 0) s_any = 0;
+            __syncthreads();
+            if (mine && s_need[t] && j != k - 1) {
+                Reader rd{un, cap, E, -1000, 0};
+                DecState st{s_np[t], s_nz[t], s_nb[t]};
+                int dcs[3] = {0, 0, 0}, f = 0;
+                const int nb = decode_run(s_bi, bpm, mcux, s_zz, dl, al, rd, st, c1 * 8, 0x7fffffff, dcs, &f, nullptr, 0, 0, nullptr);
+                s_cnt[t] = nb;
+                s_dc[t][0] = dcs[0];
+                s_dc[t][1] = dcs[1];
+                s_dc[t][2] = dcs[2];
+                if (st.p != s_ep[t] || st.z != s_ez[t] || st.b != s_eb[t]) {
+                    s_ep[t] = st.p;
+                    s_ez[t] = st.z;
+                    s_eb[t] = st.b;
+                    s_any = 1;
+                }
+            }
+            __syncthreads();
+            if (!s_any) {
+                converged = true;
+                break;
+            }
+            if (mine) {
+                s_need[t] = 0;
+                if (j > 0 && (s_ep[t - 1] != s_np[t] || s_ez[t - 1] != s_nz[t] || s_eb[t - 1] != s_nb[t])) {
+                    s_np[t] = s_ep[t - 1];
+                    s_nz[t] = s_ez[t - 1];
+                    s_nb[t] = s_eb[t - 1];
+                    s_need[t] = 1;
+                }
+            }
+            __syncthreads();
+        }
+        if (!converged) flags |= ST_COUNT;
+        // first block and DC predictors of every chunk: an exclusive scan of the block counts and DC sums over the chunks before it in its segment
+        // (segmented Hillis-Steele: chunk t - o is in the same segment iff j >= o; the last chunk's own sums are 0 and nothing follows it)
+        const int own0 = s_cnt[t], own1 = s_dc[t][0], own2 = s_dc[t][1], own3 = s_dc[t][2];
+        for (int o = 1; o < HT; o <<= 1) {
+            const bool take = mine && j >= o;
+            int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+            if (take) {
+                a0 = s_cnt[t - o];
+                a1 = s_dc[t - o][0];
+                a2 = s_dc[t - o][1];
+                a3 = s_dc[t - o][2];
+            }
+            __syncthreads();
+            if (take) {
+                s_cnt[t] += a0;
+                s_dc[t][0] += a1;
+                s_dc[t][1] += a2;
+                s_dc[t][2] += a3;
+            }
+            __syncthreads();
+        }
+        // the final pass
+        if (mine) {
+            const long first = s_cnt[t] - own0;
+            int pred[3] = {s_dc[t][0] - own1, s_dc[t][1] - own2, s_dc[t][2] - own3};
+            const long m0 = (long)s * d.ri, m1 = m0 + d.ri < nmcu ? m0 + d.ri : nmcu;
+            const long want = (m1 - m0) * bpm;
+            Reader rd{un, cap, E, -1000, 0};
+            DecState st{s_np[t], s_nz[t], s_nb[t]};
+            int dcs[3] = {0, 0, 0}, f = 0;
+            // every chunk stops at the segment's last block: the chunk that completes it must not have read past the segment's end, and the last
+            // chunk must complete it (a chunk past the data's end may have counted blocks in the padding: its successors then have nothing left)
+            const long left = want - first;
+            if (left > 0) {
+                const int nb = decode_run(s_bi, bpm, mcux, s_zz, dl, al, rd, st, j == k - 1 ? -1 : c1 * 8, (int)left, dcs, &f, ws, m0 * bpm + first,
+                                          m1 * bpm, pred);
+                if ((nb == left && st.p > E) || (j == k - 1 && nb != left)) flags |= ST_EOD;
+                flags |= f;
+            }
+        }
+    }
+    if (flags) atomicOr(&s_flags, flags);
+    __syncthreads();
+    if (t == 0 && s_flags) atomicOr(status + blockIdx.x, s_flags);
+}
+
+// jidctint.c constants (CONST_BITS 13)
+#define F0298 2446
+#define F0390 3196
+#define F0541 4433
+#define F0765 6270
+#define F0899 7373
+#define F1175 9633
+#define F1501 12299
+#define F1847 15137
+#define F1961 16069
+#define F2053 16819
+#define F2562 20995
+#define F3072 25172
+
+__device__ inline void idct1d(int s0, int s1, int s2, int s3, int s4, int s5, int s6, int s7, int* o, int shift) {
+    const int bias = 1 << (shift - 1);
+    int z1 = (s2 + s6) * F0541;
+    const int tmp2 = z1 + s6 * (-F1847), tmp3 = z1 + s2 * F0765;
+    const int tmp0 = (s0 + s4) * 8192, tmp1 = (s0 - s4) * 8192;
+    const int t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+    int o0 = s7, o1 = s5, o2 = s3, o3 = s1;
+    z1 = o0 + o3;
+    int z2 = o1 + o2, z3 = o0 + o2, z4 = o1 + o3;
+    const int z5 = (z3 + z4) * F1175;
+    o0 *= F0298;
+    o1 *= F2053;
+    o2 *= F3072;
+    o3 *= F1501;
+    z1 *= -F0899;
+    z2 *= -F2562;
+    z3 = z3 * -F1961 + z5;
+    z4 = z4 * -F0390 + z5;
+    o0 += z1 + z3;
+    o1 += z2 + z4;
+    o2 += z2 + z3;
+    o3 += z1 + z4;
+    o[0] = (t10 + o3 + bias) >> shift;
+    o[7] = (t10 - o3 + bias) >> shift;
+    o[1] = (t11 + o2 + bias) >> shift;
+    o[6] = (t11 - o2 + bias) >> shift;
+    o[2] = (t12 + o1 + bias) >> shift;
+    o[5] = (t12 - o1 + bias) >> shift;
+    o[3] = (t13 + o0 + bias) >> shift;
+    o[4] = (t13 - o0 + bias) >> shift;
+}
+
+__device__ inline uint8_t idct_limit(int v) {
+    const int x = v & 1023;
+    return (uint8_t)(x < 128 ? x + 128 : (x < 512 ? 255 : (x < 896 ? 0 : x - 896)));
+}
+
+// grid (blocks / 64, B): one thread per block of every component
+__global__ __launch_bounds__(64) void idct_kernel(const JDesc* __restrict__ descs, uint8_t* __restrict__ ws) {
+    const JDesc& d = descs[blockIdx.y];
+    long i = (long)blockIdx.x * 64 + threadIdx.x;
+    int c = 0;
+    for (; c < d.nc; ++c) {
+        const long n = (long)d.bw[c] * d.bh[c];
+        if (i < n) break;
+        i -= n;
+    }
+    if (c >= d.nc) return;
+    const int16_t* cf = reinterpret_cast<const int16_t*>(ws + d.ws_coef[c]) + i * 64;
+    const uint16_t* q = d.qt[c];
+    int ws8[64];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {          // pass 1: column u
+        int o[8];
+        idct1d(cf[u] * q[u], cf[8 + u] * q[8 + u], cf[16 + u] * q[16 + u], cf[24 + u] * q[24 + u], cf[32 + u] * q[32 + u], cf[40 + u] * q[40 + u],
+               cf[48 + u] * q[48 + u], cf[56 + u] * q[56 + u], o, 11);
+#pragma unroll
+        for (int y = 0; y < 8; ++y) ws8[y * 8 + u] = o[y];
+    }
+    const long bx = i % d.bw[c], by = i / d.bw[c];
+    const long pw = (long)d.bw[c] * 8;
+    uint8_t* out = ws + d.ws_plane[c] + by * 8 * pw + bx * 8;
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {          // pass 2: row y
+        int o[8];
+        idct1d(ws8[y * 8], ws8[y * 8 + 1], ws8[y * 8 + 2], ws8[y * 8 + 3], ws8[y * 8 + 4], ws8[y * 8 + 5], ws8[y * 8 + 6], ws8[y * 8 + 7], o, 18);
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            lo |= (uint32_t)idct_limit(o[x]) << (8 * x);
+            hi |= (uint32_t)idct_limit(o[x + 4]) << (8 * x);
+        }
+        uint32_t* row = reinterpret_cast<uint32_t*>(out + y * pw);     // planes are 256-aligned, pw and bx * 8 multiples of 8
+        row[0] = lo;
+        row[1] = hi;
+    }
+}
+
+__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// chroma sample (x, y) of the upsampled plane: jdsample.c h2v1 / h2v2 fancy (edges replicated at dw x dh), or plain replication for dw <= 2
+__device__ inline int chroma(const uint8_t* p, long pw, int x, int y, int hs, int vs, int dw, int dh) {
+    if (hs == 1) return p[(long)y * pw + x];
+    const int i = x >> 1;
+    const int ry = vs == 2 ? y >> 1 : y;
+    if (dw <= 2) return p[(long)ry * pw + i];
+    const int in = (x & 1) ? clampi(i + 1, 0, dw - 1) : clampi(i - 1, 0, dw - 1);
+    if (vs == 1) {
+        const uint8_t* r = p + (long)ry * pw;
+        return (x & 1) ? (3 * r[i] + r[in] + 2) >> 2 : (3 * r[i] + r[in] + 1) >> 2;
+    }
+    const int ny = (y & 1) ? clampi(ry + 1, 0, dh - 1) : clampi(ry - 1, 0, dh - 1);
+    const uint8_t* r0 = p + (long)ry * pw;
+    const uint8_t* r1 = p + (long)ny * pw;
+    const int cs = 3 * r0[i] + r1[i], cn = 3 * r0[in] + r1[in];
+    return (x & 1) ? (3 * cs + cn + 7) >> 4 : (3 * cs + cn + 8) >> 4;
+}
+
+// grid (ceil(max w / 256), max h, B)
+__global__ __launch_bounds__(256) void color_kernel(const JDesc* __restrict__ descs, const uint8_t* __restrict__ ws, uint8_t* __restrict__ out) {
+    const JDesc& d = descs[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= d.w || y >= d.h) return;
+    const long pw0 = (long)d.bw[0] * 8;
+    const int Y = ws[d.ws_plane[0] + (long)y * pw0 + x];
+    uint8_t* o = out + d.out + ((long)y * d.w + x) * 3;
+    if (d.nc == 1) {
+        o[0] = o[1] = o[2] = (uint8_t)Y;
+        return;
+    }
+    const long pwc = (long)d.bw[1] * 8;
+    const int cb = chroma(ws + d.ws_plane[1], pwc, x, y, d.hs, d.vs, d.dw, d.dh) - 128;
+    const int cr = chroma(ws + d.ws_plane[2], pwc, x, y, d.hs, d.vs, d.dw, d.dh) - 128;
+    // jdcolor.c: FIX(1.40200) = 91881, FIX(1.77200) = 116130, FIX(0.71414) = 46802, FIX(0.34414) = 22554, ONE_HALF = 32768
+    const int r = Y + ((91881 * cr + 32768) >> 16);
+    const int g = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    const int b = Y + ((116130 * cb + 32768) >> 16);
+    o[0] = (uint8_t)clampi(r, 0, 255);
+    o[1] = (uint8_t)clampi(g, 0, 255);
+    o[2] = (uint8_t)clampi(b, 0, 255);
+}
+
+}  // namespace
+
+extern "C" int lpi_jpeg_info(const void* data, long nbytes, long* info) {
+    if (!data || !info || nbytes < 0) return LPI_EINVAL;
+    Header hd;
+    if (parse_headers(static_cast<const uint8_t*>(data), nbytes, hd) != 0) return LPI_EINVAL;
+    info[0] = hd.gpu ? 1 : 0;
+    info[1] = hd.w;
+    info[2] = hd.h;
+    info[3] = hd.nc;
+    info[4] = hd.nc == 3 ? hd.ch[0] : 1;
+    info[5] = hd.nc == 3 ? hd.cv[0] : 1;
+    info[6] = hd.ri;
+    info[7] = hd.ent;
+    return 0;
+}
+
+extern "C" int lpi_jpeg_decode_workspace(int B, const void* host, const long* offsets, long* bytes) {
+    if (!bytes) return LPI_EINVAL;
+    return plan(B, static_cast<const uint8_t*>(host), offsets, nullptr, bytes, nullptr, nullptr);
+}
+
+extern "C" int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out,
+                                  long out_bytes, int* status, void* ws, long ws_bytes, void* stream) {
+    if (!src || !out || !status || !ws || !out_off || src_bytes < 1 || out_bytes < 1) return LPI_EINVAL;
+    std::vector<JDesc> descs;
+    long need = 0, z0 = 0, z1 = 0;
+    const int rc = plan(B, static_cast<const uint8_t*>(host), offsets, &descs, &need, &z0, &z1);
+    if (rc != 0) return rc;
+    if (ws_bytes < need || offsets[B] > src_bytes) return LPI_EINVAL;
+    int maxw = 1, maxh = 1;
+    long maxblk = 1;
+    for (int i = 0; i < B; ++i) {
+        JDesc& j = descs[i];
+        if (out_off[i] < 0 || out_off[i] > out_bytes - (long)j.w * j.h * 3) return LPI_EINVAL;
+        j.out = out_off[i];
+        maxw = j.w > maxw ? j.w : maxw;
+        maxh = j.h > maxh ? j.h : maxh;
+        long nb = 0;
+        for (int c = 0; c < j.nc; ++c) nb += (long)j.bw[c] * j.bh[c];
+        maxblk = nb > maxblk ? nb : maxblk;
+    }
+    if (maxh > 65535 || (maxblk + 63) / 64 > 0x7fffffffL) return LPI_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(ws, descs.data(), (size_t)B * sizeof(JDesc), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return (int)e;
+    e = hipMemsetAsync(static_cast<char*>(ws) + z0, 0, (size_t)(z1 - z0), s);
+    if (e != hipSuccess) return (int)e;
+    const JDesc* dd = static_cast<const JDesc*>(ws);
+    uint8_t* w8 = static_cast<uint8_t*>(ws);
+    LPI_LAUNCH(unstuff_kernel, dim3(B), dim3(NT), 0, s, dd, (const uint8_t*)src, w8, status);
+    LPI_CHECK_LAST();
+    LPI_LAUNCH(huff_kernel, dim3(B), dim3(HT), 0, s, dd, w8, status);
+    LPI_CHECK_LAST();
+    LPI_LAUNCH(idct_kernel, dim3((unsigned)((maxblk + 63) / 64), B), dim3(64), 0, s, dd, w8);
+    LPI_CHECK_LAST();
+    LPI_LAUNCH(color_kernel, dim3((maxw + 255) / 256, maxh, B), dim3(256), 0, s, dd, (const uint8_t*)w8, (uint8_t*)out);
+    LPI_CHECK_LAST();
+    return 0;
+}

@@ -89,3 +89,186 @@ def resample_decoded(batch, size=None, device="cuda", stream=None, threads=8):
         out = torch.empty((len(batch.pixels), 3, size, size), dtype=torch.uint8, device=device)
         launch(desc, src, total, ws, ws_bytes, out, size, stream)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- pixel_format='jpeg' (lpi_jpeg_decode_u8, csrc/jpeg.hip)
+JPEG_INFO = 8       # int64 fields lpi_jpeg_info fills (include/lpi_hip.h LPI_JPEG_INFO)
+
+
+def _u8(data):
+    """bytes / numpy / tensor -> a contiguous host uint8 numpy view."""
+    if torch.is_tensor(data):
+        return data.contiguous().numpy().reshape(-1).view(np.uint8)
+    return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+
+
+def jpeg_info(data):
+    """(gpu, width, height) of one file from its headers (lpi_jpeg_info: host only, it never touches the GPU, so forked loader workers may call it):
+    gpu = the file is inside lpi_jpeg_decode_u8's envelope.  None when the headers have a structural error; (False, 0, 0) for a file that is not a
+    JPEG.  The envelope is decided there and only there."""
+    a = _u8(data)
+    info = (ctypes.c_long * JPEG_INFO)()
+    rc = _lib.load().lpi_jpeg_info(a.ctypes.data if a.size else None, int(a.size), ctypes.addressof(info))
+    if rc != 0:
+        return None
+    return bool(info[0]), int(info[1]), int(info[2])
+
+
+def pil_decode(data):
+    """Pillow's decode of one file's bytes: np.asarray(Image.open(f).convert("RGB")) as an HWC uint8 tensor — the yardstick and the fallback (files
+    outside the envelope, and files whose GPU status is not OK).  Pillow's own exception propagates."""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(_u8(data).tobytes())) as im:
+        return torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8))
+
+
+def jpeg_workspace_bytes(host, offsets):
+    """Device workspace lpi_jpeg_decode_u8 needs for the files packed in host (uint8 numpy) at offsets ([n + 1] int64); LpiError when a file is outside
+    the envelope or has a structural error."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    out = ctypes.c_long(0)
+    rc = _lib.load().lpi_jpeg_decode_workspace(int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data, ctypes.addressof(out))
+    if rc != 0:
+        raise _lib.LpiError(f"lpi_jpeg_decode_workspace failed with code {rc} (a file outside the envelope or with a broken header)")
+    return int(out.value)
+
+
+def jpeg_launch(host, offsets, src, out_off, out, status, ws, stream):
+    """lpi_jpeg_decode_u8 on `stream`: the files of host / src (its device copy) at offsets into out at out_off (host int64), statuses into status."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    out_off = np.ascontiguousarray(out_off, dtype=np.int64)
+    rc = _lib.load().lpi_jpeg_decode_u8(int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data, src.data_ptr(), int(src.numel()), out_off.ctypes.data,
+                                        out.data_ptr(), int(out.numel()), status.data_ptr(), ws.data_ptr(), int(ws.numel()), stream.cuda_stream)
+    if rc != 0:
+        raise _lib.LpiError(f"lpi_jpeg_decode_u8 failed with code {rc}" + (" (invalid argument)" if rc == -22 else ""))
+
+
+class _Decoded:
+    """Full-size pixels of an EncodedBatch on the device: `pixels` (uint8, the images packed HWC back to back), per image its (offset, w, h); `status`
+    the pinned host copy of the GPU statuses, readable once the event `ready` has completed; `gpu` the batch indices the GPU decoded."""
+    __slots__ = ("pixels", "offsets", "wh", "status", "gpu", "keep", "ready")
+
+
+_SIDE = {}
+
+
+def _side_stream(device):
+    """The stream this module decodes on for callers that did not name one (one per device): waiting for a batch's statuses then waits for that batch
+    only, not for the work the caller has queued on its own stream."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    s = _SIDE.get(index)
+    if s is None:
+        s = _SIDE[index] = torch.cuda.Stream(device=torch.device("cuda", index))
+    return s
+
+
+def _issue_decode(batch, device, stream, bufs=None):
+    """Enqueues on `stream`: the H2D copy of the batch's file bytes, lpi_jpeg_decode_u8 for its GPU files, the H2D copies of its host-decoded images, the
+    D2H copy of the statuses.  bufs(key, nbytes, pinned): a buffer provider (BatchPipeline's slots); fresh tensors by default."""
+    if bufs is None:
+        def bufs(key, n, where):
+            return torch.empty(max(int(n), 1), dtype=torch.uint8, pin_memory=True) if where == "pinned" else torch.empty(max(int(n), 1), dtype=torch.uint8,
+                                                                                                                      device=device)
+    B = len(batch)
+    wh = np.asarray(batch.wh, dtype=np.int64).reshape(B, 2)
+    nbytes = wh[:, 0] * wh[:, 1] * 3
+    offs = np.concatenate(([0], np.cumsum(nbytes)))
+    total = int(offs[-1])
+    gpu = [i for i in range(B) if i not in batch.fallback]
+    data = batch.data if batch.data.is_pinned() else batch.data.pin_memory()
+    host = data.numpy()
+    file_off = np.asarray(batch.offsets, dtype=np.int64)
+    d = _Decoded()
+    d.wh, d.offsets, d.gpu = wh, offs[:-1], gpu
+    d.keep = [data]
+    with torch.cuda.stream(stream):
+        d.pixels = bufs("pixels", total, "device")[:max(total, 1)]
+        status_dev = bufs("status", 4 * max(B, 1), "device")[:4 * max(B, 1)].view(torch.int32)
+        d.status = bufs("status_host", 4 * max(B, 1), "pinned")[:4 * max(B, 1)].view(torch.int32)
+        if gpu:
+            lo, hi = int(file_off[gpu[0]]), int(file_off[gpu[-1] + 1])
+            sub_off = np.array([file_off[i] for i in gpu] + [hi], dtype=np.int64) - lo
+            sub = host[lo:hi]
+            src = bufs("src", hi - lo, "device")[:hi - lo]
+            src.copy_(data[lo:hi], non_blocking=True)
+            ws_bytes = jpeg_workspace_bytes(sub, sub_off)
+            ws = bufs("ws", ws_bytes, "device")[:ws_bytes]
+            jpeg_launch(sub, sub_off, src, d.offsets[gpu], d.pixels, status_dev, ws, stream)
+            d.status[:len(gpu)].copy_(status_dev[:len(gpu)], non_blocking=True)
+        d.ready = torch.cuda.Event()
+        d.ready.record(stream)
+        for i, px in batch.fallback.items():
+            d.pixels[int(offs[i]):int(offs[i + 1])].copy_(px.reshape(-1), non_blocking=True)
+            d.keep.append(px)
+    return d
+
+
+def _redo_failed(batch, d, stream):
+    """After the stream has passed the status copy: the files whose GPU status is not OK, decoded by Pillow (its pixels, or its exception) into their
+    slots.  Returns how many."""
+    bad = [i for k, i in enumerate(d.gpu) if int(d.status[k]) != 0]
+    with torch.cuda.stream(stream):
+        for i in bad:
+            px = pil_decode(batch.file(i))
+            w, h = (int(v) for v in d.wh[i])
+            if tuple(px.shape) != (h, w, 3):
+                raise _lib.LpiError(f"file {i}: Pillow decodes {tuple(px.shape)}, its header says {(h, w, 3)}")
+            d.pixels[int(d.offsets[i]):int(d.offsets[i]) + h * w * 3].copy_(px.reshape(-1).pin_memory(), non_blocking=True)
+    return len(bad)
+
+
+def _work_streams(device, stream):
+    """(the stream the caller reads the result on, the stream the decode runs on)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.LpiError("pixel_format='jpeg' decodes on an MI355X (device must be cuda:N)")
+    stream = torch.cuda.current_stream(device) if stream is None else stream
+    return device, stream, _side_stream(device)
+
+
+def decode_jpeg(batch, device="cuda", stream=None):
+    """EncodedBatch -> the full-size decoded images on the device, a list of B [h, w, 3] uint8 tensors (views of one buffer): for every file
+    np.asarray(Image.open(f).convert("RGB")), byte for byte.  The decode runs on this module's side stream; the host waits for that batch's statuses
+    only, and the result is ready in `stream`'s order (default: the device's current stream)."""
+    device, stream, side = _work_streams(device, stream)
+    d = _issue_decode(batch, device, side)
+    d.ready.synchronize()
+    _redo_failed(batch, d, side)
+    stream.wait_stream(side)
+    d.pixels.record_stream(stream)
+    return [d.pixels[int(o):int(o) + int(w) * int(h) * 3].view(int(h), int(w), 3) for o, (w, h) in zip(d.offsets, d.wh)]
+
+
+def encoded_descriptors(batch, d):
+    """The [B, 12] resample descriptor table of a decoded EncodedBatch (its images packed as _Decoded.pixels)."""
+    B = len(batch)
+    params = np.asarray(batch.params, dtype=np.int64).reshape(B, -1)
+    desc = np.empty((B, DESC), dtype=np.int64)
+    desc[:, 0] = d.offsets
+    desc[:, 1:3] = d.wh
+    desc[:, 3:] = params
+    return desc
+
+
+def resample_encoded(batch, size=None, device="cuda", stream=None, threads=8):
+    """EncodedBatch -> device [B,3,S,S] uint8 (CHW, contiguous): the batch resample_decoded (and pixel_format='u8') gives for the same images and
+    draws, byte for byte.  The GPU decodes the files inside the envelope (lpi_jpeg_decode_u8), the worker already decoded the others (Pillow);
+    a file whose GPU status is not OK is decoded again by Pillow and its batch resampled again.  The copies, the decode and the resample run on this
+    module's side stream; the host waits for this batch's statuses only (an event after their copy), not for the work queued on `stream`, and the
+    result is ready in `stream`'s order (default: the device's current stream).  threads: unused (the bytes arrive packed)."""
+    size = int(batch.size if size is None else size)
+    device, stream, side = _work_streams(device, stream)
+    d = _issue_decode(batch, device, side)
+    desc = encoded_descriptors(batch, d)
+    ws_bytes = workspace_bytes(desc, size)
+    with torch.cuda.stream(side):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        out = torch.empty((len(batch), 3, size, size), dtype=torch.uint8, device=device)
+        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side)
+    d.ready.synchronize()
+    if _redo_failed(batch, d, side):
+        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side)
+    stream.wait_stream(side)
+    out.record_stream(stream)
+    return out

@@ -30,7 +30,7 @@ import time
 import torch
 
 from . import _lib
-from .retrieval.utils.data import DecodedBatch
+from .retrieval.utils.data import DecodedBatch, EncodedBatch
 
 
 class DeviceBatch:
@@ -126,6 +126,34 @@ class BatchPipeline:
         imageops.launch(desc, src, total, ws, ws_bytes, out, S, self.side)
         return out[:B * 3 * S * S].view(B, 3, S, S)
 
+    def _stage_encoded(self, slot, images):
+        """Host half of an EncodedBatch: its file bytes (one tensor, packed by the worker) into the pinned byte slot."""
+        n = int(images.data.numel())
+        host = self._dec_buffer(slot, "host", n, pin_memory=True)
+        host[:n].copy_(images.data)
+        return EncodedBatch(host[:n], images.offsets, images.params, images.wh, images.size, images.fallback)
+
+    def _issue_encoded(self, slot, images):
+        """Device half, on the side stream: H2D of the file bytes, lpi_jpeg_decode_u8, lpi_image_resample_u8 into the uint8 output slot.  The statuses are
+        read here (this thread waits for the decode): a file the GPU could not decode exactly is decoded by Pillow and the batch resampled again, before
+        the batch is handed out."""
+        from . import imageops
+        B, S = len(images), int(images.size)
+
+        def bufs(key, n, where):
+            return self._dec_buffer(slot, "jpeg_" + key, n, pin_memory=True) if where == "pinned" else self._dec_buffer(slot, "jpeg_" + key, n,
+                                                                                                                     device=self.device)
+        d = imageops._issue_decode(images, self.device, self.side, bufs)
+        desc = imageops.encoded_descriptors(images, d)
+        ws_bytes = imageops.workspace_bytes(desc, S)
+        ws = self._dec_buffer(slot, "ws", ws_bytes, device=self.device)
+        out = self._dec_buffer(slot, "out", B * 3 * S * S, device=self.device)
+        imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side)
+        d.ready.synchronize()                       # the statuses' copy (the resample may still run)
+        if imageops._redo_failed(images, d, self.side):
+            imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side)
+        return out[:B * 3 * S * S].view(B, 3, S, S)
+
     def _produce(self):
         q, free, stop = self._q, self._free, self._stop      # this pass's hand-over state (a later pass replaces the attributes)
         try:
@@ -145,12 +173,16 @@ class BatchPipeline:
                         return
                 slot = index % self.depth
                 decoded = isinstance(images, DecodedBatch)
+                encoded = isinstance(images, EncodedBatch)
                 B = images.shape[0] if torch.is_tensor(images) else len(images)
                 if self._copied[slot] is not None:
                     self._copied[slot].synchronize()          # the staging slot's previous copy has left the host buffer
                 if decoded:
                     t2 = time.perf_counter()
                     dec = self._stage_decoded(slot, images)
+                elif encoded:
+                    t2 = time.perf_counter()
+                    images = self._stage_encoded(slot, images)
                 else:
                     one = images[0]
                     shape = (B,) + tuple(one.shape)
@@ -171,6 +203,8 @@ class BatchPipeline:
                         e0.record(self.side)
                     if decoded:
                         dev = self._issue_decoded(slot, images, *dec)        # the kernel runs before `cp` is recorded
+                    elif encoded:
+                        dev = self._issue_encoded(slot, images)             # decode + resample, statuses read, before `cp` is recorded
                     else:
                         dev[:B].copy_(stage[:B], non_blocking=True)
                     if torch.is_tensor(text):

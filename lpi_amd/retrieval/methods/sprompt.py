@@ -159,16 +159,20 @@ class SPrompts(BaseLearner):
         pin_memory thread needed).  A dataset that yields DecodedImage items (pixel_format = 'decoded': the decoded images at their own sizes;
         lpi_image_resample_u8 crops / resizes / flips them on the GPU, lpi_amd.imageops) is collated into a DecodedBatch, at any worker count — decided
         per dataset, since the synthetic evaluation set has no decoded form and keeps its f32 images."""
-        from lpi_amd.retrieval.utils.data import collate_decoded, collate_keep_images
+        from lpi_amd.retrieval.utils.data import collate_decoded, collate_encoded, collate_keep_images
 
         def decoded(ds):
             return getattr(ds, 'pixel_format', 'f32') == 'decoded'
+
+        def encoded(ds):        # pixel_format = 'jpeg': the files' bytes, packed into one tensor per batch by collate_encoded (EncodedBatch)
+            return getattr(ds, 'pixel_format', 'f32') == 'jpeg'
         train_loader = DataLoader(train_dataset, batch_size=self.batch_size, shuffle=sampler is None, sampler=sampler,
                                   num_workers=self.num_workers, drop_last=sampler is not None,
-                                  collate_fn=collate_decoded if decoded(train_dataset) else (collate_keep_images if self.num_workers == 0 else None),
+                                  collate_fn=collate_decoded if decoded(train_dataset) else (
+                                      collate_encoded if encoded(train_dataset) else (collate_keep_images if self.num_workers == 0 else None)),
                                   persistent_workers=self.num_workers > 0)
         test_loader = DataLoader(test_dataset, batch_size=128, shuffle=False, num_workers=self.num_workers, pin_memory=True,
-                                 collate_fn=collate_decoded if decoded(test_dataset) else None)
+                                 collate_fn=collate_decoded if decoded(test_dataset) else (collate_encoded if encoded(test_dataset) else None))
         return train_loader, test_loader
 
     def state_dict(self):
@@ -242,12 +246,14 @@ class SPrompts(BaseLearner):
 
         def plain():
             from types import SimpleNamespace
-            from lpi_amd.imageops import resample_decoded
-            from lpi_amd.retrieval.utils.data import DecodedBatch
+            from lpi_amd.imageops import resample_decoded, resample_encoded
+            from lpi_amd.retrieval.utils.data import DecodedBatch, EncodedBatch
             for item in train_loader:
                 images, captions = item[0], item[1]
                 if isinstance(images, DecodedBatch):
                     images = resample_decoded(images, device=self._device)
+                elif isinstance(images, EncodedBatch):
+                    images = resample_encoded(images, device=self._device)
                 elif not torch.is_tensor(images):
                     images = torch.stack(list(images))
                 yield SimpleNamespace(images=images.to(self._device, non_blocking=True), text=captions if torch.is_tensor(captions) else list(captions))
@@ -327,13 +333,15 @@ class SPrompts(BaseLearner):
         impl = self.args.get("kmeans_impl", "hip")
         if impl not in ("hip", "sklearn"):
             raise ValueError(f"unknown kmeans_impl {impl!r} (hip | sklearn)")
-        from lpi_amd.imageops import resample_decoded
-        from lpi_amd.retrieval.utils.data import DecodedBatch
+        from lpi_amd.imageops import resample_decoded, resample_encoded
+        from lpi_amd.retrieval.utils.data import DecodedBatch, EncodedBatch
         vf, tf = [], []
         for item in dataloader:
             inputs, captions = item[0], item[1]
             if isinstance(inputs, DecodedBatch):
                 inputs = resample_decoded(inputs, device=self._device)
+            elif isinstance(inputs, EncodedBatch):
+                inputs = resample_encoded(inputs, device=self._device)
             elif not torch.is_tensor(inputs):
                 inputs = torch.stack(list(inputs))
             with torch.no_grad():
@@ -374,10 +382,13 @@ class SPrompts(BaseLearner):
         num_text = len(texts)
         text_bs = 256
         image_feats, category_i = [], []
-        from lpi_amd.imageops import resample_decoded
-        from lpi_amd.retrieval.utils.data import DecodedBatch
+        from lpi_amd.imageops import resample_decoded, resample_encoded
+        from lpi_amd.retrieval.utils.data import DecodedBatch, EncodedBatch
         for image, img_id, category in data_loader:
-            image = resample_decoded(image, device=self._device) if isinstance(image, DecodedBatch) else image.to(self._device)
+            if isinstance(image, EncodedBatch):
+                image = resample_encoded(image, device=self._device)
+            else:
+                image = resample_decoded(image, device=self._device) if isinstance(image, DecodedBatch) else image.to(self._device)
             selection = self.get_visual_task_id(image)
             image_feats.append(self._network.visual_interface(image, selection))
             category_i.extend(int(z) for z in category)

@@ -46,6 +46,8 @@ class SyntheticCoco(Dataset):
         if captions not in ("ids", "strings"):
             raise ValueError(f"captions must be 'ids' or 'strings', not {captions!r}")
         _check_pixel_format(pixel_format)
+        if pixel_format == "jpeg":
+            raise ValueError("pixel_format='jpeg' needs image files: SyntheticCoco has none (use 'decoded')")
         self.pixel_format = pixel_format
         self.n, self.tasks, self.res = n, list(tasks), resolution
         self.seed = seed
@@ -142,12 +144,82 @@ def collate_decoded(batch):
     return [DecodedBatch([d.pixels for d in imgs], params, size)] + [default_collate(list(c)) for c in cols[1:]]
 
 
-PIXEL_FORMATS = ("f32", "u8", "decoded")
+class EncodedImage:
+    """An item's image in pixel_format='jpeg': the file's bytes still compressed (``data``: a uint8 tensor), the transform's geometry (``params``: the
+    DESCRIPTOR_FIELDS tuple of train_crop_params / test_crop_params of the frame size), the output size S (``size``) and the frame size (``wh``).
+    The file is inside lpi_jpeg_decode_u8's envelope (lpi_amd.imageops.jpeg_info); lpi_amd.imageops.resample_encoded decodes and resamples it on the
+    GPU."""
+    __slots__ = ("data", "params", "size", "wh")
+
+    def __init__(self, data, params, size, wh):
+        if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 1:
+            raise ValueError("EncodedImage.data must be a 1-D uint8 tensor (the file's bytes)")
+        w, h = (int(v) for v in wh)
+        self.data, self.size, self.wh = data, int(size), (w, h)
+        x0, y0, x1, y1, rw, rh, ox, oy, flip = params
+        self.params = resample_descriptor(w, h, (x0, y0, x1, y1), (rw, rh), (ox, oy), flip, size)
+
+    def __reduce__(self):
+        return (EncodedImage, (self.data, self.params, self.size, self.wh))
+
+
+class EncodedBatch:
+    """A batch of pixel_format='jpeg' items: ``data`` ONE uint8 tensor with the files of the encoded items back to back (file i = data[offsets[i] :
+    offsets[i+1]], empty for a host-decoded item), ``offsets`` [B+1] int64, ``params`` the [B, 9] int64 descriptor table, ``wh`` [B, 2] int64 frame
+    sizes, ``size`` S, ``fallback`` {batch index: HWC uint8 pixels} of the items Pillow decoded in the worker (files outside the envelope)."""
+    __slots__ = ("data", "offsets", "params", "wh", "size", "fallback")
+
+    def __init__(self, data, offsets, params, wh, size, fallback=None):
+        self.data, self.offsets, self.params, self.wh, self.size = data, offsets, params, wh, int(size)
+        self.fallback = dict(fallback or {})
+
+    def __len__(self):
+        return int(self.params.shape[0])
+
+    def file(self, i):
+        """File i's bytes (a uint8 tensor view)."""
+        return self.data[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def __reduce__(self):
+        return (EncodedBatch, (self.data, self.offsets, self.params, self.wh, self.size, self.fallback))
+
+    def pin_memory(self, device=None):
+        return EncodedBatch(self.data.pin_memory(), self.offsets, self.params, self.wh, self.size, {i: p.pin_memory() for i, p in self.fallback.items()})
+
+
+def collate_encoded(batch):
+    """Collate of pixel_format='jpeg' items ``(EncodedImage or DecodedImage, ...)``: the images become one EncodedBatch whose file bytes are packed into
+    a single tensor here (in the worker: one shared-memory tensor per batch), every other field goes through default_collate."""
+    from torch.utils.data import default_collate
+    cols = list(zip(*batch))
+    imgs = cols[0]
+    if not all(isinstance(d, (EncodedImage, DecodedImage)) for d in imgs):
+        raise ValueError("collate_encoded takes items whose first field is an EncodedImage or a DecodedImage (pixel_format='jpeg')")
+    size = imgs[0].size
+    if any(d.size != size for d in imgs):
+        raise ValueError("collate_encoded: the items of one batch must share the output size S")
+    n = [int(d.data.numel()) if isinstance(d, EncodedImage) else 0 for d in imgs]
+    offsets = torch.tensor([0] + n, dtype=torch.int64).cumsum(0)
+    data = torch.empty(int(offsets[-1]), dtype=torch.uint8)
+    fallback, wh = {}, []
+    for i, d in enumerate(imgs):
+        if isinstance(d, EncodedImage):
+            data[int(offsets[i]):int(offsets[i + 1])] = d.data
+            wh.append(d.wh)
+        else:
+            fallback[i] = d.pixels
+            wh.append((int(d.pixels.shape[1]), int(d.pixels.shape[0])))
+    params = torch.tensor([d.params for d in imgs], dtype=torch.int64).view(len(imgs), len(DESCRIPTOR_FIELDS))
+    return [EncodedBatch(data, offsets, params, torch.tensor(wh, dtype=torch.int64).view(len(imgs), 2), size, fallback)] + \
+        [default_collate(list(c)) for c in cols[1:]]
+
+
+PIXEL_FORMATS = ("f32", "u8", "decoded", "jpeg")
 
 
 def _check_pixel_format(pixel_format):
     if pixel_format not in PIXEL_FORMATS:
-        raise ValueError(f"pixel_format must be 'f32', 'u8' or 'decoded', not {pixel_format!r}")
+        raise ValueError(f"pixel_format must be 'f32', 'u8', 'decoded' or 'jpeg', not {pixel_format!r}")
 
 
 class SyntheticCocoEval(Dataset):
@@ -330,6 +402,30 @@ def decoded_transform(form, size=224, resize=256):
     return transform
 
 
+def encoded_transform(form, size=224, resize=256):
+    """The transform of pixel_format='jpeg': file bytes -> EncodedImage (inside the envelope; lpi_jpeg_info gives the frame size, host only) or, for
+    any other file, Pillow's decode as a DecodedImage, right here (decoded_transform).  The crop draws are decoded_transform's, in its order."""
+    fallback = decoded_transform(form, size, resize)
+
+    def transform(data):
+        from lpi_amd.imageops import jpeg_info
+        info = jpeg_info(data)
+        if info is None or not info[0]:
+            import io
+            Image = _pil()
+            with Image.open(io.BytesIO(data)) as im:
+                return fallback(im.convert("RGB"))
+        _, w, h = info
+        desc = train_crop_params(w, h, size) if form == "train" else test_crop_params(w, h, resize, size)
+        return EncodedImage(torch.frombuffer(bytearray(data), dtype=torch.uint8), desc, size, (w, h))
+    return transform
+
+
+def _read(image_root, name):
+    with open(os.path.join(image_root, name), "rb") as f:
+        return f.read()
+
+
 class Coco(Dataset):
     """Training pairs of the given tasks (utils/data.py:308-382): item = (image, prompt + pre_caption(caption), 0, task)."""
 
@@ -341,6 +437,9 @@ class Coco(Dataset):
             transform = lambda im: train_transform(im, pixel_format="u8")  # noqa: E731
         if transform is None and pixel_format == "decoded":      # size: the S of the decoded path's output (the default transforms' 224)
             transform = decoded_transform("train", size)
+        self._encoded = transform is None and pixel_format == "jpeg"     # the transform then takes the file's bytes
+        if self._encoded:
+            transform = encoded_transform("train", size)
         self.pixel_format = pixel_format
         with open(ann_file, 'r') as f:
             records = json.load(f)
@@ -360,7 +459,10 @@ class Coco(Dataset):
 
     def __getitem__(self, index):
         ann = self.annotation[index]
-        image = _load(self.image_root, ann['image'], self.transform)
+        if self._encoded:
+            image = self.transform(_read(self.image_root, ann['image']))
+        else:
+            image = _load(self.image_root, ann['image'], self.transform)
         return image, self.prompt + pre_caption(ann['caption'], self.max_words), 0, task_of_category(ann['category'])
 
 
@@ -378,6 +480,9 @@ class CocoEval(Dataset):
         if transform is None and pixel_format == "decoded" and eval_transform in ('center', 'reference'):
             # size / resize: the S and Resize of the decoded path (the default transforms' 224 / 256); 'reference' takes the training form
             transform = decoded_transform("center" if eval_transform == 'center' else "train", size, resize)
+        self._encoded = transform is None and pixel_format == "jpeg" and eval_transform in ('center', 'reference')
+        if self._encoded:
+            transform = encoded_transform("center" if eval_transform == 'center' else "train", size, resize)
         self.pixel_format = pixel_format
         with open(ann_file, 'r') as f:
             records = json.load(f)
@@ -410,4 +515,6 @@ class CocoEval(Dataset):
 
     def __getitem__(self, index):
         ann = self.ann[index]
+        if self._encoded:
+            return self.transform(_read(self.image_root, ann['image'])), index, task_of_category(ann['category'])
         return _load(self.image_root, ann['image'], self.transform), index, task_of_category(ann['category'])

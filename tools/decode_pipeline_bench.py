@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""pixel_format='u8' against 'decoded' on real COCO-format JPEGs (seeded synthetic 640 x 480 q90 images written to a temporary folder):
+"""pixel_format='u8' against 'decoded' and 'jpeg' on real COCO-format JPEGs (seeded synthetic 640 x 480 q90 images written to a temporary folder,
+no restart markers):
 
-  1. host ms per item of the datasets (decode + transform + hand-over), train (Coco) and eval (CocoEval, Resize(256) + CenterCrop(224)), one process;
+  1. host ms per item of the datasets (decode or header walk + transform + hand-over), train (Coco) and eval (CocoEval, Resize(256) +
+     CenterCrop(224)), one process;
   2. lpi_image_resample_u8 for a 256-image batch of those items: HIP events around the call (descriptor copy + launches), warm-up, median of 30;
-  3. the plugin loop (SPrompts.train_epoch, ViT-B/16 bf16, 256 pairs, BatchPipeline) over the folder: pairs/s with num_workers 0 / 8 / 14, in steady
+  3. lpi_jpeg_decode_u8 for a 256-image batch of the 'jpeg' items: the file bytes already on the device, output at full size, HIP events around the
+     call (descriptor copy + clear + launches), warm-up, median of 30; the GPU statuses, and the files outside the envelope (host fallbacks);
+  4. the plugin loop (SPrompts.train_epoch, ViT-B/16 bf16, 256 pairs, BatchPipeline) over the folder: pairs/s with num_workers 0 / 8 / 14, in steady
      state: the untimed warm-up is longer than the DataLoader's prefetch queue (prefetch_factor 2 x workers batches), so the timed steps wait for
      batches the workers make while they are timed.
 
-usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--out FILE.json]
+The decode's phases (per-kernel times): rocprofv3 --kernel-trace --stats -- python3 tools/decode_pipeline_bench.py --decode-only
+
+usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--decode-only] [--out FILE.json]
 Prints one JSON object (and writes it to --out)."""
 import argparse
 import json
@@ -75,6 +81,39 @@ def kernel_us(ds, dev, reps=30, warm=5):
             "source_MB": round(float(nbytes.sum()) / 1e6, 1), "reps": reps, "warmup": warm}
 
 
+def jpeg_decode(ds, root, dev, reps=30, warm=5):
+    """lpi_jpeg_decode_u8 on one 256-image batch of 'jpeg' items (bytes on the device, full-size output), and the folder's fallbacks."""
+    torch.manual_seed(0)
+    batch = D.collate_encoded([ds[i % len(ds)] for i in range(256)])[0]
+    gpu = [i for i in range(len(batch)) if i not in batch.fallback]
+    lo, hi = int(batch.offsets[gpu[0]]), int(batch.offsets[gpu[-1] + 1])
+    host = batch.data.numpy()[lo:hi]
+    offs = np.array([int(batch.offsets[i]) for i in gpu] + [hi], dtype=np.int64) - lo
+    wh = batch.wh.numpy()[gpu]
+    out_off = np.concatenate(([0], np.cumsum(wh[:, 0] * wh[:, 1] * 3)))
+    src = torch.from_numpy(host.copy()).to(dev)
+    ws_bytes = imageops.jpeg_workspace_bytes(host, offs)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+    status = torch.empty(len(gpu), dtype=torch.int32, device=dev)
+    s = torch.cuda.current_stream(dev)
+    times = []
+    for r in range(warm + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        imageops.jpeg_launch(host, offs, src, out_off[:-1], out, status, ws, s)
+        e1.record(s)
+        e1.synchronize()
+        if r >= warm:
+            times.append(1e3 * e0.elapsed_time(e1))
+    files = sorted(f for f in os.listdir(root) if f.endswith(".jpg"))
+    outside = sum(1 for f in files if not (imageops.jpeg_info(open(os.path.join(root, f), "rb").read()) or (False,))[0])
+    return {"median_us": round(float(np.median(times)), 1), "p10_p90_us": [round(float(np.percentile(times, q)), 1) for q in (10, 90)],
+            "files": len(gpu), "file_MB": round(hi / 1e6 - lo / 1e6, 2), "mean_file_KB": round((hi - lo) / len(gpu) / 1e3, 1),
+            "output_MB": round(float(out_off[-1]) / 1e6, 1), "workspace_MB": round(ws_bytes / 1e6, 1), "gpu_status_not_ok": int((status != 0).sum()),
+            "batch_fallbacks": len(batch.fallback), "folder_files": len(files), "folder_files_outside_envelope": outside, "reps": reps, "warmup": warm}
+
+
 def loop_pairs_per_s(root, pf, workers, steps, warm, dev):
     from lpi_amd.retrieval.methods.sprompt import SPrompts
     args = json.load(open(os.path.join(REPO, "lpi_amd", "retrieval", "configs", "lpi", "coco_lpi.json")))
@@ -83,7 +122,7 @@ def loop_pairs_per_s(root, pf, workers, steps, warm, dev):
     m = SPrompts(args)
     m._network.update_fc(0)
     ds = D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf)
-    collate = D.collate_decoded if pf == "decoded" else (D.collate_keep_images if workers == 0 else None)
+    collate = D.collate_decoded if pf == "decoded" else (D.collate_encoded if pf == "jpeg" else (D.collate_keep_images if workers == 0 else None))
     loader = DataLoader(ds, batch_size=256, shuffle=False, num_workers=workers, collate_fn=collate, persistent_workers=False)
     opt, _ = m._setup_training()
     t = {}
@@ -110,6 +149,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2, help="untimed steps; at least prefetch_factor (2) x workers + 2 whatever this says")
     ap.add_argument("--workers", default="0,8,14")
     ap.add_argument("--host-items", type=int, default=200)
+    ap.add_argument("--decode-only", action="store_true", help="write the folder and run section 3 only (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from lpi_amd.synth_bpe import ensure_vocab
@@ -120,17 +160,25 @@ def main():
         workers = [int(x) for x in a.workers.split(",")]
         warm = {w: max(a.warmup, 2 * w + 2) for w in workers}
         write_folder(root, a.images, 256 * (a.steps + max(warm.values()) + 1), 256)
-        tr = {pf: D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf) for pf in ("u8", "decoded")}
-        ev = {pf: D.CocoEval(image_root=root, ann_file=os.path.join(root, "val.json"), tasks=[0], pixel_format=pf) for pf in ("u8", "decoded")}
+        formats = ("u8", "decoded", "jpeg")
+        tr = {pf: D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf) for pf in formats}
+        ev = {pf: D.CocoEval(image_root=root, ann_file=os.path.join(root, "val.json"), tasks=[0], pixel_format=pf) for pf in formats}
+        if a.decode_only:
+            rec["jpeg_decode_256"] = jpeg_decode(tr["jpeg"], root, dev)
+            print(json.dumps(rec))
+            return
         rec["host_ms_per_item"] = {f"{form}_{pf}": round(host_ms(ds[pf], a.host_items), 3) for form, ds in (("train", tr), ("eval", ev))
-                                   for pf in ("u8", "decoded")}
+                                   for pf in formats}
         for form in ("train", "eval"):
             u, d = rec["host_ms_per_item"][f"{form}_u8"], rec["host_ms_per_item"][f"{form}_decoded"]
             rec[f"host_saving_{form}"] = round(1.0 - d / u, 3)
+            rec[f"host_saving_{form}_jpeg"] = round(1.0 - rec["host_ms_per_item"][f"{form}_jpeg"] / u, 3)
         rec["kernel_256"] = {"train": kernel_us(tr["decoded"], dev), "eval": kernel_us(ev["decoded"], dev)}
+        rec["jpeg_decode_256"] = jpeg_decode(tr["jpeg"], root, dev)
+        print(json.dumps({"jpeg_decode_256": rec["jpeg_decode_256"]}), flush=True)
         rec["loop_pairs_per_s"] = {}
         for w in workers:
-            for pf in ("u8", "decoded"):
+            for pf in formats:
                 rec["loop_pairs_per_s"][f"{pf}_workers{w}"] = loop_pairs_per_s(root, pf, w, a.steps, warm[w], dev)
                 print(json.dumps({f"{pf}_workers{w}": rec["loop_pairs_per_s"][f"{pf}_workers{w}"]}), flush=True)
     line = json.dumps(rec)
