@@ -586,29 +586,42 @@ int lpi_host_gather_v(void* dst, const void* const* srcs, const long* bytes, int
 /* ---- decoded pixels on the GPU (imageops.hip)      replaces: the host's crop / Resize (bilinear) / CenterCrop / RandomHorizontalFlip of the training and
  * evaluation transforms (lpi_amd/retrieval/utils/data.py) and the HWC -> CHW copy of pixel_format='u8'.
  * One descriptor per image: LPI_RESAMPLE_DESC int64 values {src_offset, w, h, x0, y0, x1, y1, rw, rh, ox, oy, flip}: the image is the w x h x 3 (HWC,
- * RGB) uint8 block at byte src_offset of `src`; its output is crop((x0, y0, x1, y1)).resize((rw, rh), BILINEAR), the window [ox, ox+S) x [oy, oy+S) of
- * that, mirrored left-right if flip = 1.
+ * RGB) uint8 block at byte src_offset of `src`; its output is crop((x0, y0, x1, y1)).resize((rw, rh), FILTER), the window [ox, ox+S) x [oy, oy+S) of
+ * that, mirrored left-right if flip = 1.  FILTER is one per call, a Pillow Image.Resampling value: LPI_FILTER_BILINEAR (the reference's retrieval
+ * loader; what the entry points without _f use), LPI_FILTER_BICUBIC (CLIP's own preprocessing) or LPI_FILTER_BOX.  Any other value (0 NEAREST does
+ * not go through ImagingResample; 1 LANCZOS and 5 HAMMING take their taps from the host's sin / cos, which the device's need not match in the last
+ * bit) is LPI_EINVAL, returned before any copy or launch.
  * EXACTNESS: out is Pillow 12's ImagingResample for 8-bit channels, byte for byte: per axis scale = in/out (in = the CROP's size: the filter clamps at
- * the crop's edges), filterscale = support = max(scale, 1), center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)
- * (center + support + 0.5), in) - xmin, taps tri((x + xmin - center + 0.5) * (1 / filterscale)) summed in tap order and divided by their sum, in double
- * without FMA contraction, converted to 22-bit fixed point as (int)(+-0.5 + k * 2^22); the horizontal pass is rounded to a uint8 intermediate
- * (clamp((2^21 + sum) >> 22, 0, 255)), then the vertical pass on it the same way — or vertical first, then horizontal, where Pillow's Image.resize
- * takes that order: crop height > 100 * crop width and rh < crop height.
+ * the crop's edges), filterscale = max(scale, 1), support = fs * filterscale with the filter's support fs (BOX 0.5, BILINEAR 1, BICUBIC 2), center =
+ * (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in) - xmin, taps f((x + xmin - center
+ * + 0.5) * (1 / filterscale)) summed in tap order and divided by their sum, in double without FMA contraction, f the filter's function in Pillow's
+ * association order — BILINEAR 1 - |x| below 1; BICUBIC (a = -0.5) ((a + 2) |x| - (a + 3)) |x| |x| + 1 below 1, (((|x| - 5) |x| + 8) |x| - 4) a
+ * below 2; BOX 1 for -0.5 < x <= 0.5; else 0 — converted to 22-bit fixed point as (int)(+-0.5 + k * 2^22); the horizontal pass is rounded to a
+ * uint8 intermediate (clamp((2^21 + sum) >> 22, 0, 255), both clamps live with bicubic's negative taps), then the vertical pass on it the same way —
+ * or vertical first, then horizontal, where Pillow's Image.resize takes that order, whatever the filter: crop height > 100 * crop width and rh <
+ * crop height.
  * Limits: 1 <= B <= 65535, 1 <= S <= LPI_RESAMPLE_MAX_SIZE, 1 <= w, h, rw, rh <= LPI_RESAMPLE_MAX_SIDE; the box non-empty inside the image, the window
  * inside the resized image, flip 0 or 1: anything else is LPI_EINVAL, returned before any launch. */
 #define LPI_RESAMPLE_DESC 12
 #define LPI_RESAMPLE_MAX_SIZE 1024
 #define LPI_RESAMPLE_MAX_SIDE (1L << 24)
+#define LPI_FILTER_BILINEAR 2
+#define LPI_FILTER_BICUBIC 3
+#define LPI_FILTER_BOX 4
 /* *bytes = the workspace lpi_image_resample_u8 needs for these B HOST descriptors: the descriptor table (B * LPI_RESAMPLE_DESC * 8 bytes, rounded up to
- * 256) + B * S * (4 + KX + KY) * 4 bytes, KX / KY the largest per-image tap count ceil(max(crop / resized, 1)) * 2 + 1 of each axis.  0 or LPI_EINVAL
- * (invalid descriptors, as above). */
+ * 256) + B * S * (4 + KX + KY) * 4 bytes, KX / KY the largest per-image tap count ceil(fs * max(crop / resized, 1)) * 2 + 1 of each axis (fs = the
+ * filter's support; 1 for the entry without _f, which is the LPI_FILTER_BILINEAR case).  0 or LPI_EINVAL (invalid descriptors or filter, as above). */
 int lpi_image_resample_workspace(int B, int S, const long* desc, long* bytes);
+int lpi_image_resample_workspace_f(int filter, int B, int S, const long* desc, long* bytes);
 /* out[B,3,S,S] uint8 (CHW, contiguous) from the ragged sources in `src` (device, src_bytes bytes), on `stream`.  desc: the HOST descriptor table
  * [B][LPI_RESAMPLE_DESC], validated here (also against src_bytes) and then copied by this call into the head of the workspace, from where the kernels
  * read it (pageable desc: free to change once the call returns; pinned desc: unchanged until the stream has passed the copy).  ws: device workspace of
  * ws_bytes >= lpi_image_resample_workspace's.  One copy and two launches (tap tables, then the resample; a third for images resampled
- * vertical-first). */
+ * vertical-first), the same for every filter.  A workspace sized for another filter that is too small is LPI_EINVAL, not a write past its end.
+ * lpi_image_resample_u8 is lpi_image_resample_u8_f with LPI_FILTER_BILINEAR. */
 int lpi_image_resample_u8(int B, int S, const long* desc, const void* src, long src_bytes, void* ws, long ws_bytes, void* out, void* stream);
+int lpi_image_resample_u8_f(int filter, int B, int S, const long* desc, const void* src, long src_bytes, void* ws, long ws_bytes, void* out,
+                            void* stream);
 
 /* ---- baseline JPEG decoding on the GPU (jpeg.hip)      replaces: Image.open(f).convert("RGB") of the data transforms (pixel_format='jpeg',
  * lpi_amd/imageops.py).  The output of every file is np.asarray(Image.open(f).convert("RGB")) under Pillow 12 (libjpeg-turbo: islow IDCT, fancy

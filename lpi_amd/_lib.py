@@ -128,6 +128,8 @@ SIGNATURES = {
     # decoded pixels: Pillow-exact crop / bilinear resize / flip (imageops.hip, lpi_amd/imageops.py)
     "lpi_image_resample_workspace": [_I, _I, _P, _P],
     "lpi_image_resample_u8": [_I, _I, _P, _P, _L, _P, _L, _P, _P],
+    "lpi_image_resample_workspace_f": [_I, _I, _I, _P, _P],
+    "lpi_image_resample_u8_f": [_I, _I, _I, _P, _P, _L, _P, _L, _P, _P],
     # baseline JPEG decoding on the GPU (jpeg.hip, lpi_amd/imageops.py)
     "lpi_jpeg_info": [_P, _L, _P],
     "lpi_jpeg_decode_workspace": [_I, _P, _P, _P],
@@ -145,7 +147,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_bpe_create": c_void_p, "lpi_bpe_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 606
+EXPECTED_ABI = 607
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

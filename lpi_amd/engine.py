@@ -41,6 +41,11 @@ def _grad_dtype(dt: int) -> int:
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
 
+# EngineOptions.pixel_norm by name: (mean, std) handed to make_pixel_lut (None = its ImageNet defaults); CLIP's as lpi_amd.retrieval.utils.data.CLIP_MEAN / _STD
+PIXEL_NORMS = {"imagenet": (None, None),
+               "clip": ((0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711))}
+
+
 @dataclass(frozen=True)
 class EngineOptions:
     """Everything that selects a code path of the engine, as ONE typed per-engine object (round 6; it replaced sixteen module globals read from the
@@ -69,7 +74,10 @@ class EngineOptions:
         dgrad and LN1 backward run on B*P rows.  False computes every row (the exactness test's other arm).
     qkv_grouped: in_proj's output features of the non-causal tower re-ordered to [head][q|k|v][64] (Tower.__init__).  Same numbers; the attention
         kernels' (sample, head) slices become 384-byte pieces.  OFF: measured in the step it buys nothing (attn_bwd4 170.9 us either way, forward pair
-        98.4 -> 96.5 us, step 22.27 ms both: profiles/r06_experiments.md) although the kernels alone gain 7 % — kept as the tested proof of that."""
+        98.4 -> 96.5 us, step 22.27 ms both: profiles/r06_experiments.md) although the kernels alone gain 7 % — kept as the tested proof of that.
+    pixel_norm: the ToTensor + Normalize statistics lpi_patchify_u8 applies to uint8 pixels ('u8', 'decoded' and 'jpeg' items): 'imagenet' (the
+        reference's retrieval loader), 'clip' (CLIP's own, models/clip/clip.py:77 of the reference) or a (mean, std) pair of three floats each.  f32
+        images arrive normalised by the loader and are not touched."""
     residual_f16: bool = True
     ln_fold: int = 2
     rowstats: int = 2
@@ -78,10 +86,26 @@ class EngineOptions:
     stream_pool: bool = True
     l0_prompt_rows: bool = True
     qkv_grouped: bool = False
+    pixel_norm: object = "imagenet"
 
     def __post_init__(self):
         if self.ln_fold not in (0, 1, 2) or self.rowstats not in (0, 1, 2):
             raise ValueError("ln_fold and rowstats are 0, 1 or 2")
+        if not isinstance(self.pixel_norm, str):      # a pair from a config file is a list of lists: stored as tuples (hashable, like every field)
+            try:
+                mean, std = self.pixel_norm
+                pair = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
+            except (TypeError, ValueError):
+                raise ValueError(f"pixel_norm is 'imagenet', 'clip' or a (mean, std) pair, not {self.pixel_norm!r}") from None
+            if len(pair[0]) != 3 or len(pair[1]) != 3:
+                raise ValueError("pixel_norm: a (mean, std) pair holds three values each")
+            object.__setattr__(self, "pixel_norm", pair)
+        elif self.pixel_norm not in PIXEL_NORMS:
+            raise ValueError(f"pixel_norm is 'imagenet', 'clip' or a (mean, std) pair, not {self.pixel_norm!r}")
+
+    def pixel_stats(self):
+        """(mean, std) of pixel_norm; (None, None) for 'imagenet' (make_pixel_lut's defaults)."""
+        return PIXEL_NORMS[self.pixel_norm] if isinstance(self.pixel_norm, str) else self.pixel_norm
 
     @staticmethod
     def from_env(**over):
@@ -1025,7 +1049,7 @@ class DualEncoder:
                   "pe": torch.zeros(rows, d, device=self.device), "stat": torch.zeros(2, ws["Mp"], device=self.device)}
             ws["front"] = fe
         if u8:
-            call("lpi_patchify_u8", dt, B, cfg.image_resolution, cfg.vision_patch_size, image, self.pixel_lut(), fe["cols"], self.kp, s)
+            call("lpi_patchify_u8", dt, B, cfg.image_resolution, cfg.vision_patch_size, image, self.pixel_lut(*self.opt.pixel_stats()), fe["cols"], self.kp, s)
         else:
             call("lpi_patchify", dt, B, cfg.image_resolution, cfg.vision_patch_size, image, fe["cols"], self.kp, s)
         yield GemmReq(None, dt, fe["cols"], self.conv.w, fe["pe"], fe["cols"].shape[0], d, self.kp, m_real=B * G2)

@@ -1,7 +1,8 @@
-"""pixel_format='decoded': the crop / bilinear resize / centre crop / flip of the data transforms on the GPU (lpi_image_resample_u8, csrc/imageops.hip).
+"""pixel_format='decoded': the crop / resize / centre crop / flip of the data transforms on the GPU (lpi_image_resample_u8_f, csrc/imageops.hip), with
+Pillow's bilinear (the default), bicubic or box filter.
 
 A DecodedBatch (lpi_amd.retrieval.utils.data) holds B decoded HWC uint8 images of their original sizes and a [B, 9] descriptor table; the kernel turns
-them into the [B,3,S,S] uint8 CHW batch pixel_format='u8' delivers, byte for byte (Pillow 12's fixed-point bilinear resample).  Every image consumer
+them into the [B,3,S,S] uint8 CHW batch pixel_format='u8' delivers, byte for byte (Pillow 12's fixed-point resample with the batch's filter).  Every image consumer
 goes through resample_decoded; lpi_amd.pipeline.BatchPipeline uses the pieces below with its own ring slots.
 """
 from __future__ import annotations
@@ -14,6 +15,15 @@ import torch
 from . import _lib
 
 DESC = 12       # int64 fields of one image's kernel descriptor (include/lpi_hip.h LPI_RESAMPLE_DESC)
+FILTERS = {"bilinear": 2, "bicubic": 3, "box": 4}      # LPI_FILTER_* = Pillow's Image.Resampling values
+
+
+def filter_code(filter):
+    """LPI_FILTER_* of a filter name (ValueError for a name the kernel does not restate: nearest, lanczos, hamming, ...)."""
+    try:
+        return FILTERS[filter]
+    except (KeyError, TypeError):
+        raise ValueError(f"filter must be 'bilinear', 'bicubic' or 'box', not {filter!r}") from None
 
 
 def descriptors(batch):
@@ -48,38 +58,49 @@ def gather(batch, dst, nbytes, threads=8):
         raise _lib.LpiError(f"lpi_host_gather_v failed with code {rc}")
 
 
-def workspace_bytes(desc, size):
-    """Device workspace lpi_image_resample_u8 needs for the host descriptor table `desc` (LpiError on an invalid descriptor)."""
+def workspace_bytes(desc, size, filter="bilinear"):
+    """Device workspace lpi_image_resample_u8_f needs for the host descriptor table `desc` and the filter (LpiError on an invalid descriptor)."""
+    code = filter_code(filter)
     desc = np.ascontiguousarray(desc, dtype=np.int64)
     out = ctypes.c_long(0)
-    rc = _lib.load().lpi_image_resample_workspace(int(desc.shape[0]), int(size), desc.ctypes.data, ctypes.addressof(out))
+    rc = _lib.load().lpi_image_resample_workspace_f(code, int(desc.shape[0]), int(size), desc.ctypes.data, ctypes.addressof(out))
     if rc != 0:
-        raise _lib.LpiError(f"lpi_image_resample_workspace failed with code {rc} (invalid descriptor)")
+        raise _lib.LpiError(f"lpi_image_resample_workspace_f failed with code {rc} (invalid descriptor)")
     return int(out.value)
 
 
-def launch(desc, src, src_bytes, ws, ws_bytes, out, size, stream):
-    """lpi_image_resample_u8 on `stream` (a torch.cuda.Stream): out[:B] from the packed sources src (device uint8) and the host descriptor table desc
-    (pageable numpy: the call validates it and copies it into the workspace itself)."""
+def launch(desc, src, src_bytes, ws, ws_bytes, out, size, stream, filter="bilinear"):
+    """lpi_image_resample_u8_f on `stream` (a torch.cuda.Stream): out[:B] from the packed sources src (device uint8) and the host descriptor table desc
+    (pageable numpy: the call validates it and copies it into the workspace itself).  ws_bytes: workspace_bytes of the SAME filter."""
+    code = filter_code(filter)
     desc = np.ascontiguousarray(desc, dtype=np.int64)
     B = int(desc.shape[0])
-    rc = _lib.load().lpi_image_resample_u8(B, int(size), desc.ctypes.data, src.data_ptr(), int(src_bytes), ws.data_ptr(), int(ws_bytes), out.data_ptr(),
-                                           stream.cuda_stream)
+    rc = _lib.load().lpi_image_resample_u8_f(code, B, int(size), desc.ctypes.data, src.data_ptr(), int(src_bytes), ws.data_ptr(), int(ws_bytes),
+                                             out.data_ptr(), stream.cuda_stream)
     if rc != 0:
-        raise _lib.LpiError(f"lpi_image_resample_u8 failed with code {rc}" + (" (invalid argument)" if rc == -22 else ""))
+        raise _lib.LpiError(f"lpi_image_resample_u8_f failed with code {rc}" + (" (invalid argument)" if rc == -22 else ""))
 
 
-def resample_decoded(batch, size=None, device="cuda", stream=None, threads=8):
+def _batch_filter(batch, filter):
+    """The filter of a resample call: the named one, else the batch's own; checked here, before anything is enqueued."""
+    filter = getattr(batch, "filter", "bilinear") if filter is None else filter
+    filter_code(filter)
+    return filter
+
+
+def resample_decoded(batch, size=None, device="cuda", stream=None, threads=8, filter=None):
     """DecodedBatch -> device [B,3,S,S] uint8 (CHW, contiguous): the batch pixel_format='u8' gives for the same images and draws, byte for byte.
     size: S (default: the batch's); stream: a torch.cuda.Stream (default: the device's current one) on which the copies and the kernels are enqueued
-    — the result is ready in that stream's order."""
+    — the result is ready in that stream's order; filter: 'bilinear' | 'bicubic' | 'box' (default: the batch's own, 'bilinear' unless its dataset
+    said otherwise)."""
     size = int(batch.size if size is None else size)
+    filter = _batch_filter(batch, filter)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.LpiError("resample_decoded runs on an MI355X (device must be cuda:N)")
     stream = torch.cuda.current_stream(device) if stream is None else stream
     desc, nbytes = descriptors(batch)
-    ws_bytes = workspace_bytes(desc, size)          # validates before anything is copied
+    ws_bytes = workspace_bytes(desc, size, filter)          # validates before anything is copied
     total = int(nbytes.sum())
     stage = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
     gather(batch, stage, nbytes, threads)
@@ -87,7 +108,7 @@ def resample_decoded(batch, size=None, device="cuda", stream=None, threads=8):
         src = stage.to(device, non_blocking=True)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         out = torch.empty((len(batch.pixels), 3, size, size), dtype=torch.uint8, device=device)
-        launch(desc, src, total, ws, ws_bytes, out, size, stream)
+        launch(desc, src, total, ws, ws_bytes, out, size, stream, filter)
     return out
 
 
@@ -251,24 +272,26 @@ def encoded_descriptors(batch, d):
     return desc
 
 
-def resample_encoded(batch, size=None, device="cuda", stream=None, threads=8):
+def resample_encoded(batch, size=None, device="cuda", stream=None, threads=8, filter=None):
     """EncodedBatch -> device [B,3,S,S] uint8 (CHW, contiguous): the batch resample_decoded (and pixel_format='u8') gives for the same images and
     draws, byte for byte.  The GPU decodes the files inside the envelope (lpi_jpeg_decode_u8), the worker already decoded the others (Pillow);
     a file whose GPU status is not OK is decoded again by Pillow and its batch resampled again.  The copies, the decode and the resample run on this
     module's side stream; the host waits for this batch's statuses only (an event after their copy), not for the work queued on `stream`, and the
-    result is ready in `stream`'s order (default: the device's current stream).  threads: unused (the bytes arrive packed)."""
+    result is ready in `stream`'s order (default: the device's current stream).  threads: unused (the bytes arrive packed); filter: as
+    resample_decoded's."""
     size = int(batch.size if size is None else size)
+    filter = _batch_filter(batch, filter)
     device, stream, side = _work_streams(device, stream)
     d = _issue_decode(batch, device, side)
     desc = encoded_descriptors(batch, d)
-    ws_bytes = workspace_bytes(desc, size)
+    ws_bytes = workspace_bytes(desc, size, filter)
     with torch.cuda.stream(side):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         out = torch.empty((len(batch), 3, size, size), dtype=torch.uint8, device=device)
-        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side)
+        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side, filter)
     d.ready.synchronize()
     if _redo_failed(batch, d, side):
-        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side)
+        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side, filter)
     stream.wait_stream(side)
     out.record_stream(stream)
     return out

@@ -108,7 +108,7 @@ class BatchPipeline:
         """Host half of a DecodedBatch: descriptors (validated), the ragged gather into the pinned byte slot."""
         from . import imageops
         desc, nbytes = imageops.descriptors(images)
-        ws_bytes = imageops.workspace_bytes(desc, images.size)
+        ws_bytes = imageops.workspace_bytes(desc, images.size, images.filter)
         total = int(nbytes.sum())
         host = self._dec_buffer(slot, "host", total, pin_memory=True)
         imageops.gather(images, host, nbytes, self.threads)
@@ -123,7 +123,7 @@ class BatchPipeline:
         ws = self._dec_buffer(slot, "ws", ws_bytes, device=self.device)
         out = self._dec_buffer(slot, "out", B * 3 * S * S, device=self.device)
         src[:total].copy_(self._dec[slot]["host"][:total], non_blocking=True)
-        imageops.launch(desc, src, total, ws, ws_bytes, out, S, self.side)
+        imageops.launch(desc, src, total, ws, ws_bytes, out, S, self.side, images.filter)
         return out[:B * 3 * S * S].view(B, 3, S, S)
 
     def _stage_encoded(self, slot, images):
@@ -131,7 +131,7 @@ class BatchPipeline:
         n = int(images.data.numel())
         host = self._dec_buffer(slot, "host", n, pin_memory=True)
         host[:n].copy_(images.data)
-        return EncodedBatch(host[:n], images.offsets, images.params, images.wh, images.size, images.fallback)
+        return EncodedBatch(host[:n], images.offsets, images.params, images.wh, images.size, images.fallback, filter=images.filter)
 
     def _issue_encoded(self, slot, images):
         """Device half, on the side stream: H2D of the file bytes, lpi_jpeg_decode_u8, lpi_image_resample_u8 into the uint8 output slot.  The statuses are
@@ -145,13 +145,13 @@ class BatchPipeline:
                                                                                                                      device=self.device)
         d = imageops._issue_decode(images, self.device, self.side, bufs)
         desc = imageops.encoded_descriptors(images, d)
-        ws_bytes = imageops.workspace_bytes(desc, S)
+        ws_bytes = imageops.workspace_bytes(desc, S, images.filter)
         ws = self._dec_buffer(slot, "ws", ws_bytes, device=self.device)
         out = self._dec_buffer(slot, "out", B * 3 * S * S, device=self.device)
-        imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side)
+        imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side, images.filter)
         d.ready.synchronize()                       # the statuses' copy (the resample may still run)
         if imageops._redo_failed(images, d, self.side):
-            imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side)
+            imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side, images.filter)
         return out[:B * 3 * S * S].view(B, 3, S, S)
 
     def _produce(self):

@@ -120,9 +120,18 @@ class SPrompts(BaseLearner):
             # bit for bit the f32 pipeline, a quarter of the host-to-device bytes); 'decoded': the decoded images at their own sizes + the transforms'
             # geometry, the crop / resize / flip then run on the GPU too (lpi_image_resample_u8: bit for bit the 'u8' batch)
             pf = self.args.get('pixel_format', 'f32')
-            return (Coco(image_root=self.args['image_root'], ann_file=self.args['annotation_train_root'], tasks=[i], pixel_format=pf),
+            # preprocess = 'clip' (or the single keys interpolation / normalize / eval_resize): CLIP's own preprocessing instead of the reference
+            # loader's — the filter travels with the items, 'f32' items are normalised here and the engine gets the same statistics for the
+            # other formats (models/slinet.py: EngineOptions.pixel_norm).  Without those keys the datasets are built as ever.
+            from lpi_amd.retrieval.utils.data import preprocess_options
+            pre = preprocess_options(self.args, self._network.clip_cfg.image_resolution if 'preprocess' in self.args else None)
+            kw, ekw = {}, {}
+            if pre is not None:
+                kw = dict(size=pre['size'], interpolation=pre['interpolation'], normalize=pre['normalize'])
+                ekw = dict(resize=pre['eval_resize'])
+            return (Coco(image_root=self.args['image_root'], ann_file=self.args['annotation_train_root'], tasks=[i], pixel_format=pf, **kw),
                     CocoEval(image_root=self.args['image_root'], ann_file=self.args['annotation_val_root'], tasks=np.arange(0, i + 1),
-                             eval_transform=self.args.get('eval_transform', 'center'), pixel_format=pf))
+                             eval_transform=self.args.get('eval_transform', 'center'), pixel_format=pf, **kw, **ekw))
         if impl != "synthetic":
             raise ValueError(f"unknown dataset_impl {impl!r} (coco | synthetic)")
         res = self._network.clip_cfg.image_resolution

@@ -128,6 +128,12 @@ class SliNet(nn.Module):
             dev = torch.device(device) if device is not None else self.prompts[0].dim_1_share.device
             from lpi_amd.engine import EngineOptions
             eo = self.args.get("engine_options")      # None, an EngineOptions, or a dict of its fields (the config file's form)
+            # the config's preprocessing keys (preprocess / normalize: utils/data.py preprocess_options) decide the statistics of the uint8 pixel
+            # formats too; engine_options that say otherwise are an error there
+            from lpi_amd.retrieval.utils.data import engine_pixel_norm
+            norm = engine_pixel_norm(self.args, self.clip_cfg.image_resolution)
+            if norm is not None and not isinstance(eo, EngineOptions):
+                eo = dict(eo or {}, pixel_norm=norm)
             if isinstance(eo, dict):
                 eo = EngineOptions.from_env(**eo)
             self.engine = DualEncoder(self.clip_cfg, self.clip_model.state_dict(), dtype=self.compute_dtype, device=dev, n_ctx=self.cfg.NCTX, options=eo)

@@ -94,39 +94,62 @@ def collate_keep_images(batch):
     return [list(cols[0])] + [default_collate(list(c)) for c in cols[1:]]
 
 
+INTERPOLATIONS = ("bilinear", "bicubic", "box")      # the Pillow filters lpi_image_resample_u8_f restates (lpi_amd.imageops.FILTERS)
+
+
+def _check_filter(filter):
+    if filter not in INTERPOLATIONS:
+        raise ValueError(f"interpolation must be 'bilinear', 'bicubic' or 'box', not {filter!r}")
+    return filter
+
+
+def _common_filter(imgs, who):
+    filter = imgs[0].filter
+    if any(d.filter != filter for d in imgs):
+        raise ValueError(f"{who}: the items of one batch must share the resampling filter (the kernel takes one per call)")
+    return filter
+
+
+def _rebuild(cls, filter, *args):
+    """Unpickles an image / batch class whose filter is a keyword argument."""
+    return cls(*args, filter=filter)
+
+
 class DecodedImage:
     """An item's image in pixel_format='decoded': the decoded RGB pixels at their original size (``pixels``: HWC uint8, np.array(img.convert("RGB"))
     as a tensor, not copied to CHW) and the transform's geometry (``params``: the DESCRIPTOR_FIELDS tuple of train_crop_params / test_crop_params)
-    for an S x S output (``size``).  lpi_amd.imageops.resample_decoded runs the crop / bilinear resize / flip on the GPU."""
-    __slots__ = ("pixels", "params", "size")
+    for an S x S output (``size``) with the resampling filter ``filter`` ('bilinear' | 'bicubic' | 'box').  lpi_amd.imageops.resample_decoded runs
+    the crop / resize / flip on the GPU."""
+    __slots__ = ("pixels", "params", "size", "filter")
 
-    def __init__(self, pixels, params, size):
+    def __init__(self, pixels, params, size, *, filter="bilinear"):
         if not torch.is_tensor(pixels) or pixels.dtype != torch.uint8 or pixels.dim() != 3 or pixels.shape[2] != 3:
             raise ValueError("DecodedImage.pixels must be an HWC uint8 tensor with 3 channels")
         h, w = int(pixels.shape[0]), int(pixels.shape[1])
-        self.pixels, self.size = pixels, int(size)
+        self.pixels, self.size, self.filter = pixels, int(size), _check_filter(filter)
         x0, y0, x1, y1, rw, rh, ox, oy, flip = params
         self.params = resample_descriptor(w, h, (x0, y0, x1, y1), (rw, rh), (ox, oy), flip, size)
 
     def __reduce__(self):
-        return (DecodedImage, (self.pixels, self.params, self.size))
+        return (_rebuild, (DecodedImage, self.filter, self.pixels, self.params, self.size))
 
 
 class DecodedBatch:
-    """A batch of DecodedImage: ``pixels`` a list of B HWC uint8 tensors (ragged), ``params`` the [B, 9] int64 descriptor table, ``size`` S."""
-    __slots__ = ("pixels", "params", "size")
+    """A batch of DecodedImage: ``pixels`` a list of B HWC uint8 tensors (ragged), ``params`` the [B, 9] int64 descriptor table, ``size`` S,
+    ``filter`` the one resampling filter of the batch (the kernel takes it per call)."""
+    __slots__ = ("pixels", "params", "size", "filter")
 
-    def __init__(self, pixels, params, size):
-        self.pixels, self.params, self.size = list(pixels), params, int(size)
+    def __init__(self, pixels, params, size, *, filter="bilinear"):
+        self.pixels, self.params, self.size, self.filter = list(pixels), params, int(size), _check_filter(filter)
 
     def __len__(self):
         return len(self.pixels)
 
     def __reduce__(self):
-        return (DecodedBatch, (self.pixels, self.params, self.size))
+        return (_rebuild, (DecodedBatch, self.filter, self.pixels, self.params, self.size))
 
     def pin_memory(self, device=None):
-        return DecodedBatch([p.pin_memory() for p in self.pixels], self.params.pin_memory(), self.size)
+        return DecodedBatch([p.pin_memory() for p in self.pixels], self.params.pin_memory(), self.size, filter=self.filter)
 
 
 def collate_decoded(batch):
@@ -140,38 +163,42 @@ def collate_decoded(batch):
     size = imgs[0].size
     if any(d.size != size for d in imgs):
         raise ValueError("collate_decoded: the items of one batch must share the output size S")
+    filter = _common_filter(imgs, "collate_decoded")
     params = torch.tensor([d.params for d in imgs], dtype=torch.int64).view(len(imgs), len(DESCRIPTOR_FIELDS))
-    return [DecodedBatch([d.pixels for d in imgs], params, size)] + [default_collate(list(c)) for c in cols[1:]]
+    return [DecodedBatch([d.pixels for d in imgs], params, size, filter=filter)] + [default_collate(list(c)) for c in cols[1:]]
 
 
 class EncodedImage:
     """An item's image in pixel_format='jpeg': the file's bytes still compressed (``data``: a uint8 tensor), the transform's geometry (``params``: the
-    DESCRIPTOR_FIELDS tuple of train_crop_params / test_crop_params of the frame size), the output size S (``size``) and the frame size (``wh``).
+    DESCRIPTOR_FIELDS tuple of train_crop_params / test_crop_params of the frame size), the output size S (``size``), the frame size (``wh``) and
+    the resampling filter (``filter``: 'bilinear' | 'bicubic' | 'box').
     The file is inside lpi_jpeg_decode_u8's envelope (lpi_amd.imageops.jpeg_info); lpi_amd.imageops.resample_encoded decodes and resamples it on the
     GPU."""
-    __slots__ = ("data", "params", "size", "wh")
+    __slots__ = ("data", "params", "size", "wh", "filter")
 
-    def __init__(self, data, params, size, wh):
+    def __init__(self, data, params, size, wh, *, filter="bilinear"):
         if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 1:
             raise ValueError("EncodedImage.data must be a 1-D uint8 tensor (the file's bytes)")
         w, h = (int(v) for v in wh)
-        self.data, self.size, self.wh = data, int(size), (w, h)
+        self.data, self.size, self.wh, self.filter = data, int(size), (w, h), _check_filter(filter)
         x0, y0, x1, y1, rw, rh, ox, oy, flip = params
         self.params = resample_descriptor(w, h, (x0, y0, x1, y1), (rw, rh), (ox, oy), flip, size)
 
     def __reduce__(self):
-        return (EncodedImage, (self.data, self.params, self.size, self.wh))
+        return (_rebuild, (EncodedImage, self.filter, self.data, self.params, self.size, self.wh))
 
 
 class EncodedBatch:
     """A batch of pixel_format='jpeg' items: ``data`` ONE uint8 tensor with the files of the encoded items back to back (file i = data[offsets[i] :
     offsets[i+1]], empty for a host-decoded item), ``offsets`` [B+1] int64, ``params`` the [B, 9] int64 descriptor table, ``wh`` [B, 2] int64 frame
-    sizes, ``size`` S, ``fallback`` {batch index: HWC uint8 pixels} of the items Pillow decoded in the worker (files outside the envelope)."""
-    __slots__ = ("data", "offsets", "params", "wh", "size", "fallback")
+    sizes, ``size`` S, ``fallback`` {batch index: HWC uint8 pixels} of the items Pillow decoded in the worker (files outside the envelope),
+    ``filter`` the one resampling filter of the batch."""
+    __slots__ = ("data", "offsets", "params", "wh", "size", "fallback", "filter")
 
-    def __init__(self, data, offsets, params, wh, size, fallback=None):
+    def __init__(self, data, offsets, params, wh, size, fallback=None, *, filter="bilinear"):
         self.data, self.offsets, self.params, self.wh, self.size = data, offsets, params, wh, int(size)
         self.fallback = dict(fallback or {})
+        self.filter = _check_filter(filter)
 
     def __len__(self):
         return int(self.params.shape[0])
@@ -181,10 +208,11 @@ class EncodedBatch:
         return self.data[int(self.offsets[i]):int(self.offsets[i + 1])]
 
     def __reduce__(self):
-        return (EncodedBatch, (self.data, self.offsets, self.params, self.wh, self.size, self.fallback))
+        return (_rebuild, (EncodedBatch, self.filter, self.data, self.offsets, self.params, self.wh, self.size, self.fallback))
 
     def pin_memory(self, device=None):
-        return EncodedBatch(self.data.pin_memory(), self.offsets, self.params, self.wh, self.size, {i: p.pin_memory() for i, p in self.fallback.items()})
+        return EncodedBatch(self.data.pin_memory(), self.offsets, self.params, self.wh, self.size, {i: p.pin_memory() for i, p in self.fallback.items()},
+                            filter=self.filter)
 
 
 def collate_encoded(batch):
@@ -198,6 +226,7 @@ def collate_encoded(batch):
     size = imgs[0].size
     if any(d.size != size for d in imgs):
         raise ValueError("collate_encoded: the items of one batch must share the output size S")
+    filter = _common_filter(imgs, "collate_encoded")
     n = [int(d.data.numel()) if isinstance(d, EncodedImage) else 0 for d in imgs]
     offsets = torch.tensor([0] + n, dtype=torch.int64).cumsum(0)
     data = torch.empty(int(offsets[-1]), dtype=torch.uint8)
@@ -210,7 +239,7 @@ def collate_encoded(batch):
             fallback[i] = d.pixels
             wh.append((int(d.pixels.shape[1]), int(d.pixels.shape[0])))
     params = torch.tensor([d.params for d in imgs], dtype=torch.int64).view(len(imgs), len(DESCRIPTOR_FIELDS))
-    return [EncodedBatch(data, offsets, params, torch.tensor(wh, dtype=torch.int64).view(len(imgs), 2), size, fallback)] + \
+    return [EncodedBatch(data, offsets, params, torch.tensor(wh, dtype=torch.int64).view(len(imgs), 2), size, fallback, filter=filter)] + \
         [default_collate(list(c)) for c in cols[1:]]
 
 
@@ -256,6 +285,25 @@ class SyntheticCocoEval(Dataset):
 # task t of the 12-task protocol holds COCO super-category TASK_CATEGORIES[t] (utils/data.py:233-249, 338-353)
 TASK_CATEGORIES = (11, 6, 3, 10, 5, 12, 7, 9, 2, 8, 4, 1)
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+# CLIP's own statistics (models/clip/clip.py:77 of the reference)
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+NORMALIZATIONS = {"imagenet": (IMAGENET_MEAN, IMAGENET_STD), "clip": (CLIP_MEAN, CLIP_STD)}
+
+
+def norm_stats(normalize):
+    """(mean, std) of a normalisation: 'imagenet', 'clip', or a (mean, std) pair of three floats each."""
+    if isinstance(normalize, str):
+        if normalize not in NORMALIZATIONS:
+            raise ValueError(f"normalize must be 'imagenet', 'clip' or a (mean, std) pair, not {normalize!r}")
+        return NORMALIZATIONS[normalize]
+    try:
+        mean, std = normalize
+        mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    except (TypeError, ValueError):
+        raise ValueError(f"normalize must be 'imagenet', 'clip' or a (mean, std) pair, not {normalize!r}") from None
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("a (mean, std) pair holds three values each")
+    return mean, std
 
 
 def task_of_category(category: int) -> int:
@@ -276,18 +324,18 @@ def _to_u8_chw(img):
     return torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).contiguous()
 
 
-def normalise_u8(u8):
+def normalise_u8(u8, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """ToTensor + Normalize on a CHW (or BCHW) uint8 tensor, in the operations of _to_normalised_tensor — the f32 image the 'f32' pixel format delivers."""
     a = u8.float().div_(255.0)
     shape = (3, 1, 1)
-    return (a - torch.tensor(IMAGENET_MEAN).view(shape)) / torch.tensor(IMAGENET_STD).view(shape)
+    return (a - torch.tensor(mean).view(shape)) / torch.tensor(std).view(shape)
 
 
-def _to_normalised_tensor(img):
-    """ToTensor + Normalize(ImageNet) (utils/data.py:201-204): HWC uint8 -> CHW f32 in [0,1], then (x - mean) / std."""
+def _to_normalised_tensor(img, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """ToTensor + Normalize (utils/data.py:201-204; ImageNet statistics by default): HWC uint8 -> CHW f32 in [0,1], then (x - mean) / std."""
     a = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).float().div_(255.0)
-    mean = torch.tensor(IMAGENET_MEAN).view(3, 1, 1)
-    std = torch.tensor(IMAGENET_STD).view(3, 1, 1)
+    mean = torch.tensor(mean).view(3, 1, 1)
+    std = torch.tensor(std).view(3, 1, 1)
     return (a - mean) / std
 
 
@@ -332,7 +380,7 @@ def test_crop_params(w, h, resize=256, size=224):
     return resample_descriptor(w, h, (0, 0, w, h), (nw, nh), (left, top), False, size)
 
 
-# one image's geometry, the row of a DecodedBatch's descriptor table: crop(box).resize((rw, rh), BILINEAR), the window [ox, ox+S) x [oy, oy+S), mirrored if flip
+# one image's geometry, the row of a DecodedBatch's descriptor table: crop(box).resize((rw, rh), the batch's filter), the window [ox, ox+S) x [oy, oy+S), mirrored if flip
 DESCRIPTOR_FIELDS = ("x0", "y0", "x1", "y1", "rw", "rh", "ox", "oy", "flip")
 
 
@@ -356,11 +404,16 @@ def resample_descriptor(w, h, box, resized, origin, flip, size):
     return (x0, y0, x1, y1, rw, rh, ox, oy, int(bool(flip)))
 
 
-def apply_descriptor(img, desc, size):
-    """The descriptor applied with Pillow: the PIL image the transforms produce (the GPU kernel lpi_image_resample_u8 reproduces it byte for byte)."""
+def _pil_filter(interpolation):
+    Image = _pil()
+    return {"bilinear": Image.BILINEAR, "bicubic": Image.BICUBIC, "box": Image.BOX}[_check_filter(interpolation)]
+
+
+def apply_descriptor(img, desc, size, interpolation="bilinear"):
+    """The descriptor applied with Pillow: the PIL image the transforms produce (the GPU kernel lpi_image_resample_u8_f reproduces it byte for byte)."""
     Image = _pil()
     x0, y0, x1, y1, rw, rh, ox, oy, flip = desc
-    img = img.crop((x0, y0, x1, y1)).resize((rw, rh), Image.BILINEAR)
+    img = img.crop((x0, y0, x1, y1)).resize((rw, rh), _pil_filter(interpolation))
     if (ox, oy, rw, rh) != (0, 0, size, size):
         img = img.crop((ox, oy, ox + size, oy + size))
     if flip:
@@ -368,18 +421,20 @@ def apply_descriptor(img, desc, size):
     return img
 
 
-def train_transform(img, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), pixel_format="f32"):
-    """RandomResizedCrop(size) + RandomHorizontalFlip + ToTensor + Normalize (utils/data.py:193-204), torch RNG (train_crop_params); bilinear."""
+def train_transform(img, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), pixel_format="f32", interpolation="bilinear", normalize="imagenet"):
+    """RandomResizedCrop(size) + RandomHorizontalFlip + ToTensor + Normalize (utils/data.py:193-204), torch RNG (train_crop_params); bilinear and
+    ImageNet statistics unless told otherwise."""
     w, h = img.size
-    img = apply_descriptor(img, train_crop_params(w, h, size, scale, ratio), size)
-    return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img)
+    img = apply_descriptor(img, train_crop_params(w, h, size, scale, ratio), size, interpolation)
+    return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img, *norm_stats(normalize))
 
 
-def test_transform(img, resize=256, size=224, pixel_format="f32"):
-    """Resize(256) (shorter side, bilinear) + CenterCrop(224) + ToTensor + Normalize (utils/data.py:197-204; test_crop_params)."""
+def test_transform(img, resize=256, size=224, pixel_format="f32", interpolation="bilinear", normalize="imagenet"):
+    """Resize(256) (shorter side, bilinear) + CenterCrop(224) + ToTensor + Normalize (utils/data.py:197-204; test_crop_params).  CLIP's own
+    preprocessing (models/clip/clip.py:71-78) is resize == size, interpolation='bicubic', normalize='clip'."""
     w, h = img.size
-    img = apply_descriptor(img, test_crop_params(w, h, resize, size), size)
-    return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img)
+    img = apply_descriptor(img, test_crop_params(w, h, resize, size), size, interpolation)
+    return _to_u8_chw(img) if pixel_format == "u8" else _to_normalised_tensor(img, *norm_stats(normalize))
 
 
 def _load(image_root, name, transform):
@@ -388,24 +443,26 @@ def _load(image_root, name, transform):
         return transform(im.convert("RGB"))
 
 
-def decoded_transform(form, size=224, resize=256):
+def decoded_transform(form, size=224, resize=256, interpolation="bilinear"):
     """The transform of pixel_format='decoded': PIL image -> DecodedImage(HWC pixels, descriptor of form 'train' (train_crop_params: the random draws
     happen here, in the order of train_transform) or 'center' (test_crop_params))."""
     if form not in ("train", "center"):
         raise ValueError(f"form must be 'train' or 'center', not {form!r}")
+    _check_filter(interpolation)
 
     def transform(img):
         w, h = img.size
         desc = train_crop_params(w, h, size) if form == "train" else test_crop_params(w, h, resize, size)
         # np.asarray of a PIL image is a read-only view of a bytes object: np.array takes a writable copy (0.1 ms for 640 x 480)
-        return DecodedImage(torch.from_numpy(np.array(img if img.mode == "RGB" else img.convert("RGB"), dtype=np.uint8)), desc, size)
+        return DecodedImage(torch.from_numpy(np.array(img if img.mode == "RGB" else img.convert("RGB"), dtype=np.uint8)), desc, size,
+                            filter=interpolation)
     return transform
 
 
-def encoded_transform(form, size=224, resize=256):
+def encoded_transform(form, size=224, resize=256, interpolation="bilinear"):
     """The transform of pixel_format='jpeg': file bytes -> EncodedImage (inside the envelope; lpi_jpeg_info gives the frame size, host only) or, for
     any other file, Pillow's decode as a DecodedImage, right here (decoded_transform).  The crop draws are decoded_transform's, in its order."""
-    fallback = decoded_transform(form, size, resize)
+    fallback = decoded_transform(form, size, resize, interpolation)
 
     def transform(data):
         from lpi_amd.imageops import jpeg_info
@@ -417,8 +474,54 @@ def encoded_transform(form, size=224, resize=256):
                 return fallback(im.convert("RGB"))
         _, w, h = info
         desc = train_crop_params(w, h, size) if form == "train" else test_crop_params(w, h, resize, size)
-        return EncodedImage(torch.frombuffer(bytearray(data), dtype=torch.uint8), desc, size, (w, h))
+        return EncodedImage(torch.frombuffer(bytearray(data), dtype=torch.uint8), desc, size, (w, h), filter=interpolation)
     return transform
+
+
+PREPROCESS = ("reference", "clip")
+
+
+def preprocess_options(args, resolution=None):
+    """The image preprocessing a config asks for, as {'interpolation', 'normalize', 'eval_resize', 'size'} (None when the config names none of the keys:
+    the datasets and the engine are then built exactly as without them).  Config keys: `preprocess` = 'reference' (default: the reference's retrieval
+    loader — bilinear, ImageNet statistics, Resize(256) for evaluation, 224 x 224 items) or 'clip' (CLIP's own, models/clip/clip.py:71-78 of the
+    reference: bicubic, CLIP's statistics, Resize(n_px) + CenterCrop(n_px) for evaluation, n_px = `resolution`, the model's); `interpolation`
+    ('bilinear' | 'bicubic' | 'box'), `normalize` ('imagenet' | 'clip' | a (mean, std) pair) and `eval_resize` override single parts of it."""
+    keys = ("preprocess", "interpolation", "normalize", "eval_resize")
+    if not any(k in args for k in keys):
+        return None
+    pre = args.get("preprocess", "reference")
+    if pre not in PREPROCESS:
+        raise ValueError(f"preprocess must be 'reference' or 'clip', not {pre!r}")
+    if pre == "clip":
+        if resolution is None:
+            raise ValueError("preprocess='clip' needs the model's image resolution")
+        out = {"interpolation": "bicubic", "normalize": "clip", "eval_resize": int(resolution), "size": int(resolution)}
+    else:
+        out = {"interpolation": "bilinear", "normalize": "imagenet", "eval_resize": 256, "size": 224}
+    for k in keys[1:]:
+        if k in args:
+            out[k] = args[k]
+    _check_filter(out["interpolation"])
+    norm_stats(out["normalize"])
+    out["eval_resize"] = int(out["eval_resize"])
+    if out["eval_resize"] < out["size"]:
+        raise ValueError(f"eval_resize {out['eval_resize']} is smaller than the {out['size']} x {out['size']} centre crop")
+    return out
+
+
+def engine_pixel_norm(args, resolution=None):
+    """The EngineOptions.pixel_norm a config's preprocessing keys imply (None when it names none of them).  The datasets normalise 'f32' items on the
+    host and the engine normalises every other format on the GPU, so both must use the same statistics: a config whose engine_options carry another
+    pixel_norm than its `normalize` (an EngineOptions object always carries one) is a ValueError."""
+    pre = preprocess_options(args, resolution)
+    eo = args.get("engine_options")
+    given = eo.get("pixel_norm") if isinstance(eo, dict) else getattr(eo, "pixel_norm", None)
+    want = pre["normalize"] if pre is not None else "imagenet"
+    if given is not None and norm_stats(given) != norm_stats(want):
+        raise ValueError(f"the datasets normalise with {want!r} (config keys preprocess / normalize) but engine_options.pixel_norm is {given!r}: 'f32' "
+                         "items are normalised on the host, every other pixel format by the engine, so the two must agree")
+    return None if pre is None else want
 
 
 def _read(image_root, name):
@@ -430,17 +533,24 @@ class Coco(Dataset):
     """Training pairs of the given tasks (utils/data.py:308-382): item = (image, prompt + pre_caption(caption), 0, task)."""
 
     def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, prompt='', tasks=(0,), replay_list=(), pixel_format="f32",
-                 size=224):
+                 size=224, interpolation="bilinear", normalize="imagenet"):
         _pil()
         _check_pixel_format(pixel_format)
+        _check_filter(interpolation)
+        norm_stats(normalize)
+        # interpolation / normalize: of the default transforms (an explicit `transform` wins); 'u8', 'decoded' and 'jpeg' items are normalised on the
+        # GPU (EngineOptions.pixel_norm), 'f32' items here
+        plain = (interpolation, normalize) == ("bilinear", "imagenet") and size == 224
         if transform is None and pixel_format == "u8":
-            transform = lambda im: train_transform(im, pixel_format="u8")  # noqa: E731
-        if transform is None and pixel_format == "decoded":      # size: the S of the decoded path's output (the default transforms' 224)
-            transform = decoded_transform("train", size)
+            transform = lambda im: train_transform(im, size, pixel_format="u8", interpolation=interpolation)  # noqa: E731
+        if transform is None and pixel_format == "f32" and not plain:
+            transform = lambda im: train_transform(im, size, interpolation=interpolation, normalize=normalize)  # noqa: E731
+        if transform is None and pixel_format == "decoded":      # size: the S of the output (the default transforms' 224)
+            transform = decoded_transform("train", size, interpolation=interpolation)
         self._encoded = transform is None and pixel_format == "jpeg"     # the transform then takes the file's bytes
         if self._encoded:
-            transform = encoded_transform("train", size)
-        self.pixel_format = pixel_format
+            transform = encoded_transform("train", size, interpolation=interpolation)
+        self.pixel_format, self.interpolation, self.normalize = pixel_format, interpolation, normalize
         with open(ann_file, 'r') as f:
             records = json.load(f)
         cats = {TASK_CATEGORIES[int(t)] for t in tasks}
@@ -471,19 +581,29 @@ class CocoEval(Dataset):
     (utils/data.py:186-306; sprompt.py:433-548): text, text_cat, image, txt2img, img2txt; item = (image, image index, task)."""
 
     def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, tasks=(0,), eval_transform='center', pixel_format="f32",
-                 size=224, resize=256):
+                 size=224, resize=256, interpolation="bilinear", normalize="imagenet"):
         _pil()
         _check_pixel_format(pixel_format)
+        _check_filter(interpolation)
+        norm_stats(normalize)
+        plain = (interpolation, normalize) == ("bilinear", "imagenet") and (size, resize) == (224, 256)
+
+        def host(pf):      # the host transform of 'u8' / 'f32' with this dataset's geometry, filter and statistics
+            if eval_transform == 'center':
+                return lambda im: test_transform(im, resize, size, pixel_format=pf, interpolation=interpolation, normalize=normalize)
+            return lambda im: train_transform(im, size, pixel_format=pf, interpolation=interpolation, normalize=normalize)
         if transform is None and pixel_format == "u8":
-            base = test_transform if eval_transform == 'center' else train_transform
-            transform = lambda im: base(im, pixel_format="u8")  # noqa: E731
+            transform = host("u8")
+        if transform is None and pixel_format == "f32" and not plain and eval_transform in ('center', 'reference'):
+            transform = host("f32")
         if transform is None and pixel_format == "decoded" and eval_transform in ('center', 'reference'):
-            # size / resize: the S and Resize of the decoded path (the default transforms' 224 / 256); 'reference' takes the training form
-            transform = decoded_transform("center" if eval_transform == 'center' else "train", size, resize)
+            # size / resize: the S and Resize of the output (the default transforms' 224 / 256; CLIP's own preprocessing is resize == size);
+            # 'reference' takes the training form
+            transform = decoded_transform("center" if eval_transform == 'center' else "train", size, resize, interpolation)
         self._encoded = transform is None and pixel_format == "jpeg" and eval_transform in ('center', 'reference')
         if self._encoded:
-            transform = encoded_transform("center" if eval_transform == 'center' else "train", size, resize)
-        self.pixel_format = pixel_format
+            transform = encoded_transform("center" if eval_transform == 'center' else "train", size, resize, interpolation)
+        self.pixel_format, self.interpolation, self.normalize = pixel_format, interpolation, normalize
         with open(ann_file, 'r') as f:
             records = json.load(f)
         cats = {TASK_CATEGORIES[int(t)] for t in tasks}

@@ -13,7 +13,9 @@ no restart markers):
 
 The decode's phases (per-kernel times): rocprofv3 --kernel-trace --stats -- python3 tools/decode_pipeline_bench.py --decode-only
 
-usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--decode-only] [--out FILE.json]
+--filter bilinear | bicubic | box: the resampling filter of every dataset here (host transforms and GPU kernel alike; default bilinear).
+
+usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--filter bilinear] [--decode-only] [--out FILE.json]
 Prints one JSON object (and writes it to --out)."""
 import argparse
 import json
@@ -61,7 +63,7 @@ def kernel_us(ds, dev, reps=30, warm=5):
     torch.manual_seed(0)
     batch = D.collate_decoded([ds[i % len(ds)] for i in range(256)])[0]
     desc, nbytes = imageops.descriptors(batch)
-    ws_bytes = imageops.workspace_bytes(desc, batch.size)
+    ws_bytes = imageops.workspace_bytes(desc, batch.size, batch.filter)
     stage = torch.empty(int(nbytes.sum()), dtype=torch.uint8, pin_memory=True)
     imageops.gather(batch, stage, nbytes, 8)
     src = stage.to(dev)
@@ -72,13 +74,14 @@ def kernel_us(ds, dev, reps=30, warm=5):
     for r in range(warm + reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(s)
-        imageops.launch(desc, src, int(nbytes.sum()), ws, ws_bytes, out, batch.size, s)
+        imageops.launch(desc, src, int(nbytes.sum()), ws, ws_bytes, out, batch.size, s, batch.filter)
         e1.record(s)
         e1.synchronize()
         if r >= warm:
             times.append(1e3 * e0.elapsed_time(e1))
     return {"median_us": round(float(np.median(times)), 1), "p10_p90_us": [round(float(np.percentile(times, q)), 1) for q in (10, 90)],
-            "source_MB": round(float(nbytes.sum()) / 1e6, 1), "reps": reps, "warmup": warm}
+            "source_MB": round(float(nbytes.sum()) / 1e6, 1), "workspace_MB": round(ws_bytes / 1e6, 2), "filter": batch.filter, "reps": reps,
+            "warmup": warm}
 
 
 def jpeg_decode(ds, root, dev, reps=30, warm=5):
@@ -114,14 +117,14 @@ def jpeg_decode(ds, root, dev, reps=30, warm=5):
             "batch_fallbacks": len(batch.fallback), "folder_files": len(files), "folder_files_outside_envelope": outside, "reps": reps, "warmup": warm}
 
 
-def loop_pairs_per_s(root, pf, workers, steps, warm, dev):
+def loop_pairs_per_s(root, pf, workers, steps, warm, dev, filter="bilinear"):
     from lpi_amd.retrieval.methods.sprompt import SPrompts
     args = json.load(open(os.path.join(REPO, "lpi_amd", "retrieval", "configs", "lpi", "coco_lpi.json")))
     args.update(device=[dev], compute_dtype="bf16", honor_prompt_depth=True, prompt_depth=3, batch_size=256, epochs=1, num_workers=workers,
                 pixel_format=pf)
     m = SPrompts(args)
     m._network.update_fc(0)
-    ds = D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf)
+    ds = D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf, interpolation=filter)
     collate = D.collate_decoded if pf == "decoded" else (D.collate_encoded if pf == "jpeg" else (D.collate_keep_images if workers == 0 else None))
     loader = DataLoader(ds, batch_size=256, shuffle=False, num_workers=workers, collate_fn=collate, persistent_workers=False)
     opt, _ = m._setup_training()
@@ -149,20 +152,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=2, help="untimed steps; at least prefetch_factor (2) x workers + 2 whatever this says")
     ap.add_argument("--workers", default="0,8,14")
     ap.add_argument("--host-items", type=int, default=200)
+    ap.add_argument("--filter", default="bilinear", choices=list(imageops.FILTERS), help="Pillow resampling filter of the transforms and the kernel")
     ap.add_argument("--decode-only", action="store_true", help="write the folder and run section 3 only (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from lpi_amd.synth_bpe import ensure_vocab
     ensure_vocab()
     dev = torch.device("cuda:0")
-    rec = {"tool": "tools/decode_pipeline_bench.py", "source": "640 x 480 q90 JPEG", "batch": 256, "host_threads": torch.get_num_threads()}
+    rec = {"tool": "tools/decode_pipeline_bench.py", "source": "640 x 480 q90 JPEG", "batch": 256, "host_threads": torch.get_num_threads(),
+           "filter": a.filter}
     with tempfile.TemporaryDirectory() as root:
         workers = [int(x) for x in a.workers.split(",")]
         warm = {w: max(a.warmup, 2 * w + 2) for w in workers}
         write_folder(root, a.images, 256 * (a.steps + max(warm.values()) + 1), 256)
         formats = ("u8", "decoded", "jpeg")
-        tr = {pf: D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf) for pf in formats}
-        ev = {pf: D.CocoEval(image_root=root, ann_file=os.path.join(root, "val.json"), tasks=[0], pixel_format=pf) for pf in formats}
+        tr = {pf: D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf, interpolation=a.filter)
+              for pf in formats}
+        ev = {pf: D.CocoEval(image_root=root, ann_file=os.path.join(root, "val.json"), tasks=[0], pixel_format=pf, interpolation=a.filter)
+              for pf in formats}
         if a.decode_only:
             rec["jpeg_decode_256"] = jpeg_decode(tr["jpeg"], root, dev)
             print(json.dumps(rec))
@@ -179,7 +186,7 @@ def main():
         rec["loop_pairs_per_s"] = {}
         for w in workers:
             for pf in formats:
-                rec["loop_pairs_per_s"][f"{pf}_workers{w}"] = loop_pairs_per_s(root, pf, w, a.steps, warm[w], dev)
+                rec["loop_pairs_per_s"][f"{pf}_workers{w}"] = loop_pairs_per_s(root, pf, w, a.steps, warm[w], dev, a.filter)
                 print(json.dumps({f"{pf}_workers{w}": rec["loop_pairs_per_s"][f"{pf}_workers{w}"]}), flush=True)
     line = json.dumps(rec)
     print(line)
