@@ -649,6 +649,31 @@ int lpi_jpeg_decode_workspace(int B, const void* host, const long* offsets, long
 int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out, long out_bytes,
                        int* status, void* ws, long ws_bytes, void* stream);
 
+/* ---- progressive JPEG files in the same decoder: the _x entry points take a flags word.  flags = 0 is the calls above: the same verdicts, workspace
+ * bytes, launches and output bytes.  Unknown flag bits are LPI_EINVAL before any copy or launch.
+ * LPI_JPEG_PROGRESSIVE widens THE ENVELOPE by SOF2 files (8-bit, Huffman; the component, sampling, colour-space and size rules above unchanged;
+ * LPI_JPEG_MAX_SCAN_BYTES counts from the first scan's start) whose scan script is complete and orderly:
+ *   - DC scans Ss = Se = 0 with 1 to nc components, in the frame's order when interleaved; AC scans one component, 1 <= Ss <= Se <= 63; Al <= 13;
+ *   - for every coefficient of every component the first scan that holds it has Ah = 0, each later one has Ah = the previous Al and Al = Ah - 1, the
+ *     last one Al = 0; a component's AC scans come after its first DC scan; at the file's end all 64 coefficients of every component are fully
+ *     refined (libjpeg-turbo only warns on other scripts and smooths the blocks of an incomplete one: Pillow's pixels are then not the IDCT of
+ *     the coefficients, so those files stay the host's);
+ *   - every scan uses the Huffman tables and the restart interval in force at its SOS (DHT and DRI between scans are allowed, DQT is not);
+ *   - at most LPI_JPEG_MAX_SCANS scans (Pillow's own files have 10, or 6 for grayscale).
+ * The parser walks the whole file (every SOS, the entropy-coded bytes up to the next marker other than FF00 / RSTn).  A file that ends inside a scan
+ * after a complete script is inside the envelope; its status is then nonzero.  One batch may mix baseline and progressive files.  The status bits
+ * keep their meaning (2 also: a refinement symbol of a size other than 1).  For B files with S progressive scans in R rounds (scans that touch the
+ * same coefficients of a component run in file order, in different rounds): two copies, one clear and 5 + R launches; 4 when S = 0. */
+#define LPI_JPEG_PROGRESSIVE 1
+#define LPI_JPEG_MAX_SCANS 32
+/* lpi_jpeg_info_x fills LPI_JPEG_INFO_X fields: the LPI_JPEG_INFO of lpi_jpeg_info, then {the frame is SOF2 and was parsed as such (only with
+ * LPI_JPEG_PROGRESSIVE), its scans inside the envelope (1 for a baseline file whose SOS was reached, else 0)}. */
+#define LPI_JPEG_INFO_X 10
+int lpi_jpeg_info_x(int flags, const void* data, long nbytes, long* info);
+int lpi_jpeg_decode_workspace_x(int flags, int B, const void* host, const long* offsets, long* bytes);
+int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out,
+                         long out_bytes, int* status, void* ws, long ws_bytes, void* stream);
+
 void* lpi_bpe_create(const char* merges_utf8, long nbytes);
 void lpi_bpe_destroy(void* handle);
 int lpi_bpe_encode(void* handle, const char* text_utf8, int32_t* ids, int max_ids);

@@ -134,6 +134,10 @@ SIGNATURES = {
     "lpi_jpeg_info": [_P, _L, _P],
     "lpi_jpeg_decode_workspace": [_I, _P, _P, _P],
     "lpi_jpeg_decode_u8": [_I, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _P],
+    # the same with a flags word (LPI_JPEG_PROGRESSIVE: SOF2 files with a complete scan script)
+    "lpi_jpeg_info_x": [_I, _P, _L, _P],
+    "lpi_jpeg_decode_workspace_x": [_I, _I, _P, _P, _P],
+    "lpi_jpeg_decode_u8_x": [_I, _I, _P, _P, _P, _L, _P, _P, _L, _P, _P, _L, _P],
     "lpi_bpe_create": [_P, _L],
     "lpi_bpe_destroy": [_P],
     "lpi_interact_workspace_floats": [_I, _I, _I, _I],
@@ -147,7 +151,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_bpe_create": c_void_p, "lpi_bpe_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 607
+EXPECTED_ABI = 608
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

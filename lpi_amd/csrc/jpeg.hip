@@ -1,8 +1,9 @@
-// Baseline JPEG files -> packed HWC RGB uint8 pixels on the GPU (pixel_format='jpeg', lpi_amd/imageops.py), byte for byte what Pillow 12
-// (libjpeg-turbo, default settings) gives for np.asarray(Image.open(f).convert("RGB")).  tests/jpeg_restate.py restates every step in numpy.
+// JPEG files -> packed HWC RGB uint8 pixels on the GPU (pixel_format='jpeg', lpi_amd/imageops.py), byte for byte what Pillow 12 (libjpeg-turbo,
+// default settings) gives for np.asarray(Image.open(f).convert("RGB")): baseline files, and with LPI_JPEG_PROGRESSIVE progressive files whose scan
+// script is complete.  tests/jpeg_restate.py and tests/jpeg_progressive.py restate every step in numpy / plain Python.
 //
 // The host parses the headers (parse_headers: the one place that decides the envelope), builds one JDesc per image and copies the table into the
-// workspace; four launches then do the rest:
+// workspace; four launches then do the rest for baseline files:
 //   unstuff_kernel   one workgroup per image: the entropy-coded bytes without the 0xFF00 stuffing, split at the RSTn markers, up to the first other
 //                    marker (rounds of 4096 bytes, a block-wide scan per round).  Out: the unstuffed bytes and the end of every restart interval.
 //   huff_kernel      one workgroup per image: Huffman decoding.  Every restart interval (segment) is cut into k chunks.  A chunk's decoder state at
@@ -16,8 +17,20 @@
 //   color_kernel     one thread per output pixel: jdsample.c's fancy upsampling of the chroma planes (2x1, 2x2; plain replication for chroma
 //                    planes at most 2 samples wide), jdcolor.c's YCbCr -> RGB tables; grayscale replicated into R, G, B.
 //
+// A progressive file (JDesc.k = 0: unstuff_kernel only clears its status, huff_kernel passes it over) has one PScan per scan, with the Huffman tables
+// and the restart interval in force at its SOS; between huff_kernel and idct_kernel its coefficients are built up scan by scan (jdphuff.c):
+//   punstuff_kernel  one workgroup per scan: unstuff_kernel's work on the scan's own bytes.
+//   pscan_kernel     one launch per ROUND of scans; one wave per scan.  The host puts a scan into round 1 + the latest round of an earlier scan that
+//                    touched one of its (component, coefficient) pairs, so scans over the same coefficients run in file order and the others side by
+//                    side (Pillow's 10 scans: 5 + 4 + 1).  A lane decodes one restart interval from its start: DC first / DC refinement / AC first
+//                    (EOB runs) / AC refinement (correction bits, which depend on the coefficients of the earlier scans); a scan without restart
+//                    markers is one lane's.  A one-component scan walks the component's own block grid, not the MCU-padded one.  A scan writes only
+//                    the coefficients of its own band, one int16 at a time: the scans of a round share blocks.
+//
 // Bounds: every loop runs over counts the host validated (rounds over the entropy bytes, symbols at most one per bit of a chunk, sync rounds at
-// most k + 1); the bit reader reads only its own image's unstuffed bytes and returns zeros past its segment's end.
+// most k + 1; a progressive scan's MCUs, the coefficients of its band, at most LPI_JPEG_MAX_SCANS rounds); block indices come from those counts and
+// coefficient indices stay inside [Ss, Se] whatever the bits say; the bit reader reads only its own image's (scan's) unstuffed bytes and returns
+// zeros past its segment's end.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -60,14 +73,39 @@ struct JDesc {
     HuffSpec dc[3], ac[3];          // tables of each scan component
 };
 
+// One scan of a progressive file (device copies behind the sample planes in the workspace, sorted by launch round).
+struct PScan {
+    long src_lo, src_hi;            // its entropy-coded bytes in the caller's device bytes
+    long ws_unst, unst_cap;         // unstuffed bytes (capacity: src_hi - src_lo + 16)
+    long ws_seg;                    // int32 end (unstuffed byte) of every segment
+    long nmcu;                      // scan MCUs: the frame's MCUs (interleaved), or the blocks of the component's own grid
+    int img;                        // its image's JDesc
+    int nseg, ri;                   // restart interval in scan MCUs
+    int ns, comp[3];                // frame components
+    int ss, se, ah, al;
+    int gw;                         // one-component scan: blocks per row of the component's own grid
+    HuffSpec tab[3];                // first DC scan: the DC table of each scan component; AC scan: tab[0]
+};
+
 __device__ __constant__ int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// zigzag index of the coefficient at natural index n (compile-time indices only)
+constexpr int kUnzigzag[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                               10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
 const int kZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ------------------------------------------------------------------------------------------------------------------------------ host parser
+// One scan of a progressive file: its entropy-coded bytes [ent, end) of the file, its header, the restart interval and the Huffman tables in force
+// at its SOS (tab[i]: the DC table of scan component i for a first DC scan, tab[0]: the AC table of an AC scan), and the launch round it runs in.
+struct ScanHd {
+    long ent = 0, end = 0;
+    int ns = 0, sc[3] = {}, ss = 0, se = 0, ah = 0, al = 0, ri = 0, level = 0;
+    HuffSpec tab[3] = {};
+};
+
 struct Header {
     int w = 0, h = 0, nc = 0, prec = 0;
     int cid[4] = {}, ch[4] = {}, cv[4] = {}, ctq[4] = {};
@@ -79,6 +117,9 @@ struct Header {
     HuffSpec hs[2][4] = {};
     long ent = 0;
     bool gpu = false;       // inside the envelope
+    bool prog = false;      // SOF2, parsed with LPI_JPEG_PROGRESSIVE
+    int lvl[3][64] = {};    // the launch round of the last scan that touched each coefficient of each component
+    std::vector<ScanHd> scans;       // of a progressive file inside the envelope, in file order
 };
 
 inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
@@ -96,13 +137,84 @@ bool huff_ok(const HuffSpec& t, int count, bool dc) {
     return true;
 }
 
+// One SOS of a SOF2 file against the progressive envelope; appends it to hd.scans.  false: the file is the host's.
+bool progressive_scan(Header& hd, const uint8_t* s, long ent, long end, int (*al_cur)[64]) {
+    if (hd.scans.empty()) {
+        bool ok = hd.prec == 8 && hd.h > 0 && (long)hd.w * hd.h <= LPI_JPEG_MAX_PIXELS;
+        if (hd.nc == 3) {
+            ok = ok && (hd.jfif || !hd.adobe) && (hd.jfif || !(hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'));
+            const bool luma = (hd.ch[0] == 1 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 2);
+            ok = ok && luma && hd.ch[1] == 1 && hd.cv[1] == 1 && hd.ch[2] == 1 && hd.cv[2] == 1;
+        } else {
+            ok = ok && hd.nc == 1;
+        }
+        if (!ok) return false;
+        hd.ent = ent;
+    }
+    if ((int)hd.scans.size() >= LPI_JPEG_MAX_SCANS || hd.ns > 3) return false;
+    ScanHd sc;
+    sc.ent = ent;
+    sc.end = end;
+    sc.ns = hd.ns;
+    sc.ss = s[1 + 2 * hd.ns];
+    sc.se = s[2 + 2 * hd.ns];
+    sc.ah = s[3 + 2 * hd.ns] >> 4;
+    sc.al = s[3 + 2 * hd.ns] & 15;
+    sc.ri = hd.ri;
+    for (int i = 0; i < hd.ns; ++i) {
+        sc.sc[i] = hd.sc[i];
+        if (i > 0 && hd.sc[i] <= hd.sc[i - 1]) return false;           // an interleaved scan lists its components in the frame's order
+    }
+    if (sc.al > 13 || sc.ss > sc.se || sc.se > 63) return false;
+    if (sc.ss == 0 ? sc.se != 0 : sc.ns != 1) return false;            // DC scans hold DC only; AC scans hold one component
+    if (sc.ah != 0 && sc.al != sc.ah - 1) return false;
+    int level = 0;
+    for (int i = 0; i < sc.ns; ++i) {
+        const int c = sc.sc[i];
+        if (sc.ss > 0 && al_cur[c][0] < 0) return false;               // AC before the component's first DC scan
+        for (int k = sc.ss; k <= sc.se; ++k) {
+            if (sc.ah == 0 ? al_cur[c][k] != -1 : al_cur[c][k] != sc.ah) return false;
+            al_cur[c][k] = sc.al;
+            level = std::max(level, hd.lvl[c][k]);
+        }
+        if (sc.ss == 0 && sc.ah == 0) {
+            if (!hd.hdef[0][hd.std_[i]]) return false;
+            sc.tab[i] = hd.hs[0][hd.std_[i]];
+        } else if (sc.ss > 0) {
+            if (!hd.hdef[1][hd.sta[i]]) return false;
+            sc.tab[0] = hd.hs[1][hd.sta[i]];
+        }
+    }
+    // scans over the same (component, coefficient) run in file order: round = 1 + the latest round of an earlier scan that touched one of them
+    sc.level = level + 1;
+    for (int i = 0; i < sc.ns; ++i)
+        for (int k = sc.ss; k <= sc.se; ++k) hd.lvl[sc.sc[i]][k] = sc.level;
+    hd.scans.push_back(sc);
+    return true;
+}
+
 // 0: parsed (hd.gpu says whether the GPU decodes it); LPI_EINVAL: a structural error in the headers.  A file without SOI is parsed as "host".
-int parse_headers(const uint8_t* d, long n, Header& hd) {
+// flags & LPI_JPEG_PROGRESSIVE: a SOF2 file is parsed to its end (every SOS, the DHT / DRI between the scans) and is inside the envelope when its
+// scan script is complete and orderly (include/lpi_hip.h); hd.scans then holds its scans.  Without the flag a SOF2 file is the host's at its SOF.
+int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
     hd = Header();
     if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 0;
     long p = 2;
+    int al_cur[3][64];                      // progressive: the Al every coefficient of every component has been decoded to (-1: not yet)
+    for (auto& c : al_cur)
+        for (int& v : c) v = -1;
     for (int guard = 0; guard < (1 << 20); ++guard) {
         while (p + 1 < n && d[p] == 0xFF && d[p + 1] == 0xFF) ++p;
+        if (hd.prog && !hd.scans.empty() && (p + 1 >= n || (d[p] == 0xFF && d[p + 1] == 0xD9))) {
+            // EOI, or the end of the data (a truncated file: the decoder then meets the end of its last scan): the script must be complete
+            bool ok = true;
+            for (int c = 0; c < hd.nc; ++c)
+                for (int k = 0; k < 64; ++k) ok = ok && al_cur[c][k] == 0;
+            ok = ok && n - hd.ent <= LPI_JPEG_MAX_SCAN_BYTES;
+            hd.gpu = ok;
+            if (!ok) hd.scans.clear();
+            return 0;
+        }
         if (p + 4 > n || d[p] != 0xFF) return LPI_EINVAL;
         const int m = d[p + 1];
         if (m == 0xD8 || m == 0xD9 || (m >= 0xD0 && m <= 0xD7) || m == 0x01 || m == 0x00) return LPI_EINVAL;
@@ -126,7 +238,23 @@ int parse_headers(const uint8_t* d, long n, Header& hd) {
                 if (hd.ch[i] < 1 || hd.ch[i] > 4 || hd.cv[i] < 1 || hd.cv[i] > 4 || hd.ctq[i] > 3) return LPI_EINVAL;
             }
             hd.sof = true;
+        } else if (m == 0xC2 && (flags & LPI_JPEG_PROGRESSIVE)) {
+            if (hd.sof || sl < 6) return LPI_EINVAL;
+            hd.prec = s[0];
+            hd.h = rd16(s + 1);
+            hd.w = rd16(s + 3);
+            hd.nc = s[5];
+            if (hd.nc < 1 || hd.nc > 4 || sl != 6 + 3 * hd.nc || hd.w == 0) return LPI_EINVAL;
+            for (int i = 0; i < hd.nc; ++i) {
+                hd.cid[i] = s[6 + 3 * i];
+                hd.ch[i] = s[7 + 3 * i] >> 4;
+                hd.cv[i] = s[7 + 3 * i] & 15;
+                hd.ctq[i] = s[8 + 3 * i];
+                if (hd.ch[i] < 1 || hd.ch[i] > 4 || hd.cv[i] < 1 || hd.cv[i] > 4 || hd.ctq[i] > 3) return LPI_EINVAL;
+            }
+            hd.sof = hd.prog = true;
         } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            if (hd.prog) return LPI_EINVAL;                     // a second frame header
             if (sl >= 6) {                                      // progressive, lossless, arithmetic-coded, hierarchical: the host decodes
                 hd.h = rd16(s + 1);
                 hd.w = rd16(s + 3);
@@ -152,6 +280,7 @@ int parse_headers(const uint8_t* d, long n, Header& hd) {
                 q += 17 + cnt;
             }
         } else if (m == 0xDB) {
+            if (!hd.scans.empty()) { hd.scans.clear(); return 0; }          // quantisation tables between the scans: the host's
             long q = 0;
             while (q < sl) {
                 const int pq = s[q] >> 4, tq = s[q] & 15;
@@ -182,10 +311,28 @@ int parse_headers(const uint8_t* d, long n, Header& hd) {
                 hd.sc[i] = f;
                 hd.std_[i] = s[2 + 2 * i] >> 4;
                 hd.sta[i] = s[2 + 2 * i] & 15;
-                if (hd.std_[i] > 3 || hd.sta[i] > 3 || !hd.hdef[0][hd.std_[i]] || !hd.hdef[1][hd.sta[i]]) return LPI_EINVAL;
+                if (hd.std_[i] > 3 || hd.sta[i] > 3) return LPI_EINVAL;
+                if (!hd.prog && (!hd.hdef[0][hd.std_[i]] || !hd.hdef[1][hd.sta[i]])) return LPI_EINVAL;
             }
             for (int c = 0; c < hd.nc; ++c)
                 if (!hd.qdef[hd.ctq[c]]) return LPI_EINVAL;
+            if (hd.prog) {
+                // the scan's entropy-coded bytes: up to the next marker that is neither a stuffed 0xFF00 nor RSTn (as unstuff_range reads them)
+                long q = p;
+                while (q < n) {
+                    const void* f = std::memchr(d + q, 0xFF, (size_t)(n - q));
+                    if (!f) { q = n; break; }
+                    q = static_cast<const uint8_t*>(f) - d;
+                    if (q + 1 >= n) break;
+                    const int nx = d[q + 1];
+                    if (nx == 0x00 || (nx >= 0xD0 && nx <= 0xD7)) q += 2;
+                    else if (nx == 0xFF) q += 1;
+                    else break;
+                }
+                if (!progressive_scan(hd, s, p, q, al_cur)) { hd.scans.clear(); return 0; }
+                p = q;
+                continue;
+            }
             hd.ent = p;
             const int ss = s[1 + 2 * hd.ns], se = s[2 + 2 * hd.ns], ahal = s[3 + 2 * hd.ns];
             bool ok = hd.ns == hd.nc && ss == 0 && se == 63 && ahal == 0 && hd.prec == 8 && hd.h > 0;
@@ -213,43 +360,75 @@ int parse_headers(const uint8_t* d, long n, Header& hd) {
 inline long align256(long v) { return (v + 255) / 256 * 256; }
 inline long desc_bytes(int B) { return align256((long)B * (long)sizeof(JDesc)); }
 
+// Scan MCUs of one scan of a progressive file: the frame's MCUs for an interleaved scan; for a one-component scan the blocks of the component's own
+// grid, ceil(cw / 8) x ceil(ch / 8) with cw = ceil(w * Hc / Hmax) (gw: its blocks per row), not the MCU-padded grid the coefficient arrays have.
+inline long scan_mcus(const Header& hd, const ScanHd& sc, int* gw) {
+    const int hm = hd.nc == 1 ? 1 : hd.ch[0], vm = hd.nc == 1 ? 1 : hd.cv[0];
+    if (sc.ns > 1) {
+        *gw = 0;
+        return (long)((hd.w + 8 * hm - 1) / (8 * hm)) * ((hd.h + 8 * vm - 1) / (8 * vm));
+    }
+    const int c = sc.sc[0];
+    const int H = hd.nc == 1 ? 1 : hd.ch[c], V = hd.nc == 1 ? 1 : hd.cv[c];
+    const long cw = ((long)hd.w * H + hm - 1) / hm, chh = ((long)hd.h * V + vm - 1) / vm;
+    *gw = (int)((cw + 7) / 8);
+    return (long)*gw * ((chh + 7) / 8);
+}
+
 // Fills the descriptors (their ws_* offsets from ws_base on) and returns the workspace bytes, or LPI_EINVAL.  zero_lo / zero_hi: the coefficient
-// range the caller clears before huff_kernel.
-int plan(int B, const uint8_t* host, const long* offsets, std::vector<JDesc>* descs, long* bytes, long* zero_lo, long* zero_hi) {
-    if (B < 1 || B > 65535 || !host || !offsets) return LPI_EINVAL;
+// range the caller clears before huff_kernel.  Progressive files (flags & LPI_JPEG_PROGRESSIVE) get a JDesc with k = 0, which the baseline kernels
+// pass over, and one PScan per scan: scans sorted by launch round, rounds[r] = how many run in round r, at ws_scans in the workspace (behind
+// everything a batch of baseline files has: such a batch needs the same bytes with and without the flag).
+int plan(int flags, int B, const uint8_t* host, const long* offsets, std::vector<JDesc>* descs, long* bytes, long* zero_lo, long* zero_hi,
+         std::vector<PScan>* scans = nullptr, std::vector<int>* rounds = nullptr, long* ws_scans = nullptr) {
+    if (B < 1 || B > 65535 || !host || !offsets || (flags & ~LPI_JPEG_PROGRESSIVE)) return LPI_EINVAL;
     if (descs) descs->assign(B, JDesc());
     long ws = desc_bytes(B);
     std::vector<Header> hds(B);
     std::vector<long> coef_blocks(B);
+    long nscans = 0;
     for (int i = 0; i < B; ++i) {
         if (offsets[i] < 0 || offsets[i + 1] < offsets[i] + 4) return LPI_EINVAL;
         Header& hd = hds[i];
-        if (parse_headers(host + offsets[i], offsets[i + 1] - offsets[i], hd) != 0 || !hd.gpu) return LPI_EINVAL;
-        const long ent_len = offsets[i + 1] - offsets[i] - hd.ent;
-        if (ent_len < 0) return LPI_EINVAL;
-        ws += align256(ent_len + 16);
+        if (parse_headers(host + offsets[i], offsets[i + 1] - offsets[i], hd, flags) != 0 || !hd.gpu) return LPI_EINVAL;
         const int hm = hd.nc == 1 ? 1 : hd.ch[0], vm = hd.nc == 1 ? 1 : hd.cv[0];
         const long mcux = (hd.w + 8 * hm - 1) / (8 * hm), mcuy = (hd.h + 8 * vm - 1) / (8 * vm);
         const long nmcu = mcux * mcuy;
-        const long nseg = hd.ri ? (nmcu + hd.ri - 1) / hd.ri : 1;
-        ws += align256(nseg * 4);
+        if (hd.prog) {
+            for (const ScanHd& sc : hd.scans) {
+                int gw = 0;
+                const long n = scan_mcus(hd, sc, &gw);
+                ws += align256(sc.end - sc.ent + 16);
+                ws += align256((sc.ri ? (n + sc.ri - 1) / sc.ri : 1) * 4);
+            }
+            nscans += (long)hd.scans.size();
+        } else {
+            const long ent_len = offsets[i + 1] - offsets[i] - hd.ent;
+            if (ent_len < 0) return LPI_EINVAL;
+            ws += align256(ent_len + 16);
+            const long nseg = hd.ri ? (nmcu + hd.ri - 1) / hd.ri : 1;
+            ws += align256(nseg * 4);
+        }
         coef_blocks[i] = nmcu * (hd.nc == 1 ? 1 : hm * vm + 2);
     }
     const long coef_lo = ws;
     for (int i = 0; i < B; ++i) ws += align256(coef_blocks[i] * 128);
     const long coef_hi = ws;
     for (int i = 0; i < B; ++i) ws += align256(coef_blocks[i] * 64);
+    const long scans_at = ws;
+    ws += align256(nscans * (long)sizeof(PScan));
     if (zero_lo) *zero_lo = coef_lo;
     if (zero_hi) *zero_hi = coef_hi;
+    if (ws_scans) *ws_scans = scans_at;
     *bytes = ws;
     if (!descs) return 0;
     // second walk: the offsets
+    std::vector<PScan> ps;
+    std::vector<int> level;
     long at = desc_bytes(B), at_coef = coef_lo, at_plane = coef_hi;
     for (int i = 0; i < B; ++i) {
         const Header& hd = hds[i];
         JDesc& j = (*descs)[i];
-        j.src_ent = offsets[i] + hd.ent;
-        j.src_end = offsets[i + 1];
         j.w = hd.w;
         j.h = hd.h;
         j.nc = hd.nc;
@@ -258,32 +437,61 @@ int plan(int B, const uint8_t* host, const long* offsets, std::vector<JDesc>* de
         j.mcux = (hd.w + 8 * j.hs - 1) / (8 * j.hs);
         j.mcuy = (hd.h + 8 * j.vs - 1) / (8 * j.vs);
         const long nmcu = (long)j.mcux * j.mcuy;
-        j.ri = hd.ri ? hd.ri : (int)std::min(nmcu, (long)0x7fffffff);
-        j.nseg = (int)((nmcu + j.ri - 1) / j.ri);
         j.dw = (hd.w + j.hs - 1) / j.hs;
         j.dh = (hd.h + j.vs - 1) / j.vs;
-        const long ent_len = j.src_end - j.src_ent;
-        j.ws_unst = at;
-        j.unst_cap = ent_len + 16;
-        at += align256(ent_len + 16);
-        j.ws_seg = at;
-        at += align256((long)j.nseg * 4);
-        int b = 0;
-        for (int s = 0; s < hd.ns; ++s) {
-            const int f = hd.sc[s];
-            const int H = hd.nc == 1 ? 1 : hd.ch[f], V = hd.nc == 1 ? 1 : hd.cv[f];
-            j.scomp[s] = f;
-            j.dc[s] = hd.hs[0][hd.std_[s]];
-            j.ac[s] = hd.hs[1][hd.sta[s]];
-            for (int y = 0; y < V; ++y)
-                for (int x = 0; x < H; ++x) {
-                    j.blk_comp[b] = s;
-                    j.blk_dx[b] = x;
-                    j.blk_dy[b] = y;
-                    ++b;
-                }
+        long ent_len = 0;
+        if (hd.prog) {
+            for (const ScanHd& sc : hd.scans) {
+                PScan q = PScan();
+                q.nmcu = scan_mcus(hd, sc, &q.gw);
+                q.ri = sc.ri ? sc.ri : (int)std::min(q.nmcu, (long)0x7fffffff);
+                q.nseg = (int)((q.nmcu + q.ri - 1) / q.ri);
+                q.src_lo = offsets[i] + sc.ent;
+                q.src_hi = offsets[i] + sc.end;
+                q.ws_unst = at;
+                q.unst_cap = sc.end - sc.ent + 16;
+                at += align256(q.unst_cap);
+                q.ws_seg = at;
+                at += align256((long)q.nseg * 4);
+                q.img = i;
+                q.ns = sc.ns;
+                for (int c = 0; c < 3; ++c) q.comp[c] = sc.sc[c];
+                q.ss = sc.ss;
+                q.se = sc.se;
+                q.ah = sc.ah;
+                q.al = sc.al;
+                std::memcpy(q.tab, sc.tab, sizeof(q.tab));
+                ps.push_back(q);
+                level.push_back(sc.level);
+            }
+        } else {
+            j.src_ent = offsets[i] + hd.ent;
+            j.src_end = offsets[i + 1];
+            j.ri = hd.ri ? hd.ri : (int)std::min(nmcu, (long)0x7fffffff);
+            j.nseg = (int)((nmcu + j.ri - 1) / j.ri);
+            ent_len = j.src_end - j.src_ent;
+            j.ws_unst = at;
+            j.unst_cap = ent_len + 16;
+            at += align256(ent_len + 16);
+            j.ws_seg = at;
+            at += align256((long)j.nseg * 4);
+            int b = 0;
+            for (int s = 0; s < hd.ns; ++s) {
+                const int f = hd.sc[s];
+                const int H = hd.nc == 1 ? 1 : hd.ch[f], V = hd.nc == 1 ? 1 : hd.cv[f];
+                j.scomp[s] = f;
+                j.dc[s] = hd.hs[0][hd.std_[s]];
+                j.ac[s] = hd.hs[1][hd.sta[s]];
+                for (int y = 0; y < V; ++y)
+                    for (int x = 0; x < H; ++x) {
+                        j.blk_comp[b] = s;
+                        j.blk_dx[b] = x;
+                        j.blk_dy[b] = y;
+                        ++b;
+                    }
+            }
+            j.bpm = b;
         }
-        j.bpm = b;
         for (int c = 0; c < hd.nc; ++c) {
             const int H = hd.nc == 1 ? 1 : hd.ch[c], V = hd.nc == 1 ? 1 : hd.cv[c];
             j.bw[c] = j.mcux * H;
@@ -296,11 +504,25 @@ int plan(int B, const uint8_t* host, const long* offsets, std::vector<JDesc>* de
         }
         at_coef = coef_lo + (at_coef - coef_lo + 255) / 256 * 256;     // the per-image blocks as counted above
         at_plane = coef_hi + (at_plane - coef_hi + 255) / 256 * 256;
+        if (hd.prog) {
+            j.k = 0;            // the baseline kernels pass this image over
+            continue;
+        }
         // chunks per segment: at least MIN_CHUNK bytes each on average, at most HT chunks per image (one per thread); 1 when segments are many
         long k = j.nseg <= HT / 2 ? HT / j.nseg : 1;
         const long by_len = ent_len / ((long)j.nseg * MIN_CHUNK);
         if (k > by_len) k = by_len;
         j.k = (int)(k < 1 ? 1 : k);
+    }
+    if (scans && rounds) {
+        scans->clear();
+        rounds->assign(LPI_JPEG_MAX_SCANS + 1, 0);
+        for (int r = 1; r <= LPI_JPEG_MAX_SCANS; ++r)
+            for (size_t q = 0; q < ps.size(); ++q)
+                if (level[q] == r) {
+                    scans->push_back(ps[q]);
+                    ++(*rounds)[r];
+                }
     }
     return 0;
 }
@@ -322,15 +544,12 @@ __device__ inline int block_excl_scan(int v, int* sh, int& total) {
     return r;
 }
 
-__global__ __launch_bounds__(NT) void unstuff_kernel(const JDesc* __restrict__ descs, const uint8_t* __restrict__ src, uint8_t* __restrict__ ws,
-                                                     int* __restrict__ status) {
-    __shared__ int sh[NT];
-    __shared__ long s_end;
-    const JDesc& d = descs[blockIdx.x];
+// One workgroup: src[lo, hi) without the stuffing into un, the end of each of the nseg restart intervals into seg.  Returns the status flags (valid
+// in thread 0).  sh: NT ints of LDS, s_end: one long.
+__device__ inline int unstuff_range(const uint8_t* __restrict__ src, long lo, long hi, uint8_t* __restrict__ un, int* __restrict__ seg, int nseg,
+                                    int* sh, long* s_end_p) {
+    long& s_end = *s_end_p;
     const int t = threadIdx.x;
-    uint8_t* un = ws + d.ws_unst;
-    int* seg = reinterpret_cast<int*>(ws + d.ws_seg);
-    const long lo = d.src_ent, hi = d.src_end;
     long emitted = 0;
     int nrst = 0, flags = 0;
     if (t == 0) s_end = hi;
@@ -381,7 +600,7 @@ __global__ __launch_bounds__(NT) void unstuff_kernel(const JDesc* __restrict__ d
                 const int nx = src[i + 1];
                 if (nx == 0x00) un[w++] = 0xFF;
                 else if (nx >= 0xD0 && nx <= 0xD7) {
-                    if (nx != 0xD0 + (r & 7) || r >= d.nseg - 1) flags |= ST_RST;
+                    if (nx != 0xD0 + (r & 7) || r >= nseg - 1) flags |= ST_RST;
                     else seg[r] = (int)w;
                     ++r;
                 }
@@ -392,18 +611,40 @@ __global__ __launch_bounds__(NT) void unstuff_kernel(const JDesc* __restrict__ d
         if (e < base + ROUND) break;
     }
     if (t == 0) {
-        if (nrst != d.nseg - 1) flags |= ST_RST;
-        seg[d.nseg - 1] = (int)emitted;
+        if (nrst != nseg - 1) flags |= ST_RST;
+        seg[nseg - 1] = (int)emitted;
         for (int q = 0; q < 16; ++q) un[emitted + q] = 0;      // the reader's tail: inside unst_cap (emitted <= entropy bytes)
     }
     __syncthreads();
     sh[t] = flags;
     __syncthreads();
-    if (t == 0) {
-        int f = 0;
+    int f = 0;
+    if (t == 0)
         for (int q = 0; q < NT; ++q) f |= sh[q];
-        status[blockIdx.x] = f;
+    return f;
+}
+
+__global__ __launch_bounds__(NT) void unstuff_kernel(const JDesc* __restrict__ descs, const uint8_t* __restrict__ src, uint8_t* __restrict__ ws,
+                                                     int* __restrict__ status) {
+    __shared__ int sh[NT];
+    __shared__ long s_end;
+    const JDesc& d = descs[blockIdx.x];
+    if (d.k == 0) {                                 // a progressive file: its scans are punstuff_kernel's, which adds to this status
+        if (threadIdx.x == 0) status[blockIdx.x] = 0;
+        return;
     }
+    const int f = unstuff_range(src, d.src_ent, d.src_end, ws + d.ws_unst, reinterpret_cast<int*>(ws + d.ws_seg), d.nseg, sh, &s_end);
+    if (threadIdx.x == 0) status[blockIdx.x] = f;
+}
+
+// grid: the scans of the batch's progressive files
+__global__ __launch_bounds__(NT) void punstuff_kernel(const PScan* __restrict__ scans, const uint8_t* __restrict__ src, uint8_t* __restrict__ ws,
+                                                      int* __restrict__ status) {
+    __shared__ int sh[NT];
+    __shared__ long s_end;
+    const PScan& sc = scans[blockIdx.x];
+    const int f = unstuff_range(src, sc.src_lo, sc.src_hi, ws + sc.ws_unst, reinterpret_cast<int*>(ws + sc.ws_seg), sc.nseg, sh, &s_end);
+    if (threadIdx.x == 0 && f) atomicOr(status + sc.img, f);
 }
 
 struct Lut {
@@ -546,6 +787,7 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
     __shared__ int s_any, s_flags;
     const JDesc& d = descs[blockIdx.x];
     const int t = threadIdx.x;
+    if (d.k == 0) return;                        // a progressive file: pscan_kernel's
     if (status[blockIdx.x] != 0) return;         // restart markers out of order: the segment table is not valid (uniform: before any barrier)
     const uint8_t* un = ws + d.ws_unst;
     const int* seg = reinterpret_cast<const int*>(ws + d.ws_seg);
@@ -716,6 +958,259 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
     if (t == 0 && s_flags) atomicOr(status + blockIdx.x, s_flags);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------ progressive scans
+// jdphuff.c.  Returns the code's length (0: not a code) and its symbol.
+__device__ inline int huff_symbol(const Lut& L, uint32_t w32, int& sym) {
+    const uint32_t w16 = w32 >> 16;
+    const int e = L.lut[w16 >> (16 - LUT_BITS)];
+    if (e) {
+        sym = e & 255;
+        return e >> 8;
+    }
+    for (int l = LUT_BITS + 1; l <= 16; ++l) {
+        const int code = (int)(w16 >> (16 - l));
+        if (code <= L.maxcode[l]) {
+            sym = L.vals[(code + L.valoff[l]) & 255];
+            return l;
+        }
+    }
+    return 0;
+}
+
+// The decoding tables of one Huffman table: the code ranges per length, then the short-code lookup entry by entry (huff_kernel builds the same).
+__device__ inline void lut_codes(const HuffSpec& hs, Lut& L) {
+    int code = 0, k = 0;
+    L.maxcode[0] = -1;
+    L.valoff[0] = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int n = hs.bits[l - 1];
+        L.valoff[l] = k - code;
+        code += n;
+        k += n;
+        L.maxcode[l] = n ? code - 1 : -1;
+        code <<= 1;
+    }
+    for (int q = 0; q < 256; ++q) L.vals[q] = hs.vals[q];
+}
+
+__device__ inline uint16_t lut_entry(const Lut& L, int e) {
+    for (int l = 1; l <= LUT_BITS; ++l) {
+        const int code = e >> (LUT_BITS - l);
+        if (code <= L.maxcode[l]) return (uint16_t)((l << 8) | L.vals[(code + L.valoff[l]) & 255]);
+    }
+    return 0;
+}
+
+// One restart interval (scan MCUs [m0, m1), bits from p) of one scan, by one lane.  Returns the status flags.  Whatever the bits are, block indices
+// stay below the scan's host-validated MCU count and coefficient indices inside [Ss, Se]; anything libjpeg would only warn about is a flag (the host
+// then decodes the file).  blk: 64 int16 of LDS of this lane (AC refinement reads the block's earlier coefficients through it).
+__device__ int pscan_segment(const JDesc& d, const PScan& sc, const Lut* __restrict__ luts, const int* __restrict__ zz, Reader& rd, int p, long m0,
+                             long m1, uint8_t* __restrict__ ws, int16_t* blk) {
+    const int al = sc.al, ss = sc.ss, se = sc.se;
+    if (ss == 0) {
+        // DC: first scan (Huffman-coded difference, predictor per component, stored << Al) or refinement (one raw bit per block)
+        int pr0 = 0, pr1 = 0, pr2 = 0;
+        for (long m = m0; m < m1; ++m) {
+            for (int i = 0; i < sc.ns; ++i) {
+                const int c = sc.comp[i];
+                int H = 1, V = 1;
+                long bx0, by0;
+                if (sc.ns == 1) {
+                    bx0 = m % sc.gw;
+                    by0 = m / sc.gw;
+                } else {
+                    const bool luma = d.nc == 3 && c == 0;
+                    H = luma ? d.hs : 1;
+                    V = luma ? d.vs : 1;
+                    bx0 = (m % d.mcux) * H;
+                    by0 = (m / d.mcux) * V;
+                }
+                int16_t* base = reinterpret_cast<int16_t*>(ws + d.ws_coef[c]);
+                for (int y = 0; y < V; ++y)
+                    for (int x = 0; x < H; ++x) {
+                        int16_t* bp = base + ((by0 + y) * d.bw[c] + bx0 + x) * 64;
+                        if (p > rd.E) return ST_EOD;
+                        const uint32_t w32 = rd.peek32(p);
+                        if (sc.ah == 0) {
+                            int sym = 0;
+                            const int len = huff_symbol(luts[i], w32, sym);
+                            if (!len) return ST_CODE;
+                            const int s = sym & 15;
+                            const int v = s ? extend((int)((w32 << len) >> (32 - s)), s) : 0;
+                            p += len + s;
+                            int pr = i == 0 ? pr0 : (i == 1 ? pr1 : pr2);
+                            pr += v;
+                            if (i == 0) pr0 = pr;
+                            else if (i == 1) pr1 = pr;
+                            else pr2 = pr;
+                            bp[0] = (int16_t)(pr * (1 << al));
+                        } else {
+                            if (w32 >> 31) bp[0] = (int16_t)(bp[0] | (1 << al));
+                            p += 1;
+                        }
+                    }
+            }
+        }
+        return p > rd.E ? ST_EOD : 0;
+    }
+    const int c = sc.comp[0];
+    int16_t* base = reinterpret_cast<int16_t*>(ws + d.ws_coef[c]);
+    const long bw = d.bw[c];
+    int eobrun = 0;
+    if (sc.ah == 0) {
+        // AC first: run / size symbols, EOB runs across blocks, ZRL; values stored << Al
+        for (long m = m0; m < m1; ++m) {
+            if (eobrun > 0) {
+                --eobrun;
+                continue;
+            }
+            int16_t* bp = base + ((m / sc.gw) * bw + m % sc.gw) * 64;
+            for (int k = ss; k <= se; ++k) {
+                if (p > rd.E) return ST_EOD;
+                const uint32_t w32 = rd.peek32(p);
+                int sym = 0;
+                const int len = huff_symbol(luts[0], w32, sym);
+                if (!len) return ST_CODE;
+                const int r = sym >> 4, s = sym & 15;
+                if (s) {
+                    k += r;
+                    if (k > se) return ST_INDEX;
+                    const int v = extend((int)((w32 << len) >> (32 - s)), s);
+                    p += len + s;
+                    bp[zz[k]] = (int16_t)(v * (1 << al));
+                } else if (r == 15) {
+                    k += 15;
+                    p += len;
+                } else {
+                    eobrun = 1 << r;
+                    if (r) eobrun += (int)((w32 << len) >> (32 - r));
+                    p += len + r;
+                    --eobrun;
+                    break;
+                }
+            }
+        }
+        return p > rd.E ? ST_EOD : 0;
+    }
+    // AC refinement (decode_mcu_AC_refine): a correction bit for every already-nonzero coefficient the run passes over, new coefficients +-(1 << Al),
+    // EOB runs still refine the rest of the band.  The block's 64 coefficients are read once (registers -> this lane's LDS copy for the few that
+    // are corrected) and their nonzero-ness kept as a bit mask in zigzag order, so that a zero costs no memory access.  Only coefficients of the
+    // band are written back, one by one: scans of the same round own other coefficients of the same blocks.
+    const int p1 = 1 << al, m1v = -p1;
+    for (long m = m0; m < m1; ++m) {
+        int16_t* gp = base + ((m / sc.gw) * bw + m % sc.gw) * 64;        // 128-byte aligned, as blk is 16-byte aligned
+        uint64_t nz = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {          // 8 bytes at a time; memcpy, so that the int16 reads below see these stores
+            uint64_t v;
+            __builtin_memcpy(&v, gp + 4 * q, 8);
+            __builtin_memcpy(blk + 4 * q, &v, 8);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) nz |= (uint64_t)(((v >> (16 * u)) & 0xffff) != 0) << kUnzigzag[4 * q + u];
+        }
+        auto correct = [&](int k) {             // the correction bit of the nonzero coefficient at zigzag index k
+            const uint32_t bit = rd.peek32(p) >> 31;
+            ++p;
+            if (bit) {
+                const int at = zz[k];
+                const int cur = blk[at];
+                if ((cur & p1) == 0) gp[at] = (int16_t)(cur >= 0 ? cur + p1 : cur + m1v);
+            }
+        };
+        int k = ss;
+        if (eobrun == 0) {
+            for (; k <= se; ++k) {
+                if (p > rd.E) return ST_EOD;
+                const uint32_t w32 = rd.peek32(p);
+                int sym = 0;
+                const int len = huff_symbol(luts[0], w32, sym);
+                if (!len) return ST_CODE;
+                int r = sym >> 4;
+                const int s = sym & 15;
+                int nv = 0;
+                if (s) {
+                    if (s != 1) return ST_CODE;
+                    nv = ((w32 << len) >> 31) ? p1 : m1v;
+                    p += len + 1;
+                } else if (r != 15) {
+                    eobrun = 1 << r;
+                    if (r) eobrun += (int)((w32 << len) >> (32 - r));
+                    p += len + r;
+                    break;
+                } else {
+                    p += len;
+                }
+                do {
+                    if ((nz >> k) & 1) correct(k);
+                    else if (--r < 0) break;
+                    ++k;
+                } while (k <= se);
+                if (s) {
+                    if (k > se) return ST_INDEX;
+                    gp[zz[k]] = (int16_t)nv;
+                }
+            }
+        }
+        if (eobrun > 0) {
+            if (k <= se) {
+                uint64_t rest = (nz >> k) << k;                         // the nonzero coefficients of [k, se]
+                if (se < 63) rest &= (1ull << (se + 1)) - 1;
+                while (rest) {
+                    correct(__builtin_ctzll(rest));
+                    rest &= rest - 1;
+                }
+            }
+            --eobrun;
+        }
+        if (p > rd.E) return ST_EOD;
+    }
+    return 0;
+}
+
+constexpr int PT = 64;      // threads of pscan_kernel's workgroups: one wave per scan, one lane per restart interval at a time
+
+// grid: the scans of one launch round (scans that touch the same coefficients of a component run in different rounds, in file order).  A scan without
+// restart markers is one lane's; a lane's loops run over the scan's MCUs and bands, and the reader returns zeros past its interval's end.
+__global__ __launch_bounds__(PT) void pscan_kernel(const JDesc* __restrict__ descs, const PScan* __restrict__ scans, uint8_t* __restrict__ ws,
+                                                   int* __restrict__ status) {
+    __shared__ Lut luts[3];
+    __shared__ int s_zz[64];
+    // every lane's block copy starts in the same LDS bank: lanes of a file with restart markers conflict on the copy (a pitch of 68 would spread them)
+    __shared__ __align__(16) int16_t s_blk[PT][64];
+    __shared__ int s_skip;
+    const PScan& sc = scans[blockIdx.x];
+    const JDesc& d = descs[sc.img];
+    const int t = threadIdx.x;
+    if (t == 0) s_skip = status[sc.img];        // a file that has already failed is the host's: one read, so that the whole wave agrees
+    const int ntab = sc.ss == 0 ? (sc.ah == 0 ? sc.ns : 0) : 1;
+    if (t < ntab) {
+        lut_codes(sc.tab[t], luts[t]);
+    }
+    s_zz[t] = kZigzag[t];
+    __syncthreads();
+    if (s_skip != 0) return;
+    for (int q = t; q < ntab * (1 << LUT_BITS); q += PT) {
+        Lut& L = luts[q >> LUT_BITS];
+        const int e = q & ((1 << LUT_BITS) - 1);
+        L.lut[e] = lut_entry(L, e);
+    }
+    __syncthreads();
+    const uint8_t* un = ws + sc.ws_unst;
+    const int* seg = reinterpret_cast<const int*>(ws + sc.ws_seg);
+    int flags = 0;
+    for (int s = t; s < sc.nseg; s += PT) {
+        const int s0 = s ? seg[s - 1] : 0, s1 = seg[s];
+        if (s0 > s1) {
+            flags |= ST_RST;
+            continue;
+        }
+        Reader rd{un, sc.unst_cap, s1 * 8, -1000, 0};
+        const long m0 = (long)s * sc.ri, m1 = m0 + sc.ri < sc.nmcu ? m0 + sc.ri : sc.nmcu;
+        flags |= pscan_segment(d, sc, luts, s_zz, rd, s0 * 8, m0, m1, ws, s_blk[t]);
+    }
+    if (flags) atomicOr(status + sc.img, flags);
+}
+
 // jidctint.c constants (CONST_BITS 13)
 #define F0298 2446
 #define F0390 3196
@@ -854,10 +1349,10 @@ __global__ __launch_bounds__(256) void color_kernel(const JDesc* __restrict__ de
 
 }  // namespace
 
-extern "C" int lpi_jpeg_info(const void* data, long nbytes, long* info) {
-    if (!data || !info || nbytes < 0) return LPI_EINVAL;
+extern "C" int lpi_jpeg_info_x(int flags, const void* data, long nbytes, long* info) {
+    if (!data || !info || nbytes < 0 || (flags & ~LPI_JPEG_PROGRESSIVE)) return LPI_EINVAL;
     Header hd;
-    if (parse_headers(static_cast<const uint8_t*>(data), nbytes, hd) != 0) return LPI_EINVAL;
+    if (parse_headers(static_cast<const uint8_t*>(data), nbytes, hd, flags) != 0) return LPI_EINVAL;
     info[0] = hd.gpu ? 1 : 0;
     info[1] = hd.w;
     info[2] = hd.h;
@@ -866,20 +1361,36 @@ extern "C" int lpi_jpeg_info(const void* data, long nbytes, long* info) {
     info[5] = hd.nc == 3 ? hd.cv[0] : 1;
     info[6] = hd.ri;
     info[7] = hd.ent;
+    info[8] = hd.prog ? 1 : 0;
+    info[9] = hd.prog ? (long)hd.scans.size() : (hd.ent ? 1 : 0);
     return 0;
 }
 
-extern "C" int lpi_jpeg_decode_workspace(int B, const void* host, const long* offsets, long* bytes) {
-    if (!bytes) return LPI_EINVAL;
-    return plan(B, static_cast<const uint8_t*>(host), offsets, nullptr, bytes, nullptr, nullptr);
+extern "C" int lpi_jpeg_info(const void* data, long nbytes, long* info) {
+    long x[LPI_JPEG_INFO_X];
+    if (!info) return LPI_EINVAL;
+    const int rc = lpi_jpeg_info_x(0, data, nbytes, x);
+    if (rc == 0) std::memcpy(info, x, LPI_JPEG_INFO * sizeof(long));
+    return rc;
 }
 
-extern "C" int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out,
-                                  long out_bytes, int* status, void* ws, long ws_bytes, void* stream) {
+extern "C" int lpi_jpeg_decode_workspace_x(int flags, int B, const void* host, const long* offsets, long* bytes) {
+    if (!bytes) return LPI_EINVAL;
+    return plan(flags, B, static_cast<const uint8_t*>(host), offsets, nullptr, bytes, nullptr, nullptr);
+}
+
+extern "C" int lpi_jpeg_decode_workspace(int B, const void* host, const long* offsets, long* bytes) {
+    return lpi_jpeg_decode_workspace_x(0, B, host, offsets, bytes);
+}
+
+extern "C" int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off,
+                                    void* out, long out_bytes, int* status, void* ws, long ws_bytes, void* stream) {
     if (!src || !out || !status || !ws || !out_off || src_bytes < 1 || out_bytes < 1) return LPI_EINVAL;
     std::vector<JDesc> descs;
-    long need = 0, z0 = 0, z1 = 0;
-    const int rc = plan(B, static_cast<const uint8_t*>(host), offsets, &descs, &need, &z0, &z1);
+    std::vector<PScan> scans;
+    std::vector<int> rounds;
+    long need = 0, z0 = 0, z1 = 0, ws_scans = 0;
+    const int rc = plan(flags, B, static_cast<const uint8_t*>(host), offsets, &descs, &need, &z0, &z1, &scans, &rounds, &ws_scans);
     if (rc != 0) return rc;
     if (ws_bytes < need || offsets[B] > src_bytes) return LPI_EINVAL;
     int maxw = 1, maxh = 1;
@@ -894,10 +1405,14 @@ extern "C" int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, 
         for (int c = 0; c < j.nc; ++c) nb += (long)j.bw[c] * j.bh[c];
         maxblk = nb > maxblk ? nb : maxblk;
     }
-    if (maxh > 65535 || (maxblk + 63) / 64 > 0x7fffffffL) return LPI_EINVAL;
+    if (maxh > 65535 || (maxblk + 63) / 64 > 0x7fffffffL || scans.size() > 0x7fffffffUL) return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemcpyAsync(ws, descs.data(), (size_t)B * sizeof(JDesc), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return (int)e;
+    if (!scans.empty()) {
+        e = hipMemcpyAsync(static_cast<char*>(ws) + ws_scans, scans.data(), scans.size() * sizeof(PScan), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return (int)e;
+    }
     e = hipMemsetAsync(static_cast<char*>(ws) + z0, 0, (size_t)(z1 - z0), s);
     if (e != hipSuccess) return (int)e;
     const JDesc* dd = static_cast<const JDesc*>(ws);
@@ -906,9 +1421,27 @@ extern "C" int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, 
     LPI_CHECK_LAST();
     LPI_LAUNCH(huff_kernel, dim3(B), dim3(HT), 0, s, dd, w8, status);
     LPI_CHECK_LAST();
+    if (!scans.empty()) {
+        // progressive files: their scans' bytes unstuffed, then one launch per round of scans that may run side by side
+        const PScan* ps = reinterpret_cast<const PScan*>(w8 + ws_scans);
+        LPI_LAUNCH(punstuff_kernel, dim3((unsigned)scans.size()), dim3(NT), 0, s, ps, (const uint8_t*)src, w8, status);
+        LPI_CHECK_LAST();
+        size_t first = 0;
+        for (int r = 1; r <= LPI_JPEG_MAX_SCANS; ++r) {
+            if (!rounds[r]) continue;
+            LPI_LAUNCH(pscan_kernel, dim3((unsigned)rounds[r]), dim3(PT), 0, s, dd, ps + first, w8, status);
+            LPI_CHECK_LAST();
+            first += (size_t)rounds[r];
+        }
+    }
     LPI_LAUNCH(idct_kernel, dim3((unsigned)((maxblk + 63) / 64), B), dim3(64), 0, s, dd, w8);
     LPI_CHECK_LAST();
     LPI_LAUNCH(color_kernel, dim3((maxw + 255) / 256, maxh, B), dim3(256), 0, s, dd, (const uint8_t*)w8, (uint8_t*)out);
     LPI_CHECK_LAST();
     return 0;
+}
+
+extern "C" int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out,
+                                  long out_bytes, int* status, void* ws, long ws_bytes, void* stream) {
+    return lpi_jpeg_decode_u8_x(0, B, host, offsets, src, src_bytes, out_off, out, out_bytes, status, ws, ws_bytes, stream);
 }

@@ -81,9 +81,16 @@ def _dist_rank():
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
+def _check_jpeg_progressive(args):
+    """jpeg_progressive widens the envelope of pixel_format = 'jpeg' (LPI_JPEG_PROGRESSIVE): with any other pixel format it is a ValueError."""
+    if args.get('jpeg_progressive') and args.get('pixel_format', 'f32') != 'jpeg':
+        raise ValueError(f"jpeg_progressive widens the envelope of pixel_format='jpeg': it cannot go with pixel_format={args.get('pixel_format', 'f32')!r}")
+
+
 class SPrompts(BaseLearner):
     def __init__(self, args):
         super().__init__(args)
+        _check_jpeg_progressive(args)           # a conflicting key fails here, beside the preprocessing keys, not at the first task
         if args["net_type"] == "slip":
             self._network = SliNet(args)
         else:
@@ -111,6 +118,7 @@ class SPrompts(BaseLearner):
         logging.info('Exemplar size: {}'.format(self.exemplar_size))
 
     def _datasets(self, i):
+        _check_jpeg_progressive(self.args)
         impl = self.args.get("dataset_impl")
         if impl is None:
             impl = "coco" if os.path.isdir(str(self.args.get("image_root", ""))) else "synthetic"
@@ -129,11 +137,17 @@ class SPrompts(BaseLearner):
             if pre is not None:
                 kw = dict(size=pre['size'], interpolation=pre['interpolation'], normalize=pre['normalize'])
                 ekw = dict(resize=pre['eval_resize'])
+            # jpeg_progressive = true: pixel_format = 'jpeg' also hands progressive files with a complete scan script to the GPU decoder
+            # (LPI_JPEG_PROGRESSIVE); the datasets refuse the key with any other pixel format
+            if 'jpeg_progressive' in self.args:
+                kw['jpeg_progressive'] = bool(self.args['jpeg_progressive'])
             return (Coco(image_root=self.args['image_root'], ann_file=self.args['annotation_train_root'], tasks=[i], pixel_format=pf, **kw),
                     CocoEval(image_root=self.args['image_root'], ann_file=self.args['annotation_val_root'], tasks=np.arange(0, i + 1),
                              eval_transform=self.args.get('eval_transform', 'center'), pixel_format=pf, **kw, **ekw))
         if impl != "synthetic":
             raise ValueError(f"unknown dataset_impl {impl!r} (coco | synthetic)")
+        if self.args.get('jpeg_progressive'):
+            raise ValueError("jpeg_progressive widens the envelope of pixel_format='jpeg', which needs image files: the synthetic datasets have none")
         res = self._network.clip_cfg.image_resolution
         n_train = int(self.args.get("synthetic_train_size", 4 * self.batch_size))
         n_eval = int(self.args.get("synthetic_eval_images_per_task", 16))

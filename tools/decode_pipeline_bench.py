@@ -13,9 +13,15 @@ no restart markers):
 
 The decode's phases (per-kernel times): rocprofv3 --kernel-trace --stats -- python3 tools/decode_pipeline_bench.py --decode-only
 
+--progressive: the same seeded pixels saved with progressive=True in a second folder.  Reports the host ms per item of 'jpeg' with jpeg_progressive
+(the parser walks the whole file) beside the baseline folder's, lpi_jpeg_decode_u8_x on one 256-file progressive batch beside the baseline batch's
+time from the same process, and the plugin loop's pairs/s of 'jpeg' with the key on, with the key off (Pillow decodes every file in the loader) and of
+'u8'.  With --decode-only: the two decode timings only.
+
 --filter bilinear | bicubic | box: the resampling filter of every dataset here (host transforms and GPU kernel alike; default bilinear).
 
-usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--filter bilinear] [--decode-only] [--out FILE.json]
+usage: python3 tools/decode_pipeline_bench.py [--images 512] [--steps 16] [--workers 0,8,14] [--filter bilinear] [--decode-only] [--progressive]
+       [--out FILE.json]
 Prints one JSON object (and writes it to --out)."""
 import argparse
 import json
@@ -35,15 +41,16 @@ from lpi_amd import imageops  # noqa: E402
 from lpi_amd.retrieval.utils import data as D  # noqa: E402
 
 
-def write_folder(root, n_files, n_train, n_val):
+def write_folder(root, n_files, n_train, n_val, progressive=False):
     from PIL import Image
+    kw = {"progressive": True} if progressive else {}
     rng = np.random.default_rng(0)
     for i in range(n_files):
         # smooth-ish content (a JPEG of uniform noise decodes slower than a photo): low-resolution noise upsampled, plus a little grain
         base = rng.integers(0, 256, (30, 40, 3), dtype=np.uint8)
         im = Image.fromarray(base).resize((640, 480), Image.BILINEAR)
         a = np.asarray(im).astype(np.int16) + rng.integers(-8, 9, (480, 640, 3))
-        Image.fromarray(np.clip(a, 0, 255).astype(np.uint8)).save(os.path.join(root, f"im{i}.jpg"), quality=90)
+        Image.fromarray(np.clip(a, 0, 255).astype(np.uint8)).save(os.path.join(root, f"im{i}.jpg"), quality=90, **kw)
     train = [{"image": f"im{i % n_files}.jpg", "caption": f"a photo of a thing number {i}", "category": 11, "image_id": f"coco_{i}"} for i in range(n_train)]
     val = [{"image": f"im{i % n_files}.jpg", "caption": [f"first caption {i}", f"second caption {i}"], "category": 11, "image_id": i} for i in range(n_val)]
     json.dump(train, open(os.path.join(root, "train.json"), "w"))
@@ -84,8 +91,9 @@ def kernel_us(ds, dev, reps=30, warm=5):
             "warmup": warm}
 
 
-def jpeg_decode(ds, root, dev, reps=30, warm=5):
-    """lpi_jpeg_decode_u8 on one 256-image batch of 'jpeg' items (bytes on the device, full-size output), and the folder's fallbacks."""
+def jpeg_decode(ds, root, dev, reps=30, warm=5, progressive=False):
+    """lpi_jpeg_decode_u8 (progressive: lpi_jpeg_decode_u8_x with LPI_JPEG_PROGRESSIVE) on one 256-image batch of 'jpeg' items (bytes on the device,
+    full-size output), and the folder's fallbacks."""
     torch.manual_seed(0)
     batch = D.collate_encoded([ds[i % len(ds)] for i in range(256)])[0]
     gpu = [i for i in range(len(batch)) if i not in batch.fallback]
@@ -95,36 +103,46 @@ def jpeg_decode(ds, root, dev, reps=30, warm=5):
     wh = batch.wh.numpy()[gpu]
     out_off = np.concatenate(([0], np.cumsum(wh[:, 0] * wh[:, 1] * 3)))
     src = torch.from_numpy(host.copy()).to(dev)
-    ws_bytes = imageops.jpeg_workspace_bytes(host, offs)
+    ws_bytes = imageops.jpeg_workspace_bytes(host, offs, progressive)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
     status = torch.empty(len(gpu), dtype=torch.int32, device=dev)
     s = torch.cuda.current_stream(dev)
-    times = []
+    times, host_call = [], []
     for r in range(warm + reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(s)
-        imageops.jpeg_launch(host, offs, src, out_off[:-1], out, status, ws, s)
+        t0 = time.perf_counter()
+        imageops.jpeg_launch(host, offs, src, out_off[:-1], out, status, ws, s, progressive)
+        t1 = time.perf_counter()
         e1.record(s)
         e1.synchronize()
         if r >= warm:
             times.append(1e3 * e0.elapsed_time(e1))
+            host_call.append(1e3 * (t1 - t0))
+    # the host's share: the parse of every file for the workspace size (once per batch), and the decode call itself until it returns (parse again,
+    # descriptor and scan tables built and copied from pageable memory, launches enqueued)
+    t0 = time.perf_counter()
+    for _ in range(10):
+        imageops.jpeg_workspace_bytes(host, offs, progressive)
+    ws_ms = 1e2 * (time.perf_counter() - t0)
     files = sorted(f for f in os.listdir(root) if f.endswith(".jpg"))
-    outside = sum(1 for f in files if not (imageops.jpeg_info(open(os.path.join(root, f), "rb").read()) or (False,))[0])
+    outside = sum(1 for f in files if not (imageops.jpeg_info(open(os.path.join(root, f), "rb").read(), progressive) or (False,))[0])
     return {"median_us": round(float(np.median(times)), 1), "p10_p90_us": [round(float(np.percentile(times, q)), 1) for q in (10, 90)],
-            "files": len(gpu), "file_MB": round(hi / 1e6 - lo / 1e6, 2), "mean_file_KB": round((hi - lo) / len(gpu) / 1e3, 1),
+            "host_call_ms_median": round(float(np.median(host_call)), 3), "host_workspace_call_ms": round(ws_ms, 3), "files": len(gpu), "file_MB": round(hi / 1e6 - lo / 1e6, 2), "mean_file_KB": round((hi - lo) / len(gpu) / 1e3, 1),
             "output_MB": round(float(out_off[-1]) / 1e6, 1), "workspace_MB": round(ws_bytes / 1e6, 1), "gpu_status_not_ok": int((status != 0).sum()),
             "batch_fallbacks": len(batch.fallback), "folder_files": len(files), "folder_files_outside_envelope": outside, "reps": reps, "warmup": warm}
 
 
-def loop_pairs_per_s(root, pf, workers, steps, warm, dev, filter="bilinear"):
+def loop_pairs_per_s(root, pf, workers, steps, warm, dev, filter="bilinear", jpeg_progressive=False):
     from lpi_amd.retrieval.methods.sprompt import SPrompts
     args = json.load(open(os.path.join(REPO, "lpi_amd", "retrieval", "configs", "lpi", "coco_lpi.json")))
     args.update(device=[dev], compute_dtype="bf16", honor_prompt_depth=True, prompt_depth=3, batch_size=256, epochs=1, num_workers=workers,
                 pixel_format=pf)
     m = SPrompts(args)
     m._network.update_fc(0)
-    ds = D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf, interpolation=filter)
+    ds = D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format=pf, interpolation=filter,
+                jpeg_progressive=jpeg_progressive)
     collate = D.collate_decoded if pf == "decoded" else (D.collate_encoded if pf == "jpeg" else (D.collate_keep_images if workers == 0 else None))
     loader = DataLoader(ds, batch_size=256, shuffle=False, num_workers=workers, collate_fn=collate, persistent_workers=False)
     opt, _ = m._setup_training()
@@ -145,6 +163,45 @@ def loop_pairs_per_s(root, pf, workers, steps, warm, dev, filter="bilinear"):
             "prefetch_queue_batches": 2 * workers if workers else 0}
 
 
+def progressive_sections(a, rec, dev):
+    """--progressive: a baseline and a progressive folder of the same seeded pixels."""
+    workers = [int(x) for x in a.workers.split(",")]
+    warm = {w: max(a.warmup, 2 * w + 2) for w in workers}
+    rec["source"] = "640 x 480 q90 JPEG, progressive=True (Pillow's 10-scan script) beside the baseline files of the same pixels"
+    with tempfile.TemporaryDirectory() as base, tempfile.TemporaryDirectory() as prog:
+        n_train = 256 * ((0 if a.decode_only else a.steps + max(warm.values())) + 1)
+        write_folder(base, a.images, 256, 256)
+        write_folder(prog, a.images, n_train, 256, progressive=True)
+
+        def sets(root, **kw):
+            return (D.Coco(image_root=root, ann_file=os.path.join(root, "train.json"), tasks=[0], pixel_format="jpeg", interpolation=a.filter, **kw),
+                    D.CocoEval(image_root=root, ann_file=os.path.join(root, "val.json"), tasks=[0], pixel_format="jpeg", interpolation=a.filter, **kw))
+        b_tr, b_ev = sets(base)
+        on_tr, on_ev = sets(prog, jpeg_progressive=True)
+        off_tr, off_ev = sets(prog)
+        rec["jpeg_decode_256"] = {"baseline_files": jpeg_decode(b_tr, base, dev), "progressive_files": jpeg_decode(on_tr, prog, dev, progressive=True)}
+        print(json.dumps({"jpeg_decode_256": rec["jpeg_decode_256"]}), flush=True)
+        if not a.decode_only:
+            rec["host_ms_per_item"] = {"train_jpeg_baseline_files": round(host_ms(b_tr, a.host_items), 3),
+                                       "eval_jpeg_baseline_files": round(host_ms(b_ev, a.host_items), 3),
+                                       "train_jpeg_progressive_key_on": round(host_ms(on_tr, a.host_items), 3),
+                                       "eval_jpeg_progressive_key_on": round(host_ms(on_ev, a.host_items), 3),
+                                       "train_jpeg_progressive_key_off": round(host_ms(off_tr, min(a.host_items, 50)), 3),
+                                       "eval_jpeg_progressive_key_off": round(host_ms(off_ev, min(a.host_items, 50)), 3)}
+            rec["loop_pairs_per_s"] = {}
+            for w in workers:
+                for name, pf, key in (("jpeg_key_on", "jpeg", True), ("jpeg_key_off", "jpeg", False), ("u8", "u8", False)):
+                    r = loop_pairs_per_s(prog, pf, w, a.steps, warm[w], dev, a.filter, jpeg_progressive=key)
+                    rec["loop_pairs_per_s"][f"{name}_workers{w}"] = r
+                    print(json.dumps({f"{name}_workers{w}": r}), flush=True)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=512)
@@ -154,6 +211,7 @@ def main():
     ap.add_argument("--host-items", type=int, default=200)
     ap.add_argument("--filter", default="bilinear", choices=list(imageops.FILTERS), help="Pillow resampling filter of the transforms and the kernel")
     ap.add_argument("--decode-only", action="store_true", help="write the folder and run section 3 only (for a rocprofv3 --kernel-trace run)")
+    ap.add_argument("--progressive", action="store_true", help="the progressive folder: jpeg_progressive on / off / 'u8' (see above)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from lpi_amd.synth_bpe import ensure_vocab
@@ -161,6 +219,9 @@ def main():
     dev = torch.device("cuda:0")
     rec = {"tool": "tools/decode_pipeline_bench.py", "source": "640 x 480 q90 JPEG", "batch": 256, "host_threads": torch.get_num_threads(),
            "filter": a.filter}
+    if a.progressive:
+        progressive_sections(a, rec, dev)
+        return
     with tempfile.TemporaryDirectory() as root:
         workers = [int(x) for x in a.workers.split(",")]
         warm = {w: max(a.warmup, 2 * w + 2) for w in workers}
