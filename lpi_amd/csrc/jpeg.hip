@@ -2,8 +2,10 @@
 // default settings) gives for np.asarray(Image.open(f).convert("RGB")): baseline files, and with LPI_JPEG_PROGRESSIVE progressive files whose scan
 // script is complete.  tests/jpeg_restate.py and tests/jpeg_progressive.py restate every step in numpy / plain Python.
 //
-// The host parses the headers (parse_headers: the one place that decides the envelope), builds one JDesc per image and copies the table into the
-// workspace; four launches then do the rest for baseline files:
+// The host parses the headers (parse_headers: the one place that decides the envelope; frame_in_envelope is the frame's share of it, the same for
+// a baseline file and a progressive one) and lays the workspace out in one walk over the files (plan: one JDesc per image, its geometry from Geom,
+// the entropy-coded bytes of every scan an EntRange that place_range fills), then copies the descriptors into the workspace; four launches do the rest
+// for baseline files:
 //   unstuff_kernel   one workgroup per image: the entropy-coded bytes without the 0xFF00 stuffing, split at the RSTn markers, up to the first other
 //                    marker (rounds of 4096 bytes, a block-wide scan per round).  Out: the unstuffed bytes and the end of every restart interval.
 //   huff_kernel      one workgroup per image: Huffman decoding.  Every restart interval (segment) is cut into k chunks.  A chunk's decoder state at
@@ -19,13 +21,14 @@
 //
 // A progressive file (JDesc.k = 0: unstuff_kernel only clears its status, huff_kernel passes it over) has one PScan per scan, with the Huffman tables
 // and the restart interval in force at its SOS; between huff_kernel and idct_kernel its coefficients are built up scan by scan (jdphuff.c):
-//   punstuff_kernel  one workgroup per scan: unstuff_kernel's work on the scan's own bytes.
+//   punstuff_kernel  one workgroup per scan: unstuff_kernel's work (unstuff_range) on the scan's own EntRange.
 //   pscan_kernel     one launch per ROUND of scans; one wave per scan.  The host puts a scan into round 1 + the latest round of an earlier scan that
 //                    touched one of its (component, coefficient) pairs, so scans over the same coefficients run in file order and the others side by
 //                    side (Pillow's 10 scans: 5 + 4 + 1).  A lane decodes one restart interval from its start: DC first / DC refinement / AC first
 //                    (EOB runs) / AC refinement (correction bits, which depend on the coefficients of the earlier scans); a scan without restart
 //                    markers is one lane's.  A one-component scan walks the component's own block grid, not the MCU-padded one.  A scan writes only
 //                    the coefficients of its own band, one int16 at a time: the scans of a round share blocks.
+// huff_kernel and pscan_kernel build their decoding tables with lut_codes / lut_entry and read codes with huff_symbol.
 //
 // Bounds: every loop runs over counts the host validated (rounds over the entropy bytes, symbols at most one per bit of a chunk, sync rounds at
 // most k + 1; a progressive scan's MCUs, the coefficients of its band, at most LPI_JPEG_MAX_SCANS rounds); block indices come from those counts and
@@ -52,16 +55,22 @@ struct HuffSpec {
     uint8_t vals[256];
 };
 
-// One image (device copy in the workspace's head).  Offsets: src_* into the caller's device bytes, out into the caller's output, ws_* into the
-// workspace.
-struct JDesc {
-    long src_ent, src_end;          // entropy-coded bytes [src_ent, src_end) of the file
-    long out;                       // first byte of the h x w x 3 output
-    long ws_unst, unst_cap;         // unstuffed bytes (capacity: src_end - src_ent + 16)
+// The entropy-coded bytes of one scan (a baseline file's only one, or one of a progressive file's) and where they go.  Offsets: src_* into the
+// caller's device bytes, ws_* into the workspace.
+struct EntRange {
+    long src_lo, src_hi;            // the scan's entropy-coded bytes
+    long ws_unst, unst_cap;         // unstuffed bytes (capacity: src_hi - src_lo + 16)
     long ws_seg;                    // int32 end (unstuffed byte) of every segment
+    int nseg, ri;                   // segments; restart interval in scan MCUs (a scan without restart markers: all of them)
+};
+
+// One image (device copy in the workspace's head).  out: offset into the caller's output, ws_*: into the workspace.
+struct JDesc {
+    EntRange ent;                   // a baseline file's scan
+    long out;                       // first byte of the h x w x 3 output
     long ws_coef[3];                // int16 [blocks][64] of each frame component
     long ws_plane[3];               // uint8 sample plane of each frame component
-    int w, h, nc, mcux, mcuy, ri, nseg, bpm;
+    int w, h, nc, mcux, mcuy, bpm;
     int bw[3], bh[3];               // block grid of each frame component
     int blk_comp[10];               // scan component of block b of an MCU
     int blk_dx[10], blk_dy[10];     // its position inside the MCU's share of that component
@@ -75,27 +84,28 @@ struct JDesc {
 
 // One scan of a progressive file (device copies behind the sample planes in the workspace, sorted by launch round).
 struct PScan {
-    long src_lo, src_hi;            // its entropy-coded bytes in the caller's device bytes
-    long ws_unst, unst_cap;         // unstuffed bytes (capacity: src_hi - src_lo + 16)
-    long ws_seg;                    // int32 end (unstuffed byte) of every segment
+    EntRange ent;
     long nmcu;                      // scan MCUs: the frame's MCUs (interleaved), or the blocks of the component's own grid
     int img;                        // its image's JDesc
-    int nseg, ri;                   // restart interval in scan MCUs
     int ns, comp[3];                // frame components
     int ss, se, ah, al;
     int gw;                         // one-component scan: blocks per row of the component's own grid
     HuffSpec tab[3];                // first DC scan: the DC table of each scan component; AC scan: tab[0]
 };
 
-__device__ __constant__ int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-// zigzag index of the coefficient at natural index n (compile-time indices only)
-constexpr int kUnzigzag[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
-                               10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
-const int kZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+// Natural index of the coefficient at zigzag index z: the one list, read by the host parser and (as a constant the compiler emits for the device
+// too) by the kernels.
+constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// its inverse: v[n] = zigzag index of the coefficient at natural index n (compile-time indices only)
+struct Unzigzag {
+    int v[64];
+    constexpr Unzigzag() : v() {
+        for (int z = 0; z < 64; ++z) v[kZigzag[z]] = z;
+    }
+};
+constexpr Unzigzag kUnzigzag;
 
 // ------------------------------------------------------------------------------------------------------------------------------ host parser
 // One scan of a progressive file: its entropy-coded bytes [ent, end) of the file, its header, the restart interval and the Huffman tables in force
@@ -137,18 +147,20 @@ bool huff_ok(const HuffSpec& t, int count, bool dc) {
     return true;
 }
 
+// The frame's share of the envelope, whatever its scans are: 8-bit, a height in the header, a size the decoder's workspace and its int bit positions
+// take, and grayscale or the three components libjpeg takes for YCbCr with luma sampled 1x1, 2x1 or 2x2 over 1x1 chroma.
+bool frame_in_envelope(const Header& hd) {
+    if (hd.prec != 8 || hd.h <= 0 || (long)hd.w * hd.h > LPI_JPEG_MAX_PIXELS) return false;
+    if (hd.nc != 3) return hd.nc == 1;
+    if (!hd.jfif && (hd.adobe || (hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'))) return false;
+    const bool luma = (hd.ch[0] == 1 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 2);
+    return luma && hd.ch[1] == 1 && hd.cv[1] == 1 && hd.ch[2] == 1 && hd.cv[2] == 1;
+}
+
 // One SOS of a SOF2 file against the progressive envelope; appends it to hd.scans.  false: the file is the host's.
 bool progressive_scan(Header& hd, const uint8_t* s, long ent, long end, int (*al_cur)[64]) {
     if (hd.scans.empty()) {
-        bool ok = hd.prec == 8 && hd.h > 0 && (long)hd.w * hd.h <= LPI_JPEG_MAX_PIXELS;
-        if (hd.nc == 3) {
-            ok = ok && (hd.jfif || !hd.adobe) && (hd.jfif || !(hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'));
-            const bool luma = (hd.ch[0] == 1 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 2);
-            ok = ok && luma && hd.ch[1] == 1 && hd.cv[1] == 1 && hd.ch[2] == 1 && hd.cv[2] == 1;
-        } else {
-            ok = ok && hd.nc == 1;
-        }
-        if (!ok) return false;
+        if (!frame_in_envelope(hd)) return false;
         hd.ent = ent;
     }
     if ((int)hd.scans.size() >= LPI_JPEG_MAX_SCANS || hd.ns > 3) return false;
@@ -223,7 +235,7 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
         const uint8_t* s = d + p + 4;
         const long sl = L - 2;
         p += 2 + L;
-        if (m == 0xC0 || m == 0xC1) {
+        if (m == 0xC0 || m == 0xC1 || (m == 0xC2 && (flags & LPI_JPEG_PROGRESSIVE))) {
             if (hd.sof || sl < 6) return LPI_EINVAL;
             hd.prec = s[0];
             hd.h = rd16(s + 1);
@@ -238,21 +250,7 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
                 if (hd.ch[i] < 1 || hd.ch[i] > 4 || hd.cv[i] < 1 || hd.cv[i] > 4 || hd.ctq[i] > 3) return LPI_EINVAL;
             }
             hd.sof = true;
-        } else if (m == 0xC2 && (flags & LPI_JPEG_PROGRESSIVE)) {
-            if (hd.sof || sl < 6) return LPI_EINVAL;
-            hd.prec = s[0];
-            hd.h = rd16(s + 1);
-            hd.w = rd16(s + 3);
-            hd.nc = s[5];
-            if (hd.nc < 1 || hd.nc > 4 || sl != 6 + 3 * hd.nc || hd.w == 0) return LPI_EINVAL;
-            for (int i = 0; i < hd.nc; ++i) {
-                hd.cid[i] = s[6 + 3 * i];
-                hd.ch[i] = s[7 + 3 * i] >> 4;
-                hd.cv[i] = s[7 + 3 * i] & 15;
-                hd.ctq[i] = s[8 + 3 * i];
-                if (hd.ch[i] < 1 || hd.ch[i] > 4 || hd.cv[i] < 1 || hd.cv[i] > 4 || hd.ctq[i] > 3) return LPI_EINVAL;
-            }
-            hd.sof = hd.prog = true;
+            hd.prog = m == 0xC2;
         } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
             if (hd.prog) return LPI_EINVAL;                     // a second frame header
             if (sl >= 6) {                                      // progressive, lossless, arithmetic-coded, hierarchical: the host decodes
@@ -286,7 +284,7 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
                 const int pq = s[q] >> 4, tq = s[q] & 15;
                 const long size = 64L * (pq + 1);
                 if (pq > 1 || tq > 3 || q + 1 + size > sl) return LPI_EINVAL;
-                for (int i = 0; i < 64; ++i) hd.qt[tq][kZigzagHost[i]] = (uint16_t)(pq ? rd16(s + q + 1 + 2 * i) : s[q + 1 + i]);
+                for (int i = 0; i < 64; ++i) hd.qt[tq][kZigzag[i]] = (uint16_t)(pq ? rd16(s + q + 1 + 2 * i) : s[q + 1 + i]);
                 hd.qdef[tq] = true;
                 q += 1 + size;
             }
@@ -335,20 +333,11 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
             }
             hd.ent = p;
             const int ss = s[1 + 2 * hd.ns], se = s[2 + 2 * hd.ns], ahal = s[3 + 2 * hd.ns];
-            bool ok = hd.ns == hd.nc && ss == 0 && se == 63 && ahal == 0 && hd.prec == 8 && hd.h > 0;
+            bool ok = frame_in_envelope(hd) && hd.ns == hd.nc && ss == 0 && se == 63 && ahal == 0;
             // libjpeg-turbo's get_sos looks a scan component up among the frame components whose slot in the SCAN's list is still empty: a
             // full scan in any order but the frame's ends in JERR_BAD_COMPONENT_ID, so such files are Pillow's (its exception)
             for (int i = 0; i < hd.ns; ++i) ok = ok && hd.sc[i] == i;
-            if (hd.nc == 3) {
-                ok = ok && (hd.jfif || !hd.adobe) && (hd.jfif || !(hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'));
-                const bool luma = (hd.ch[0] == 1 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 2);
-                ok = ok && luma && hd.ch[1] == 1 && hd.cv[1] == 1 && hd.ch[2] == 1 && hd.cv[2] == 1;
-            } else {
-                ok = ok && hd.nc == 1;
-            }
-            // sizes the decoder's workspace and its int bit positions take: larger files are the host's too
-            ok = ok && (long)hd.w * hd.h <= LPI_JPEG_MAX_PIXELS && n - hd.ent <= LPI_JPEG_MAX_SCAN_BYTES;
-            hd.gpu = ok;
+            hd.gpu = ok && n - hd.ent <= LPI_JPEG_MAX_SCAN_BYTES;          // as the frame's size: what the int bit positions take
             return 0;
         }
         // APPn, COM, DNL and anything else with a length: skipped
@@ -358,172 +347,149 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
 
 // ------------------------------------------------------------------------------------------------------------------------------ plan
 inline long align256(long v) { return (v + 255) / 256 * 256; }
-inline long desc_bytes(int B) { return align256((long)B * (long)sizeof(JDesc)); }
+
+// A frame's geometry: the MCU's size in blocks (1 x 1 for grayscale, whatever its sampling factors say), the MCU grid, every component's share.
+struct Geom {
+    int hm, vm, mcux, mcuy;
+    int H[3], V[3];
+    explicit Geom(const Header& hd) {
+        for (int c = 0; c < 3; ++c) {
+            H[c] = hd.nc == 1 ? 1 : hd.ch[c];
+            V[c] = hd.nc == 1 ? 1 : hd.cv[c];
+        }
+        hm = H[0];
+        vm = V[0];
+        mcux = (hd.w + 8 * hm - 1) / (8 * hm);
+        mcuy = (hd.h + 8 * vm - 1) / (8 * vm);
+    }
+    long nmcu() const { return (long)mcux * mcuy; }
+};
 
 // Scan MCUs of one scan of a progressive file: the frame's MCUs for an interleaved scan; for a one-component scan the blocks of the component's own
 // grid, ceil(cw / 8) x ceil(ch / 8) with cw = ceil(w * Hc / Hmax) (gw: its blocks per row), not the MCU-padded grid the coefficient arrays have.
-inline long scan_mcus(const Header& hd, const ScanHd& sc, int* gw) {
-    const int hm = hd.nc == 1 ? 1 : hd.ch[0], vm = hd.nc == 1 ? 1 : hd.cv[0];
+inline long scan_mcus(const Header& hd, const Geom& g, const ScanHd& sc, int* gw) {
     if (sc.ns > 1) {
         *gw = 0;
-        return (long)((hd.w + 8 * hm - 1) / (8 * hm)) * ((hd.h + 8 * vm - 1) / (8 * vm));
+        return g.nmcu();
     }
     const int c = sc.sc[0];
-    const int H = hd.nc == 1 ? 1 : hd.ch[c], V = hd.nc == 1 ? 1 : hd.cv[c];
-    const long cw = ((long)hd.w * H + hm - 1) / hm, chh = ((long)hd.h * V + vm - 1) / vm;
+    const long cw = ((long)hd.w * g.H[c] + g.hm - 1) / g.hm, chh = ((long)hd.h * g.V[c] + g.vm - 1) / g.vm;
     *gw = (int)((cw + 7) / 8);
     return (long)*gw * ((chh + 7) / 8);
 }
 
-// Fills the descriptors (their ws_* offsets from ws_base on) and returns the workspace bytes, or LPI_EINVAL.  zero_lo / zero_hi: the coefficient
-// range the caller clears before huff_kernel.  Progressive files (flags & LPI_JPEG_PROGRESSIVE) get a JDesc with k = 0, which the baseline kernels
-// pass over, and one PScan per scan: scans sorted by launch round, rounds[r] = how many run in round r, at ws_scans in the workspace (behind
-// everything a batch of baseline files has: such a batch needs the same bytes with and without the flag).
-int plan(int flags, int B, const uint8_t* host, const long* offsets, std::vector<JDesc>* descs, long* bytes, long* zero_lo, long* zero_hi,
-         std::vector<PScan>* scans = nullptr, std::vector<int>* rounds = nullptr, long* ws_scans = nullptr) {
+// A scan of nmcu scan MCUs with the entropy-coded bytes src[lo, hi): its unstuffed bytes and its segment table placed at `at`, which moves past
+// them.  ri: the restart interval at its SOS; 0 makes the whole scan one interval.
+EntRange place_range(long lo, long hi, long nmcu, int ri, long& at) {
+    EntRange e;
+    e.src_lo = lo;
+    e.src_hi = hi;
+    e.ri = ri ? ri : (int)std::min(nmcu, (long)0x7fffffff);
+    e.nseg = (int)((nmcu + e.ri - 1) / e.ri);
+    e.unst_cap = hi - lo + 16;
+    e.ws_unst = at;
+    at += align256(e.unst_cap);
+    e.ws_seg = at;
+    at += align256((long)e.nseg * 4);
+    return e;
+}
+
+// What one decode call needs.  The workspace, every part rounded up to 256 bytes: the descriptors; every scan's unstuffed bytes and segment table,
+// in file order and scan order; every image's coefficient arrays, [zero_lo, zero_hi), which the caller clears before huff_kernel; every image's
+// sample planes; at ws_scans the PScan table (behind everything a batch of baseline files has: such a batch needs the same bytes with and without
+// the flag).  scans: sorted by launch round, rounds[r] of them run in round r.
+struct Plan {
+    std::vector<JDesc> descs;
+    std::vector<PScan> scans;
+    std::vector<int> rounds;
+    long bytes = 0, zero_lo = 0, zero_hi = 0, ws_scans = 0;
+};
+
+// 0, or LPI_EINVAL (an argument, or a file with a structural error or outside the envelope of `flags`).  A progressive file gets a JDesc with
+// k = 0, which the baseline kernels pass over, and one PScan per scan.
+int plan(int flags, int B, const uint8_t* host, const long* offsets, Plan& pl) {
     if (B < 1 || B > 65535 || !host || !offsets || (flags & ~LPI_JPEG_PROGRESSIVE)) return LPI_EINVAL;
-    if (descs) descs->assign(B, JDesc());
-    long ws = desc_bytes(B);
-    std::vector<Header> hds(B);
-    std::vector<long> coef_blocks(B);
-    long nscans = 0;
+    pl.descs.assign(B, JDesc());
+    std::vector<PScan> ps;              // in file order
+    std::vector<int> level;
+    Header hd;
+    long at = align256((long)B * (long)sizeof(JDesc)), coef = 0, plane = 0;        // coef, plane: from the start of their regions
     for (int i = 0; i < B; ++i) {
         if (offsets[i] < 0 || offsets[i + 1] < offsets[i] + 4) return LPI_EINVAL;
-        Header& hd = hds[i];
         if (parse_headers(host + offsets[i], offsets[i + 1] - offsets[i], hd, flags) != 0 || !hd.gpu) return LPI_EINVAL;
-        const int hm = hd.nc == 1 ? 1 : hd.ch[0], vm = hd.nc == 1 ? 1 : hd.cv[0];
-        const long mcux = (hd.w + 8 * hm - 1) / (8 * hm), mcuy = (hd.h + 8 * vm - 1) / (8 * vm);
-        const long nmcu = mcux * mcuy;
-        if (hd.prog) {
-            for (const ScanHd& sc : hd.scans) {
-                int gw = 0;
-                const long n = scan_mcus(hd, sc, &gw);
-                ws += align256(sc.end - sc.ent + 16);
-                ws += align256((sc.ri ? (n + sc.ri - 1) / sc.ri : 1) * 4);
-            }
-            nscans += (long)hd.scans.size();
-        } else {
-            const long ent_len = offsets[i + 1] - offsets[i] - hd.ent;
-            if (ent_len < 0) return LPI_EINVAL;
-            ws += align256(ent_len + 16);
-            const long nseg = hd.ri ? (nmcu + hd.ri - 1) / hd.ri : 1;
-            ws += align256(nseg * 4);
-        }
-        coef_blocks[i] = nmcu * (hd.nc == 1 ? 1 : hm * vm + 2);
-    }
-    const long coef_lo = ws;
-    for (int i = 0; i < B; ++i) ws += align256(coef_blocks[i] * 128);
-    const long coef_hi = ws;
-    for (int i = 0; i < B; ++i) ws += align256(coef_blocks[i] * 64);
-    const long scans_at = ws;
-    ws += align256(nscans * (long)sizeof(PScan));
-    if (zero_lo) *zero_lo = coef_lo;
-    if (zero_hi) *zero_hi = coef_hi;
-    if (ws_scans) *ws_scans = scans_at;
-    *bytes = ws;
-    if (!descs) return 0;
-    // second walk: the offsets
-    std::vector<PScan> ps;
-    std::vector<int> level;
-    long at = desc_bytes(B), at_coef = coef_lo, at_plane = coef_hi;
-    for (int i = 0; i < B; ++i) {
-        const Header& hd = hds[i];
-        JDesc& j = (*descs)[i];
+        const Geom g(hd);
+        JDesc& j = pl.descs[i];
         j.w = hd.w;
         j.h = hd.h;
         j.nc = hd.nc;
-        j.hs = hd.nc == 1 ? 1 : hd.ch[0];
-        j.vs = hd.nc == 1 ? 1 : hd.cv[0];
-        j.mcux = (hd.w + 8 * j.hs - 1) / (8 * j.hs);
-        j.mcuy = (hd.h + 8 * j.vs - 1) / (8 * j.vs);
-        const long nmcu = (long)j.mcux * j.mcuy;
-        j.dw = (hd.w + j.hs - 1) / j.hs;
-        j.dh = (hd.h + j.vs - 1) / j.vs;
-        long ent_len = 0;
-        if (hd.prog) {
-            for (const ScanHd& sc : hd.scans) {
-                PScan q = PScan();
-                q.nmcu = scan_mcus(hd, sc, &q.gw);
-                q.ri = sc.ri ? sc.ri : (int)std::min(q.nmcu, (long)0x7fffffff);
-                q.nseg = (int)((q.nmcu + q.ri - 1) / q.ri);
-                q.src_lo = offsets[i] + sc.ent;
-                q.src_hi = offsets[i] + sc.end;
-                q.ws_unst = at;
-                q.unst_cap = sc.end - sc.ent + 16;
-                at += align256(q.unst_cap);
-                q.ws_seg = at;
-                at += align256((long)q.nseg * 4);
-                q.img = i;
-                q.ns = sc.ns;
-                for (int c = 0; c < 3; ++c) q.comp[c] = sc.sc[c];
-                q.ss = sc.ss;
-                q.se = sc.se;
-                q.ah = sc.ah;
-                q.al = sc.al;
-                std::memcpy(q.tab, sc.tab, sizeof(q.tab));
-                ps.push_back(q);
-                level.push_back(sc.level);
-            }
-        } else {
-            j.src_ent = offsets[i] + hd.ent;
-            j.src_end = offsets[i + 1];
-            j.ri = hd.ri ? hd.ri : (int)std::min(nmcu, (long)0x7fffffff);
-            j.nseg = (int)((nmcu + j.ri - 1) / j.ri);
-            ent_len = j.src_end - j.src_ent;
-            j.ws_unst = at;
-            j.unst_cap = ent_len + 16;
-            at += align256(ent_len + 16);
-            j.ws_seg = at;
-            at += align256((long)j.nseg * 4);
-            int b = 0;
+        j.hs = g.hm;
+        j.vs = g.vm;
+        j.mcux = g.mcux;
+        j.mcuy = g.mcuy;
+        j.dw = (hd.w + g.hm - 1) / g.hm;
+        j.dh = (hd.h + g.vm - 1) / g.vm;
+        for (const ScanHd& sc : hd.scans) {             // a progressive file's
+            PScan q = PScan();
+            q.nmcu = scan_mcus(hd, g, sc, &q.gw);
+            q.ent = place_range(offsets[i] + sc.ent, offsets[i] + sc.end, q.nmcu, sc.ri, at);
+            q.img = i;
+            q.ns = sc.ns;
+            for (int c = 0; c < 3; ++c) q.comp[c] = sc.sc[c];
+            q.ss = sc.ss;
+            q.se = sc.se;
+            q.ah = sc.ah;
+            q.al = sc.al;
+            std::memcpy(q.tab, sc.tab, sizeof(q.tab));
+            ps.push_back(q);
+            level.push_back(sc.level);
+        }
+        if (!hd.prog) {
+            j.ent = place_range(offsets[i] + hd.ent, offsets[i + 1], g.nmcu(), hd.ri, at);
             for (int s = 0; s < hd.ns; ++s) {
                 const int f = hd.sc[s];
-                const int H = hd.nc == 1 ? 1 : hd.ch[f], V = hd.nc == 1 ? 1 : hd.cv[f];
                 j.scomp[s] = f;
                 j.dc[s] = hd.hs[0][hd.std_[s]];
                 j.ac[s] = hd.hs[1][hd.sta[s]];
-                for (int y = 0; y < V; ++y)
-                    for (int x = 0; x < H; ++x) {
-                        j.blk_comp[b] = s;
-                        j.blk_dx[b] = x;
-                        j.blk_dy[b] = y;
-                        ++b;
+                for (int y = 0; y < g.V[f]; ++y)
+                    for (int x = 0; x < g.H[f]; ++x) {
+                        j.blk_comp[j.bpm] = s;
+                        j.blk_dx[j.bpm] = x;
+                        j.blk_dy[j.bpm] = y;
+                        ++j.bpm;
                     }
             }
-            j.bpm = b;
+            // chunks per segment: at least MIN_CHUNK bytes each on average, at most HT chunks per image (one per thread); 1 when segments are many
+            const long by_len = (j.ent.src_hi - j.ent.src_lo) / ((long)j.ent.nseg * MIN_CHUNK);
+            j.k = (int)std::max(1L, std::min(j.ent.nseg <= HT / 2 ? (long)(HT / j.ent.nseg) : 1L, by_len));
         }
         for (int c = 0; c < hd.nc; ++c) {
-            const int H = hd.nc == 1 ? 1 : hd.ch[c], V = hd.nc == 1 ? 1 : hd.cv[c];
-            j.bw[c] = j.mcux * H;
-            j.bh[c] = j.mcuy * V;
+            j.bw[c] = g.mcux * g.H[c];
+            j.bh[c] = g.mcuy * g.V[c];
             std::memcpy(j.qt[c], hd.qt[hd.ctq[c]], sizeof(j.qt[c]));
-            j.ws_coef[c] = at_coef;
-            at_coef += (long)j.bw[c] * j.bh[c] * 128;
-            j.ws_plane[c] = at_plane;
-            at_plane += (long)j.bw[c] * j.bh[c] * 64;
+            j.ws_coef[c] = coef;
+            coef += (long)j.bw[c] * j.bh[c] * 128;
+            j.ws_plane[c] = plane;
+            plane += (long)j.bw[c] * j.bh[c] * 64;
         }
-        at_coef = coef_lo + (at_coef - coef_lo + 255) / 256 * 256;     // the per-image blocks as counted above
-        at_plane = coef_hi + (at_plane - coef_hi + 255) / 256 * 256;
-        if (hd.prog) {
-            j.k = 0;            // the baseline kernels pass this image over
-            continue;
+        coef = align256(coef);
+        plane = align256(plane);
+    }
+    pl.zero_lo = at;
+    pl.zero_hi = pl.zero_lo + coef;
+    pl.ws_scans = pl.zero_hi + plane;
+    pl.bytes = pl.ws_scans + align256((long)ps.size() * (long)sizeof(PScan));
+    for (JDesc& j : pl.descs)
+        for (int c = 0; c < j.nc; ++c) {
+            j.ws_coef[c] += pl.zero_lo;
+            j.ws_plane[c] += pl.zero_hi;
         }
-        // chunks per segment: at least MIN_CHUNK bytes each on average, at most HT chunks per image (one per thread); 1 when segments are many
-        long k = j.nseg <= HT / 2 ? HT / j.nseg : 1;
-        const long by_len = ent_len / ((long)j.nseg * MIN_CHUNK);
-        if (k > by_len) k = by_len;
-        j.k = (int)(k < 1 ? 1 : k);
-    }
-    if (scans && rounds) {
-        scans->clear();
-        rounds->assign(LPI_JPEG_MAX_SCANS + 1, 0);
-        for (int r = 1; r <= LPI_JPEG_MAX_SCANS; ++r)
-            for (size_t q = 0; q < ps.size(); ++q)
-                if (level[q] == r) {
-                    scans->push_back(ps[q]);
-                    ++(*rounds)[r];
-                }
-    }
+    pl.rounds.assign(LPI_JPEG_MAX_SCANS + 1, 0);
+    for (int r = 1; r <= LPI_JPEG_MAX_SCANS; ++r)
+        for (size_t q = 0; q < ps.size(); ++q)
+            if (level[q] == r) {
+                pl.scans.push_back(ps[q]);
+                ++pl.rounds[r];
+            }
     return 0;
 }
 
@@ -544,10 +510,13 @@ __device__ inline int block_excl_scan(int v, int* sh, int& total) {
     return r;
 }
 
-// One workgroup: src[lo, hi) without the stuffing into un, the end of each of the nseg restart intervals into seg.  Returns the status flags (valid
-// in thread 0).  sh: NT ints of LDS, s_end: one long.
-__device__ inline int unstuff_range(const uint8_t* __restrict__ src, long lo, long hi, uint8_t* __restrict__ un, int* __restrict__ seg, int nseg,
-                                    int* sh, long* s_end_p) {
+// One workgroup: the bytes of range r without the stuffing into its unstuffed bytes, the end of each of its restart intervals into its segment
+// table.  Returns the status flags (valid in thread 0).  sh: NT ints of LDS, s_end: one long.
+__device__ inline int unstuff_range(const EntRange& r, const uint8_t* __restrict__ src, uint8_t* __restrict__ ws, int* sh, long* s_end_p) {
+    const long lo = r.src_lo, hi = r.src_hi;
+    uint8_t* __restrict__ un = ws + r.ws_unst;
+    int* __restrict__ seg = reinterpret_cast<int*>(ws + r.ws_seg);
+    const int nseg = r.nseg;
     long& s_end = *s_end_p;
     const int t = threadIdx.x;
     long emitted = 0;
@@ -633,7 +602,7 @@ __global__ __launch_bounds__(NT) void unstuff_kernel(const JDesc* __restrict__ d
         if (threadIdx.x == 0) status[blockIdx.x] = 0;
         return;
     }
-    const int f = unstuff_range(src, d.src_ent, d.src_end, ws + d.ws_unst, reinterpret_cast<int*>(ws + d.ws_seg), d.nseg, sh, &s_end);
+    const int f = unstuff_range(d.ent, src, ws, sh, &s_end);
     if (threadIdx.x == 0) status[blockIdx.x] = f;
 }
 
@@ -643,7 +612,7 @@ __global__ __launch_bounds__(NT) void punstuff_kernel(const PScan* __restrict__ 
     __shared__ int sh[NT];
     __shared__ long s_end;
     const PScan& sc = scans[blockIdx.x];
-    const int f = unstuff_range(src, sc.src_lo, sc.src_hi, ws + sc.ws_unst, reinterpret_cast<int*>(ws + sc.ws_seg), sc.nseg, sh, &s_end);
+    const int f = unstuff_range(sc.ent, src, ws, sh, &s_end);
     if (threadIdx.x == 0 && f) atomicOr(status + sc.img, f);
 }
 
@@ -685,6 +654,48 @@ struct Reader {
 
 __device__ inline int extend(int v, int s) { return s && v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
+// The code at the head of w32: returns its length (0: not a code) and its symbol.
+__device__ inline int huff_symbol(const Lut& L, uint32_t w32, int& sym) {
+    const uint32_t w16 = w32 >> 16;
+    const int e = L.lut[w16 >> (16 - LUT_BITS)];
+    if (e) {
+        sym = e & 255;
+        return e >> 8;
+    }
+    for (int l = LUT_BITS + 1; l <= 16; ++l) {
+        const int code = (int)(w16 >> (16 - l));
+        if (code <= L.maxcode[l]) {
+            sym = L.vals[(code + L.valoff[l]) & 255];
+            return l;
+        }
+    }
+    return 0;
+}
+
+// The decoding tables of one Huffman table: the code ranges per length, then the short-code lookup entry by entry.
+__device__ inline void lut_codes(const HuffSpec& hs, Lut& L) {
+    int code = 0, k = 0;
+    L.maxcode[0] = -1;
+    L.valoff[0] = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int n = hs.bits[l - 1];
+        L.valoff[l] = k - code;
+        code += n;
+        k += n;
+        L.maxcode[l] = n ? code - 1 : -1;
+        code <<= 1;
+    }
+    for (int q = 0; q < 256; ++q) L.vals[q] = hs.vals[q];
+}
+
+__device__ inline uint16_t lut_entry(const Lut& L, int e) {
+    for (int l = 1; l <= LUT_BITS; ++l) {
+        const int code = e >> (LUT_BITS - l);
+        if (code <= L.maxcode[l]) return (uint16_t)((l << 8) | L.vals[(code + L.valoff[l]) & 255]);
+    }
+    return 0;
+}
+
 // Where block b of an MCU goes: its scan component, and the position of its 8x8 block inside the MCU's share of that component (huff_kernel's LDS)
 struct BlkInfo {
     int sc, dx, dy, H, V, bw;
@@ -714,22 +725,8 @@ __device__ int decode_run(const BlkInfo* __restrict__ bi, int bpm, int mcux, con
         if (stop_bit < 0 && st.p > rd.E) break;
         const uint32_t w32 = rd.peek32(st.p);
         const Lut& L = st.z == 0 ? dl[sc] : al[sc];
-        const uint32_t w16 = w32 >> 16;
-        int len = 0, sym = 0;
-        const int e = L.lut[w16 >> (16 - LUT_BITS)];
-        if (e) {
-            len = e >> 8;
-            sym = e & 255;
-        } else {
-            for (int l = LUT_BITS + 1; l <= 16; ++l) {
-                const int code = (int)(w16 >> (16 - l));
-                if (code <= L.maxcode[l]) {
-                    len = l;
-                    sym = L.vals[(code + L.valoff[l]) & 255];
-                    break;
-                }
-            }
-        }
+        int sym = 0;
+        const int len = huff_symbol(L, w32, sym);
         if (!len) {                                  // invalid code
             *flags |= ST_CODE;
             st.p += 1;
@@ -789,27 +786,12 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
     const int t = threadIdx.x;
     if (d.k == 0) return;                        // a progressive file: pscan_kernel's
     if (status[blockIdx.x] != 0) return;         // restart markers out of order: the segment table is not valid (uniform: before any barrier)
-    const uint8_t* un = ws + d.ws_unst;
-    const int* seg = reinterpret_cast<const int*>(ws + d.ws_seg);
+    const uint8_t* un = ws + d.ent.ws_unst;
+    const int* seg = reinterpret_cast<const int*>(ws + d.ent.ws_seg);
     const int ns = d.nc, bpm = d.bpm, mcux = d.mcux;
 
     // tables
-    if (t < 2 * ns) {
-        const HuffSpec& hs = t < ns ? d.dc[t] : d.ac[t - ns];
-        Lut& L = luts[t < ns ? t : 3 + t - ns];
-        int code = 0, k = 0;
-        L.maxcode[0] = -1;
-        L.valoff[0] = 0;
-        for (int l = 1; l <= 16; ++l) {
-            const int n = hs.bits[l - 1];
-            L.valoff[l] = k - code;
-            code += n;
-            k += n;
-            L.maxcode[l] = n ? code - 1 : -1;
-            code <<= 1;
-        }
-        for (int q = 0; q < 256; ++q) L.vals[q] = hs.vals[q];
-    }
+    if (t < 2 * ns) lut_codes(t < ns ? d.dc[t] : d.ac[t - ns], luts[t < ns ? t : 3 + t - ns]);
     if (t < bpm) {
         const int sc = d.blk_comp[t], f = d.scomp[sc];
         const bool luma = d.nc == 3 && f == 0;
@@ -821,15 +803,7 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
     for (int q = t; q < 2 * ns * (1 << LUT_BITS); q += HT) {
         const int tb = q >> LUT_BITS, e = q & ((1 << LUT_BITS) - 1);
         Lut& L = luts[tb < ns ? tb : 3 + tb - ns];
-        uint16_t v = 0;
-        for (int l = 1; l <= LUT_BITS; ++l) {
-            const int code = e >> (LUT_BITS - l);
-            if (code <= L.maxcode[l]) {
-                v = (uint16_t)((l << 8) | L.vals[(code + L.valoff[l]) & 255]);
-                break;
-            }
-        }
-        L.lut[e] = v;
+        L.lut[e] = lut_entry(L, e);
     }
     __syncthreads();
     const Lut* dl = luts;
@@ -837,16 +811,16 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
     int flags = 0;
     const int k = d.k;
     const long nmcu = (long)mcux * d.mcuy;
-    const long cap = d.unst_cap;
+    const long cap = d.ent.unst_cap;
 
     if (k == 1) {
         // every segment is one chunk with an exact start: each thread decodes whole segments
-        for (int s = t; s < d.nseg; s += HT) {
+        for (int s = t; s < d.ent.nseg; s += HT) {
             const int s0 = s ? seg[s - 1] : 0, s1 = seg[s];
             if (s0 > s1) { flags |= ST_RST; continue; }
             Reader rd{un, cap, s1 * 8, -1000, 0};
             DecState st{s0 * 8, 0, 0};
-            const long m0 = (long)s * d.ri, m1 = m0 + d.ri < nmcu ? m0 + d.ri : nmcu;
+            const long m0 = (long)s * d.ent.ri, m1 = m0 + d.ent.ri < nmcu ? m0 + d.ent.ri : nmcu;
             const long want = (m1 - m0) * bpm;
             int dcs[3] = {0, 0, 0}, pred[3] = {0, 0, 0}, f = 0;
             const int nb = decode_run(s_bi, bpm, mcux, s_zz, dl, al, rd, st, -1, (int)want, dcs, &f, ws, m0 * bpm, m1 * bpm, pred);
@@ -854,7 +828,7 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
             if (nb != want || st.p > rd.E) flags |= ST_EOD;
         }
     } else {
-        const int nch = d.nseg * k;          // <= HT
+        const int nch = d.ent.nseg * k;          // <= HT
         const int s = t / k, j = t % k;
         const bool mine = t < nch;
         int c0 = 0, c1 = 0, E = 0;
@@ -937,7 +911,7 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
         if (mine) {
             const long first = s_cnt[t] - own0;
             int pred[3] = {s_dc[t][0] - own1, s_dc[t][1] - own2, s_dc[t][2] - own3};
-            const long m0 = (long)s * d.ri, m1 = m0 + d.ri < nmcu ? m0 + d.ri : nmcu;
+            const long m0 = (long)s * d.ent.ri, m1 = m0 + d.ent.ri < nmcu ? m0 + d.ent.ri : nmcu;
             const long want = (m1 - m0) * bpm;
             Reader rd{un, cap, E, -1000, 0};
             DecState st{s_np[t], s_nz[t], s_nb[t]};
@@ -959,48 +933,7 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------ progressive scans
-// jdphuff.c.  Returns the code's length (0: not a code) and its symbol.
-__device__ inline int huff_symbol(const Lut& L, uint32_t w32, int& sym) {
-    const uint32_t w16 = w32 >> 16;
-    const int e = L.lut[w16 >> (16 - LUT_BITS)];
-    if (e) {
-        sym = e & 255;
-        return e >> 8;
-    }
-    for (int l = LUT_BITS + 1; l <= 16; ++l) {
-        const int code = (int)(w16 >> (16 - l));
-        if (code <= L.maxcode[l]) {
-            sym = L.vals[(code + L.valoff[l]) & 255];
-            return l;
-        }
-    }
-    return 0;
-}
-
-// The decoding tables of one Huffman table: the code ranges per length, then the short-code lookup entry by entry (huff_kernel builds the same).
-__device__ inline void lut_codes(const HuffSpec& hs, Lut& L) {
-    int code = 0, k = 0;
-    L.maxcode[0] = -1;
-    L.valoff[0] = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int n = hs.bits[l - 1];
-        L.valoff[l] = k - code;
-        code += n;
-        k += n;
-        L.maxcode[l] = n ? code - 1 : -1;
-        code <<= 1;
-    }
-    for (int q = 0; q < 256; ++q) L.vals[q] = hs.vals[q];
-}
-
-__device__ inline uint16_t lut_entry(const Lut& L, int e) {
-    for (int l = 1; l <= LUT_BITS; ++l) {
-        const int code = e >> (LUT_BITS - l);
-        if (code <= L.maxcode[l]) return (uint16_t)((l << 8) | L.vals[(code + L.valoff[l]) & 255]);
-    }
-    return 0;
-}
-
+// jdphuff.c
 // One restart interval (scan MCUs [m0, m1), bits from p) of one scan, by one lane.  Returns the status flags.  Whatever the bits are, block indices
 // stay below the scan's host-validated MCU count and coefficient indices inside [Ss, Se]; anything libjpeg would only warn about is a flag (the host
 // then decodes the file).  blk: 64 int16 of LDS of this lane (AC refinement reads the block's earlier coefficients through it).
@@ -1106,7 +1039,7 @@ __device__ int pscan_segment(const JDesc& d, const PScan& sc, const Lut* __restr
             __builtin_memcpy(&v, gp + 4 * q, 8);
             __builtin_memcpy(blk + 4 * q, &v, 8);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) nz |= (uint64_t)(((v >> (16 * u)) & 0xffff) != 0) << kUnzigzag[4 * q + u];
+            for (int u = 0; u < 4; ++u) nz |= (uint64_t)(((v >> (16 * u)) & 0xffff) != 0) << kUnzigzag.v[4 * q + u];
         }
         auto correct = [&](int k) {             // the correction bit of the nonzero coefficient at zigzag index k
             const uint32_t bit = rd.peek32(p) >> 31;
@@ -1195,17 +1128,17 @@ __global__ __launch_bounds__(PT) void pscan_kernel(const JDesc* __restrict__ des
         L.lut[e] = lut_entry(L, e);
     }
     __syncthreads();
-    const uint8_t* un = ws + sc.ws_unst;
-    const int* seg = reinterpret_cast<const int*>(ws + sc.ws_seg);
+    const uint8_t* un = ws + sc.ent.ws_unst;
+    const int* seg = reinterpret_cast<const int*>(ws + sc.ent.ws_seg);
     int flags = 0;
-    for (int s = t; s < sc.nseg; s += PT) {
+    for (int s = t; s < sc.ent.nseg; s += PT) {
         const int s0 = s ? seg[s - 1] : 0, s1 = seg[s];
         if (s0 > s1) {
             flags |= ST_RST;
             continue;
         }
-        Reader rd{un, sc.unst_cap, s1 * 8, -1000, 0};
-        const long m0 = (long)s * sc.ri, m1 = m0 + sc.ri < sc.nmcu ? m0 + sc.ri : sc.nmcu;
+        Reader rd{un, sc.ent.unst_cap, s1 * 8, -1000, 0};
+        const long m0 = (long)s * sc.ent.ri, m1 = m0 + sc.ent.ri < sc.nmcu ? m0 + sc.ent.ri : sc.nmcu;
         flags |= pscan_segment(d, sc, luts, s_zz, rd, s0 * 8, m0, m1, ws, s_blk[t]);
     }
     if (flags) atomicOr(status + sc.img, flags);
@@ -1376,7 +1309,10 @@ extern "C" int lpi_jpeg_info(const void* data, long nbytes, long* info) {
 
 extern "C" int lpi_jpeg_decode_workspace_x(int flags, int B, const void* host, const long* offsets, long* bytes) {
     if (!bytes) return LPI_EINVAL;
-    return plan(flags, B, static_cast<const uint8_t*>(host), offsets, nullptr, bytes, nullptr, nullptr);
+    Plan pl;
+    const int rc = plan(flags, B, static_cast<const uint8_t*>(host), offsets, pl);
+    if (rc == 0) *bytes = pl.bytes;
+    return rc;
 }
 
 extern "C" int lpi_jpeg_decode_workspace(int B, const void* host, const long* offsets, long* bytes) {
@@ -1386,13 +1322,12 @@ extern "C" int lpi_jpeg_decode_workspace(int B, const void* host, const long* of
 extern "C" int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off,
                                     void* out, long out_bytes, int* status, void* ws, long ws_bytes, void* stream) {
     if (!src || !out || !status || !ws || !out_off || src_bytes < 1 || out_bytes < 1) return LPI_EINVAL;
-    std::vector<JDesc> descs;
-    std::vector<PScan> scans;
-    std::vector<int> rounds;
-    long need = 0, z0 = 0, z1 = 0, ws_scans = 0;
-    const int rc = plan(flags, B, static_cast<const uint8_t*>(host), offsets, &descs, &need, &z0, &z1, &scans, &rounds, &ws_scans);
+    Plan pl;
+    const int rc = plan(flags, B, static_cast<const uint8_t*>(host), offsets, pl);
     if (rc != 0) return rc;
-    if (ws_bytes < need || offsets[B] > src_bytes) return LPI_EINVAL;
+    if (ws_bytes < pl.bytes || offsets[B] > src_bytes) return LPI_EINVAL;
+    std::vector<JDesc>& descs = pl.descs;
+    const std::vector<PScan>& scans = pl.scans;
     int maxw = 1, maxh = 1;
     long maxblk = 1;
     for (int i = 0; i < B; ++i) {
@@ -1410,10 +1345,10 @@ extern "C" int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const lo
     hipError_t e = hipMemcpyAsync(ws, descs.data(), (size_t)B * sizeof(JDesc), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return (int)e;
     if (!scans.empty()) {
-        e = hipMemcpyAsync(static_cast<char*>(ws) + ws_scans, scans.data(), scans.size() * sizeof(PScan), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(static_cast<char*>(ws) + pl.ws_scans, scans.data(), scans.size() * sizeof(PScan), hipMemcpyHostToDevice, s);
         if (e != hipSuccess) return (int)e;
     }
-    e = hipMemsetAsync(static_cast<char*>(ws) + z0, 0, (size_t)(z1 - z0), s);
+    e = hipMemsetAsync(static_cast<char*>(ws) + pl.zero_lo, 0, (size_t)(pl.zero_hi - pl.zero_lo), s);
     if (e != hipSuccess) return (int)e;
     const JDesc* dd = static_cast<const JDesc*>(ws);
     uint8_t* w8 = static_cast<uint8_t*>(ws);
@@ -1423,15 +1358,15 @@ extern "C" int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const lo
     LPI_CHECK_LAST();
     if (!scans.empty()) {
         // progressive files: their scans' bytes unstuffed, then one launch per round of scans that may run side by side
-        const PScan* ps = reinterpret_cast<const PScan*>(w8 + ws_scans);
+        const PScan* ps = reinterpret_cast<const PScan*>(w8 + pl.ws_scans);
         LPI_LAUNCH(punstuff_kernel, dim3((unsigned)scans.size()), dim3(NT), 0, s, ps, (const uint8_t*)src, w8, status);
         LPI_CHECK_LAST();
         size_t first = 0;
         for (int r = 1; r <= LPI_JPEG_MAX_SCANS; ++r) {
-            if (!rounds[r]) continue;
-            LPI_LAUNCH(pscan_kernel, dim3((unsigned)rounds[r]), dim3(PT), 0, s, dd, ps + first, w8, status);
+            if (!pl.rounds[r]) continue;
+            LPI_LAUNCH(pscan_kernel, dim3((unsigned)pl.rounds[r]), dim3(PT), 0, s, dd, ps + first, w8, status);
             LPI_CHECK_LAST();
-            first += (size_t)rounds[r];
+            first += (size_t)pl.rounds[r];
         }
     }
     LPI_LAUNCH(idct_kernel, dim3((unsigned)((maxblk + 63) / 64), B), dim3(64), 0, s, dd, w8);

@@ -118,6 +118,10 @@ JPEG_INFO_X = 10    # ... and lpi_jpeg_info_x (LPI_JPEG_INFO_X: + {parsed as pro
 JPEG_PROGRESSIVE = 1        # LPI_JPEG_PROGRESSIVE: progressive files with a complete scan script are inside the envelope
 
 
+def _flags(progressive):
+    return JPEG_PROGRESSIVE if progressive else 0       # the flags word of the lpi_jpeg_*_x calls
+
+
 def _u8(data):
     """bytes / numpy / tensor -> a contiguous host uint8 numpy view."""
     if torch.is_tensor(data):
@@ -132,7 +136,7 @@ def jpeg_info(data, progressive=False):
     decided there and only there."""
     a = _u8(data)
     info = (ctypes.c_long * JPEG_INFO_X)()
-    rc = _lib.load().lpi_jpeg_info_x(JPEG_PROGRESSIVE if progressive else 0, a.ctypes.data if a.size else None, int(a.size), ctypes.addressof(info))
+    rc = _lib.load().lpi_jpeg_info_x(_flags(progressive), a.ctypes.data if a.size else None, int(a.size), ctypes.addressof(info))
     if rc != 0:
         return None
     return bool(info[0]), int(info[1]), int(info[2])
@@ -152,7 +156,7 @@ def jpeg_workspace_bytes(host, offsets, progressive=False):
     outside the envelope (progressive: that of LPI_JPEG_PROGRESSIVE) or has a structural error."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     out = ctypes.c_long(0)
-    rc = _lib.load().lpi_jpeg_decode_workspace_x(JPEG_PROGRESSIVE if progressive else 0, int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
+    rc = _lib.load().lpi_jpeg_decode_workspace_x(_flags(progressive), int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
                                                  ctypes.addressof(out))
     if rc != 0:
         raise _lib.LpiError(f"lpi_jpeg_decode_workspace_x failed with code {rc} (a file outside the envelope or with a broken header)")
@@ -164,7 +168,7 @@ def jpeg_launch(host, offsets, src, out_off, out, status, ws, stream, progressiv
     progressive: with LPI_JPEG_PROGRESSIVE (flags = 0 is lpi_jpeg_decode_u8)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     out_off = np.ascontiguousarray(out_off, dtype=np.int64)
-    rc = _lib.load().lpi_jpeg_decode_u8_x(JPEG_PROGRESSIVE if progressive else 0, int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
+    rc = _lib.load().lpi_jpeg_decode_u8_x(_flags(progressive), int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
                                           src.data_ptr(), int(src.numel()), out_off.ctypes.data, out.data_ptr(), int(out.numel()), status.data_ptr(),
                                           ws.data_ptr(), int(ws.numel()), stream.cuda_stream)
     if rc != 0:
@@ -190,13 +194,14 @@ def _side_stream(device):
     return s
 
 
+def _fresh(device):     # the default buffer provider bufs(key, nbytes, 'pinned' | 'device'): a fresh tensor for every request
+    return lambda key, n, where: torch.empty(max(int(n), 1), dtype=torch.uint8, **({"pin_memory": True} if where == "pinned" else {"device": device}))
+
+
 def _issue_decode(batch, device, stream, bufs=None):
     """Enqueues on `stream`: the H2D copy of the batch's file bytes, lpi_jpeg_decode_u8 for its GPU files, the H2D copies of its host-decoded images, the
-    D2H copy of the statuses.  bufs(key, nbytes, pinned): a buffer provider (BatchPipeline's slots); fresh tensors by default."""
-    if bufs is None:
-        def bufs(key, n, where):
-            return torch.empty(max(int(n), 1), dtype=torch.uint8, pin_memory=True) if where == "pinned" else torch.empty(max(int(n), 1), dtype=torch.uint8,
-                                                                                                                      device=device)
+    D2H copy of the statuses.  bufs: a buffer provider (BatchPipeline's slots); fresh tensors by default."""
+    bufs = bufs or _fresh(device)
     B = len(batch)
     wh = np.asarray(batch.wh, dtype=np.int64).reshape(B, 2)
     nbytes = wh[:, 0] * wh[:, 1] * 3
@@ -268,37 +273,32 @@ def decode_jpeg(batch, device="cuda", stream=None):
     return [d.pixels[int(o):int(o) + int(w) * int(h) * 3].view(int(h), int(w), 3) for o, (w, h) in zip(d.offsets, d.wh)]
 
 
-def encoded_descriptors(batch, d):
-    """The [B, 12] resample descriptor table of a decoded EncodedBatch (its images packed as _Decoded.pixels)."""
+def _decode_resample(batch, size, filter, device, stream, bufs):
+    """EncodedBatch -> device [B,3,S,S] uint8 on `stream`, buffers from bufs (as _issue_decode's): decode, resample, then the host waits for the
+    statuses' copy (the resample may still run); a file whose GPU status is not OK is decoded again by Pillow and the batch resampled again."""
     B = len(batch)
-    params = np.asarray(batch.params, dtype=np.int64).reshape(B, -1)
-    desc = np.empty((B, DESC), dtype=np.int64)
-    desc[:, 0] = d.offsets
-    desc[:, 1:3] = d.wh
-    desc[:, 3:] = params
-    return desc
+    d = _issue_decode(batch, device, stream, bufs)
+    desc = np.empty((B, DESC), dtype=np.int64)          # the resample descriptor table of the images as d.pixels packs them
+    desc[:, 0], desc[:, 1:3], desc[:, 3:] = d.offsets, d.wh, np.asarray(batch.params, dtype=np.int64).reshape(B, -1)
+    ws_bytes = workspace_bytes(desc, size, filter)
+    with torch.cuda.stream(stream):
+        ws, out = bufs("resample_ws", ws_bytes, "device"), bufs("out", B * 3 * size * size, "device")
+    launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, stream, filter)
+    d.ready.synchronize()
+    if _redo_failed(batch, d, stream):
+        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, stream, filter)
+    return out[:B * 3 * size * size].view(B, 3, size, size)
 
 
 def resample_encoded(batch, size=None, device="cuda", stream=None, threads=8, filter=None):
     """EncodedBatch -> device [B,3,S,S] uint8 (CHW, contiguous): the batch resample_decoded (and pixel_format='u8') gives for the same images and
-    draws, byte for byte.  The GPU decodes the files inside the envelope (lpi_jpeg_decode_u8), the worker already decoded the others (Pillow);
-    a file whose GPU status is not OK is decoded again by Pillow and its batch resampled again.  The copies, the decode and the resample run on this
-    module's side stream; the host waits for this batch's statuses only (an event after their copy), not for the work queued on `stream`, and the
-    result is ready in `stream`'s order (default: the device's current stream).  threads: unused (the bytes arrive packed); filter: as
-    resample_decoded's."""
+    draws, byte for byte.  The GPU decodes the files inside the envelope (lpi_jpeg_decode_u8), the worker already decoded the others (Pillow).  All
+    of it runs on this module's side stream (_decode_resample): the host waits for this batch's statuses only, not for the work queued on `stream`;
+    the result is ready in `stream`'s order (default: the device's current one).  threads: unused (the bytes arrive packed); filter: as resample_decoded's."""
     size = int(batch.size if size is None else size)
     filter = _batch_filter(batch, filter)
     device, stream, side = _work_streams(device, stream)
-    d = _issue_decode(batch, device, side)
-    desc = encoded_descriptors(batch, d)
-    ws_bytes = workspace_bytes(desc, size, filter)
-    with torch.cuda.stream(side):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        out = torch.empty((len(batch), 3, size, size), dtype=torch.uint8, device=device)
-        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side, filter)
-    d.ready.synchronize()
-    if _redo_failed(batch, d, side):
-        launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, size, side, filter)
+    out = _decode_resample(batch, size, filter, device, side, _fresh(device))
     stream.wait_stream(side)
     out.record_stream(stream)
     return out

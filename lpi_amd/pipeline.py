@@ -139,21 +139,10 @@ class BatchPipeline:
         read here (this thread waits for the decode): a file the GPU could not decode exactly is decoded by Pillow and the batch resampled again, before
         the batch is handed out."""
         from . import imageops
-        B, S = len(images), int(images.size)
 
         def bufs(key, n, where):
-            return self._dec_buffer(slot, "jpeg_" + key, n, pin_memory=True) if where == "pinned" else self._dec_buffer(slot, "jpeg_" + key, n,
-                                                                                                                     device=self.device)
-        d = imageops._issue_decode(images, self.device, self.side, bufs)
-        desc = imageops.encoded_descriptors(images, d)
-        ws_bytes = imageops.workspace_bytes(desc, S, images.filter)
-        ws = self._dec_buffer(slot, "ws", ws_bytes, device=self.device)
-        out = self._dec_buffer(slot, "out", B * 3 * S * S, device=self.device)
-        imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side, images.filter)
-        d.ready.synchronize()                       # the statuses' copy (the resample may still run)
-        if imageops._redo_failed(images, d, self.side):
-            imageops.launch(desc, d.pixels, d.pixels.numel(), ws, ws_bytes, out, S, self.side, images.filter)
-        return out[:B * 3 * S * S].view(B, 3, S, S)
+            return self._dec_buffer(slot, "jpeg_" + key, n, **({"pin_memory": True} if where == "pinned" else {"device": self.device}))
+        return imageops._decode_resample(images, int(images.size), images.filter, self.device, self.side, bufs)
 
     def _produce(self):
         q, free, stop = self._q, self._free, self._stop      # this pass's hand-over state (a later pass replaces the attributes)

@@ -3,9 +3,10 @@
 of tools/decode_pipeline_bench.py): has a change made the baseline decode slower?  The protocol of profiles/filters_resample_ab.json: warm-up rounds,
 then 40 timed calls of each (HIP events around the call: descriptor copy + clear + launches), interleaved round by round; median, p10 / p90 and
 minimum; the parent against a second handle of itself (its own file copied, so that the loader maps it again) gives the run-to-run spread.  The
-outputs and statuses of the two builds are compared byte for byte.
+outputs and statuses of the two builds are compared byte for byte.  --progressive: the same protocol with lpi_jpeg_decode_u8_x and
+LPI_JPEG_PROGRESSIVE on the 256-file progressive batch of the same pixels (Pillow's 10-scan script).
 
-usage: python3 tools/jpeg_decode_ab.py --parent PATH/liblpi_hip.so [--out FILE.json]   (the other build is this tree's)"""
+usage: python3 tools/jpeg_decode_ab.py --parent PATH/liblpi_hip.so [--progressive] [--out FILE.json]   (the other build is this tree's)"""
 import argparse
 import ctypes
 import json
@@ -29,6 +30,10 @@ def bind(path):
     lib.lpi_jpeg_decode_u8.restype = I
     lib.lpi_jpeg_decode_workspace.argtypes = [I, P, P, P]
     lib.lpi_jpeg_decode_workspace.restype = I
+    lib.lpi_jpeg_decode_u8_x.argtypes = [I, I, P, P, P, L, P, P, L, P, P, L, P]
+    lib.lpi_jpeg_decode_u8_x.restype = I
+    lib.lpi_jpeg_decode_workspace_x.argtypes = [I, I, P, P, P]
+    lib.lpi_jpeg_decode_workspace_x.restype = I
     lib.lpi_version.restype = I
     return lib
 
@@ -38,13 +43,14 @@ def main():
     ap.add_argument("--parent", required=True)
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--progressive", action="store_true", help="lpi_jpeg_decode_u8_x with LPI_JPEG_PROGRESSIVE on the progressive batch")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from decode_pipeline_bench import write_folder
     from lpi_amd import _lib
     dev = torch.device("cuda:0")
     with tempfile.TemporaryDirectory() as root:
-        write_folder(root, 256, 256, 1)
+        write_folder(root, 256, 256, 1, progressive=a.progressive)
         files = [open(os.path.join(root, f"im{i}.jpg"), "rb").read() for i in range(256)]
         twin = os.path.join(root, "parent_twin.so")
         shutil.copyfile(a.parent, twin)
@@ -55,7 +61,8 @@ def main():
     need = {}
     for k, lib in libs.items():
         v = ctypes.c_long(0)
-        assert lib.lpi_jpeg_decode_workspace(256, host.ctypes.data, offs.ctypes.data, ctypes.addressof(v)) == 0
+        workspace = (lib.lpi_jpeg_decode_workspace_x, 1) if a.progressive else (lib.lpi_jpeg_decode_workspace,)
+        assert workspace[0](*workspace[1:], 256, host.ctypes.data, offs.ctypes.data, ctypes.addressof(v)) == 0
         need[k] = v.value
     src = torch.from_numpy(host).to(dev)
     ws = torch.empty(max(need.values()), dtype=torch.uint8, device=dev)
@@ -63,13 +70,14 @@ def main():
     status = torch.empty(256, dtype=torch.int32, device=dev)
     s = torch.cuda.current_stream(dev)
     times = {k: [] for k in libs}
+    decode = {k: (lib.lpi_jpeg_decode_u8_x, 1) if a.progressive else (lib.lpi_jpeg_decode_u8,) for k, lib in libs.items()}
     digest = {}
     for r in range(a.warmup + a.reps):
         for k, lib in libs.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
-            rc = lib.lpi_jpeg_decode_u8(256, host.ctypes.data, offs.ctypes.data, src.data_ptr(), src.numel(), out_off.ctypes.data, out.data_ptr(),
-                                        out.numel(), status.data_ptr(), ws.data_ptr(), need[k], s.cuda_stream)
+            rc = decode[k][0](*decode[k][1:], 256, host.ctypes.data, offs.ctypes.data, src.data_ptr(), src.numel(), out_off.ctypes.data, out.data_ptr(),
+                              out.numel(), status.data_ptr(), ws.data_ptr(), need[k], s.cuda_stream)
             e1.record(s)
             e1.synchronize()
             assert rc == 0, (k, rc)
@@ -77,7 +85,7 @@ def main():
                 times[k].append(1e3 * e0.elapsed_time(e1))
             if r == 0:
                 digest[k] = (out.cpu(), status.tolist())
-    rec = {"tool": "tools/jpeg_decode_ab.py", "batch": "256 baseline files 640 x 480 q90 4:2:0", "file_MB": round(host.size / 1e6, 2), "reps": a.reps,
+    rec = {"tool": "tools/jpeg_decode_ab.py", "batch": f"256 {'progressive' if a.progressive else 'baseline'} files 640 x 480 q90 4:2:0", "file_MB": round(host.size / 1e6, 2), "reps": a.reps,
            "warmup": a.warmup, "versions": {k: int(lib.lpi_version()) for k, lib in libs.items()}, "workspace_bytes": need,
            "bits_equal_parent_new": bool(torch.equal(digest["parent"][0], digest["new"][0]) and digest["parent"][1] == digest["new"][1]),
            "statuses_not_ok": int(sum(1 for v in digest["new"][1] if v))}
