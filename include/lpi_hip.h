@@ -669,6 +669,20 @@ int lpi_jpeg_decode_u8(int B, const void* host, const long* offsets, const void*
 /* lpi_jpeg_info_x fills LPI_JPEG_INFO_X fields: the LPI_JPEG_INFO of lpi_jpeg_info, then {the frame is SOF2 and was parsed as such (only with
  * LPI_JPEG_PROGRESSIVE), its scans inside the envelope (1 for a baseline file whose SOS was reached, else 0)}. */
 #define LPI_JPEG_INFO_X 10
+/* LPI_JPEG_LAYOUTS widens the frame rule of THE ENVELOPE for SOF0 / SOF1 files (one scan in the frame's order, 8-bit, Huffman and the size limits
+ * as above): 1, 3 or 4 components; the first sampled 1x1, 2x1, 2x2, 1x2 (4:4:0), 4x1 (4:1:1) or 1x4, every other component 1x1; any colour marking
+ * libjpeg accepts.  Three components: a JFIF APP0 says YCbCr; else an Adobe APP14 says RGB (transform 0) or YCbCr (any other value); else the ids
+ * 'R','G','B' say RGB, any others YCbCr.  Four components: an Adobe APP14 with a transform other than 0 says YCCK, anything else CMYK; the output is
+ * Pillow's convert("RGB") of its (inverted) CMYK image.  A four-component scan names up to four DC and four AC tables.  Upsampling as libjpeg-turbo's:
+ * the triangle filter for 2x1, 2x2 and 1x2, replication for 4x1 and 1x4.  Other factors (3x1, 4x2, 2x4, ...), a later component that is not 1x1
+ * and ratios that are not whole stay the host's.  lpi_jpeg_info_x then reports the first component's H and V for four-component files too.
+ * A LIMIT OF THIS DECODER, not of the format: SOF2 files keep the frame rule above with LPI_JPEG_PROGRESSIVE | LPI_JPEG_LAYOUTS; the two flags
+ * combine in one batch, but a progressive CMYK or 4:4:0 file is the host's.
+ * A batch without a four-component file: the same workspace bytes, copies and launches as without the flag; with one: one more copy and one more
+ * launch (the Huffman kernel's four-component instantiation).
+ * The value is 4: flags 2 and 3 have been LPI_EINVAL since the flags word exists and callers rely on that, so bit 1 is never given a meaning. */
+#define LPI_JPEG_LAYOUTS 4
+#define LPI_JPEG_FLAGS (LPI_JPEG_PROGRESSIVE | LPI_JPEG_LAYOUTS) /* every valid bit */
 int lpi_jpeg_info_x(int flags, const void* data, long nbytes, long* info);
 int lpi_jpeg_decode_workspace_x(int flags, int B, const void* host, const long* offsets, long* bytes);
 int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const long* offsets, const void* src, long src_bytes, const long* out_off, void* out,

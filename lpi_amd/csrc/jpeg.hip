@@ -1,6 +1,7 @@
 // JPEG files -> packed HWC RGB uint8 pixels on the GPU (pixel_format='jpeg', lpi_amd/imageops.py), byte for byte what Pillow 12 (libjpeg-turbo,
-// default settings) gives for np.asarray(Image.open(f).convert("RGB")): baseline files, and with LPI_JPEG_PROGRESSIVE progressive files whose scan
-// script is complete.  tests/jpeg_restate.py and tests/jpeg_progressive.py restate every step in numpy / plain Python.
+// default settings) gives for np.asarray(Image.open(f).convert("RGB")): baseline files, with LPI_JPEG_PROGRESSIVE progressive files whose scan
+// script is complete, with LPI_JPEG_LAYOUTS baseline files of more layouts (the first component 1x2, 4x1 or 1x4 over the others; RGB; four
+// components, CMYK or YCCK).  tests/jpeg_restate.py, tests/jpeg_progressive.py and tests/jpeg_layouts.py restate every step in numpy / plain Python.
 //
 // The host parses the headers (parse_headers: the one place that decides the envelope; frame_in_envelope is the frame's share of it, the same for
 // a baseline file and a progressive one) and lays the workspace out in one walk over the files (plan: one JDesc per image, its geometry from Geom,
@@ -16,8 +17,10 @@
 //                    quantised coefficients.  A segment whose chunks do not add up to its MCUs, an invalid code, a coefficient index past 63, or
 //                    a read past the segment's end sets the image's status: the caller then decodes that file on the host.
 //   idct_kernel      one thread per 8x8 block: jidctint.c's islow IDCT with its range limit -> the component's sample plane.
-//   color_kernel     one thread per output pixel: jdsample.c's fancy upsampling of the chroma planes (2x1, 2x2; plain replication for chroma
-//                    planes at most 2 samples wide), jdcolor.c's YCbCr -> RGB tables; grayscale replicated into R, G, B.
+//   color_kernel     one thread per output pixel: jdsample.c's fancy upsampling of the planes behind the first (2x1, 2x2; plain replication for
+//                    planes at most 2 samples wide; 1x2 at every width; replication for 4x1 and 1x4), jdcolor.c's YCbCr -> RGB tables;
+//                    grayscale replicated into R, G, B; RGB planes as they are; CMYK / YCCK through Pillow's inversion and convert("RGB").
+// A file of four components is decoded by huff_kernel<4> (one more launch, only for a batch that has one); its fourth component's tables are a JExt.
 //
 // A progressive file (JDesc.k = 0: unstuff_kernel only clears its status, huff_kernel passes it over) has one PScan per scan, with the Huffman tables
 // and the restart interval in force at its SOS; between huff_kernel and idct_kernel its coefficients are built up scan by scan (jdphuff.c):
@@ -64,22 +67,37 @@ struct EntRange {
     int nseg, ri;                   // segments; restart interval in scan MCUs (a scan without restart markers: all of them)
 };
 
-// One image (device copy in the workspace's head).  out: offset into the caller's output, ws_*: into the workspace.
+// What libjpeg's output planes are, and so what color_kernel does with them (jdapimin.c default_decompress_parms, then Pillow's convert("RGB"))
+enum { CT_GRAY = 0, CT_YCC = 1, CT_RGB = 2, CT_CMYK = 3, CT_YCCK = 4 };
+
+// One image (device copy in the workspace's head).  out: offset into the caller's output, ws_*: into the workspace.  The workspace holds B of them
+// in front of everything else, so sizeof(JDesc) is part of the workspace size of every batch: it stays at the 2320 bytes it had before
+// LPI_JPEG_LAYOUTS (the fourth component's tables are a JExt behind the PScan table, which only a batch with such a file has).
 struct JDesc {
     EntRange ent;                   // a baseline file's scan
     long out;                       // first byte of the h x w x 3 output
-    long ws_coef[3];                // int16 [blocks][64] of each frame component
-    long ws_plane[3];               // uint8 sample plane of each frame component
+    long ws_coef[4];                // int16 [blocks][64] of each frame component
+    long ws_plane[4];               // uint8 sample plane of each frame component
+    long ws_ext;                    // a four-component file's JExt
     int w, h, nc, mcux, mcuy, bpm;
-    int bw[3], bh[3];               // block grid of each frame component
-    int blk_comp[10];               // scan component of block b of an MCU
-    int blk_dx[10], blk_dy[10];     // its position inside the MCU's share of that component
-    int scomp[3];                   // frame component of scan component s
-    int hs, vs;                     // luma sampling (1,1), (2,1), (2,2); 1,1 for grayscale
-    int dw, dh;                     // chroma downsampled size
+    int bw[4], bh[4];               // block grid of each frame component
+    int scomp[4];                   // frame component of scan component s
+    int hs, vs;                     // sampling of the first component over the others (which are 1x1); 1,1 for grayscale
+    int dw, dh;                     // downsampled size of the other components
     int k;                          // chunks per segment
-    uint16_t qt[3][64];             // dequantisation table of each frame component, natural order
-    HuffSpec dc[3], ac[3];          // tables of each scan component
+    int ct;                         // CT_*
+    uint8_t blk_comp[10];           // scan component of block b of an MCU
+    uint8_t blk_dx[10], blk_dy[10]; // its position inside the MCU's share of that component
+    uint8_t spare[50];              // what the byte-sized block tables freed and the fourth component did not take: keeps the size (above)
+    uint16_t qt[3][64];             // dequantisation table of each of the first three frame components, natural order
+    HuffSpec dc[3], ac[3];          // tables of each of the first three scan components
+};
+static_assert(sizeof(JDesc) == 2320, "the workspace of a batch of three-component files must not change");
+
+// The fourth component's tables of a four-component file (CMYK, YCCK).
+struct JExt {
+    uint16_t qt[64];
+    HuffSpec dc, ac;
 };
 
 // One scan of a progressive file (device copies behind the sample planes in the workspace, sorted by launch round).
@@ -122,6 +140,7 @@ struct Header {
     int ns = 0, sc[4] = {}, std_[4] = {}, sta[4] = {};
     int ri = 0;
     bool jfif = false, adobe = false, sof = false;
+    int adobe_tf = 0;       // the Adobe APP14's transform byte
     bool qdef[4] = {}, hdef[2][4] = {};
     uint16_t qt[4][64] = {};
     HuffSpec hs[2][4] = {};
@@ -147,20 +166,37 @@ bool huff_ok(const HuffSpec& t, int count, bool dc) {
     return true;
 }
 
+// What libjpeg takes the frame's components for (default_decompress_parms).  Three: a JFIF APP0 says YCbCr; else an Adobe APP14 says RGB with
+// transform 0 and YCbCr with any other value; else the ids 'R','G','B' say RGB and any others YCbCr.  Four: an Adobe APP14 with a transform other
+// than 0 says YCCK, anything else CMYK.
+int color_transform(const Header& hd) {
+    if (hd.nc == 1) return CT_GRAY;
+    if (hd.nc == 4) return hd.adobe && hd.adobe_tf != 0 ? CT_YCCK : CT_CMYK;
+    if (hd.jfif) return CT_YCC;
+    if (hd.adobe) return hd.adobe_tf == 0 ? CT_RGB : CT_YCC;
+    return hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B' ? CT_RGB : CT_YCC;
+}
+
 // The frame's share of the envelope, whatever its scans are: 8-bit, a height in the header, a size the decoder's workspace and its int bit positions
-// take, and grayscale or the three components libjpeg takes for YCbCr with luma sampled 1x1, 2x1 or 2x2 over 1x1 chroma.
-bool frame_in_envelope(const Header& hd) {
+// take, and grayscale or the three components libjpeg takes for YCbCr with luma sampled 1x1, 2x1 or 2x2 over 1x1 chroma.  layouts
+// (LPI_JPEG_LAYOUTS, baseline files only): three components of any marking (color_transform) or four, the first sampled 1x1, 2x1, 2x2, 1x2, 4x1 or
+// 1x4 over the others at 1x1.
+bool frame_in_envelope(const Header& hd, bool layouts) {
     if (hd.prec != 8 || hd.h <= 0 || (long)hd.w * hd.h > LPI_JPEG_MAX_PIXELS) return false;
-    if (hd.nc != 3) return hd.nc == 1;
-    if (!hd.jfif && (hd.adobe || (hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'))) return false;
-    const bool luma = (hd.ch[0] == 1 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 1) || (hd.ch[0] == 2 && hd.cv[0] == 2);
-    return luma && hd.ch[1] == 1 && hd.cv[1] == 1 && hd.ch[2] == 1 && hd.cv[2] == 1;
+    if (hd.nc == 1) return true;
+    if (hd.nc != 3 && !(layouts && hd.nc == 4)) return false;
+    if (!layouts && !hd.jfif && (hd.adobe || (hd.cid[0] == 'R' && hd.cid[1] == 'G' && hd.cid[2] == 'B'))) return false;
+    for (int c = 1; c < hd.nc; ++c)
+        if (hd.ch[c] != 1 || hd.cv[c] != 1) return false;
+    const int H = hd.ch[0], V = hd.cv[0];
+    if ((H == 1 && V == 1) || (H == 2 && V == 1) || (H == 2 && V == 2)) return true;
+    return layouts && ((H == 1 && V == 2) || (H == 4 && V == 1) || (H == 1 && V == 4));
 }
 
 // One SOS of a SOF2 file against the progressive envelope; appends it to hd.scans.  false: the file is the host's.
 bool progressive_scan(Header& hd, const uint8_t* s, long ent, long end, int (*al_cur)[64]) {
     if (hd.scans.empty()) {
-        if (!frame_in_envelope(hd)) return false;
+        if (!frame_in_envelope(hd, false)) return false;        // the new layouts are baseline files only: pscan_kernel holds three tables
         hd.ent = ent;
     }
     if ((int)hd.scans.size() >= LPI_JPEG_MAX_SCANS || hd.ns > 3) return false;
@@ -208,6 +244,7 @@ bool progressive_scan(Header& hd, const uint8_t* s, long ent, long end, int (*al
 // 0: parsed (hd.gpu says whether the GPU decodes it); LPI_EINVAL: a structural error in the headers.  A file without SOI is parsed as "host".
 // flags & LPI_JPEG_PROGRESSIVE: a SOF2 file is parsed to its end (every SOS, the DHT / DRI between the scans) and is inside the envelope when its
 // scan script is complete and orderly (include/lpi_hip.h); hd.scans then holds its scans.  Without the flag a SOF2 file is the host's at its SOF.
+// flags & LPI_JPEG_LAYOUTS: the wider frame rule of frame_in_envelope for SOF0 / SOF1 files.
 int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
     hd = Header();
     if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 0;
@@ -294,7 +331,10 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
         } else if (m == 0xE0) {
             if (sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) hd.jfif = true;
         } else if (m == 0xEE) {
-            if (sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) hd.adobe = true;
+            if (sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
+                hd.adobe = true;
+                hd.adobe_tf = s[11];
+            }
         } else if (m == 0xDA) {
             if (!hd.sof || sl < 1) return LPI_EINVAL;
             hd.ns = s[0];
@@ -333,7 +373,7 @@ int parse_headers(const uint8_t* d, long n, Header& hd, int flags = 0) {
             }
             hd.ent = p;
             const int ss = s[1 + 2 * hd.ns], se = s[2 + 2 * hd.ns], ahal = s[3 + 2 * hd.ns];
-            bool ok = frame_in_envelope(hd) && hd.ns == hd.nc && ss == 0 && se == 63 && ahal == 0;
+            bool ok = frame_in_envelope(hd, (flags & LPI_JPEG_LAYOUTS) != 0) && hd.ns == hd.nc && ss == 0 && se == 63 && ahal == 0;
             // libjpeg-turbo's get_sos looks a scan component up among the frame components whose slot in the SCAN's list is still empty: a
             // full scan in any order but the frame's ends in JERR_BAD_COMPONENT_ID, so such files are Pillow's (its exception)
             for (int i = 0; i < hd.ns; ++i) ok = ok && hd.sc[i] == i;
@@ -351,9 +391,9 @@ inline long align256(long v) { return (v + 255) / 256 * 256; }
 // A frame's geometry: the MCU's size in blocks (1 x 1 for grayscale, whatever its sampling factors say), the MCU grid, every component's share.
 struct Geom {
     int hm, vm, mcux, mcuy;
-    int H[3], V[3];
+    int H[4], V[4];
     explicit Geom(const Header& hd) {
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < 4; ++c) {
             H[c] = hd.nc == 1 ? 1 : hd.ch[c];
             V[c] = hd.nc == 1 ? 1 : hd.cv[c];
         }
@@ -397,18 +437,19 @@ EntRange place_range(long lo, long hi, long nmcu, int ri, long& at) {
 // What one decode call needs.  The workspace, every part rounded up to 256 bytes: the descriptors; every scan's unstuffed bytes and segment table,
 // in file order and scan order; every image's coefficient arrays, [zero_lo, zero_hi), which the caller clears before huff_kernel; every image's
 // sample planes; at ws_scans the PScan table (behind everything a batch of baseline files has: such a batch needs the same bytes with and without
-// the flag).  scans: sorted by launch round, rounds[r] of them run in round r.
+// the flag), at ws_exts the JExt table.  scans: sorted by launch round, rounds[r] of them run in round r.
 struct Plan {
     std::vector<JDesc> descs;
     std::vector<PScan> scans;
     std::vector<int> rounds;
-    long bytes = 0, zero_lo = 0, zero_hi = 0, ws_scans = 0;
+    std::vector<JExt> exts;         // of the four-component files, at ws_exts behind the PScan table
+    long bytes = 0, zero_lo = 0, zero_hi = 0, ws_scans = 0, ws_exts = 0;
 };
 
 // 0, or LPI_EINVAL (an argument, or a file with a structural error or outside the envelope of `flags`).  A progressive file gets a JDesc with
 // k = 0, which the baseline kernels pass over, and one PScan per scan.
 int plan(int flags, int B, const uint8_t* host, const long* offsets, Plan& pl) {
-    if (B < 1 || B > 65535 || !host || !offsets || (flags & ~LPI_JPEG_PROGRESSIVE)) return LPI_EINVAL;
+    if (B < 1 || B > 65535 || !host || !offsets || (flags & ~LPI_JPEG_FLAGS)) return LPI_EINVAL;
     pl.descs.assign(B, JDesc());
     std::vector<PScan> ps;              // in file order
     std::vector<int> level;
@@ -419,9 +460,11 @@ int plan(int flags, int B, const uint8_t* host, const long* offsets, Plan& pl) {
         if (parse_headers(host + offsets[i], offsets[i + 1] - offsets[i], hd, flags) != 0 || !hd.gpu) return LPI_EINVAL;
         const Geom g(hd);
         JDesc& j = pl.descs[i];
+        JExt ext = JExt();
         j.w = hd.w;
         j.h = hd.h;
         j.nc = hd.nc;
+        j.ct = color_transform(hd);
         j.hs = g.hm;
         j.vs = g.vm;
         j.mcux = g.mcux;
@@ -448,13 +491,13 @@ int plan(int flags, int B, const uint8_t* host, const long* offsets, Plan& pl) {
             for (int s = 0; s < hd.ns; ++s) {
                 const int f = hd.sc[s];
                 j.scomp[s] = f;
-                j.dc[s] = hd.hs[0][hd.std_[s]];
-                j.ac[s] = hd.hs[1][hd.sta[s]];
+                (s < 3 ? j.dc[s] : ext.dc) = hd.hs[0][hd.std_[s]];
+                (s < 3 ? j.ac[s] : ext.ac) = hd.hs[1][hd.sta[s]];
                 for (int y = 0; y < g.V[f]; ++y)
                     for (int x = 0; x < g.H[f]; ++x) {
-                        j.blk_comp[j.bpm] = s;
-                        j.blk_dx[j.bpm] = x;
-                        j.blk_dy[j.bpm] = y;
+                        j.blk_comp[j.bpm] = (uint8_t)s;
+                        j.blk_dx[j.bpm] = (uint8_t)x;
+                        j.blk_dy[j.bpm] = (uint8_t)y;
                         ++j.bpm;
                     }
             }
@@ -465,7 +508,7 @@ int plan(int flags, int B, const uint8_t* host, const long* offsets, Plan& pl) {
         for (int c = 0; c < hd.nc; ++c) {
             j.bw[c] = g.mcux * g.H[c];
             j.bh[c] = g.mcuy * g.V[c];
-            std::memcpy(j.qt[c], hd.qt[hd.ctq[c]], sizeof(j.qt[c]));
+            std::memcpy(c < 3 ? j.qt[c] : ext.qt, hd.qt[hd.ctq[c]], sizeof(ext.qt));
             j.ws_coef[c] = coef;
             coef += (long)j.bw[c] * j.bh[c] * 128;
             j.ws_plane[c] = plane;
@@ -473,16 +516,23 @@ int plan(int flags, int B, const uint8_t* host, const long* offsets, Plan& pl) {
         }
         coef = align256(coef);
         plane = align256(plane);
+        if (hd.nc == 4) {
+            j.ws_ext = (long)pl.exts.size() * (long)sizeof(JExt);
+            pl.exts.push_back(ext);
+        }
     }
     pl.zero_lo = at;
     pl.zero_hi = pl.zero_lo + coef;
     pl.ws_scans = pl.zero_hi + plane;
-    pl.bytes = pl.ws_scans + align256((long)ps.size() * (long)sizeof(PScan));
-    for (JDesc& j : pl.descs)
+    pl.ws_exts = pl.ws_scans + align256((long)ps.size() * (long)sizeof(PScan));
+    pl.bytes = pl.ws_exts + align256((long)pl.exts.size() * (long)sizeof(JExt));
+    for (JDesc& j : pl.descs) {
+        j.ws_ext += pl.ws_exts;
         for (int c = 0; c < j.nc; ++c) {
             j.ws_coef[c] += pl.zero_lo;
             j.ws_plane[c] += pl.zero_hi;
         }
+    }
     pl.rounds.assign(LPI_JPEG_MAX_SCANS + 1, 0);
     for (int r = 1; r <= LPI_JPEG_MAX_SCANS; ++r)
         for (size_t q = 0; q < ps.size(); ++q)
@@ -773,28 +823,41 @@ __device__ int decode_run(const BlkInfo* __restrict__ bi, int bpm, int mcux, con
     return nb;
 }
 
+// NS: the scan components the workgroup has tables and DC sums for.  huff_kernel<3> decodes the files of one or three components and passes over
+// those of four, huff_kernel<4> (launched only for a batch that has one) the reverse: the fourth component's tables and sums cost LDS that the
+// other files need not pay for.
+template <int NS>
 __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ descs, uint8_t* __restrict__ ws, int* __restrict__ status) {
-    __shared__ Lut luts[6];
+    __shared__ Lut luts[2 * NS];
     __shared__ BlkInfo s_bi[10];
     __shared__ int s_zz[64];
     __shared__ int s_ep[HT], s_ez[HT], s_eb[HT];        // exit state of each chunk
     __shared__ int s_np[HT], s_nz[HT], s_nb[HT];        // entry state of each chunk
-    __shared__ int s_cnt[HT], s_dc[HT][3];              // blocks and DC sums from entry to exit; after the scan: those of the chunks before
+    __shared__ int s_cnt[HT], s_dc[HT][NS];              // blocks and DC sums from entry to exit; after the scan: those of the chunks before
     __shared__ int s_need[HT];
     __shared__ int s_any, s_flags;
     const JDesc& d = descs[blockIdx.x];
     const int t = threadIdx.x;
     if (d.k == 0) return;                        // a progressive file: pscan_kernel's
+    if ((d.nc == 4) != (NS == 4)) return;        // the other instantiation's
     if (status[blockIdx.x] != 0) return;         // restart markers out of order: the segment table is not valid (uniform: before any barrier)
     const uint8_t* un = ws + d.ent.ws_unst;
     const int* seg = reinterpret_cast<const int*>(ws + d.ent.ws_seg);
     const int ns = d.nc, bpm = d.bpm, mcux = d.mcux;
 
     // tables
-    if (t < 2 * ns) lut_codes(t < ns ? d.dc[t] : d.ac[t - ns], luts[t < ns ? t : 3 + t - ns]);
+    if (t < 2 * ns) {
+        const int sc = t < ns ? t : t - ns;
+        const HuffSpec* hs = t < ns ? &d.dc[sc < 3 ? sc : 0] : &d.ac[sc < 3 ? sc : 0];
+        if (NS == 4 && sc == 3) {
+            const JExt* x = reinterpret_cast<const JExt*>(ws + d.ws_ext);
+            hs = t < ns ? &x->dc : &x->ac;
+        }
+        lut_codes(*hs, luts[t < ns ? t : NS + t - ns]);
+    }
     if (t < bpm) {
         const int sc = d.blk_comp[t], f = d.scomp[sc];
-        const bool luma = d.nc == 3 && f == 0;
+        const bool luma = d.nc > 1 && f == 0;
         s_bi[t] = BlkInfo{sc, d.blk_dx[t], d.blk_dy[t], luma ? d.hs : 1, luma ? d.vs : 1, d.bw[f], d.ws_coef[f]};
     }
     if (t < 64) s_zz[t] = kZigzag[t];
@@ -802,12 +865,12 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
     __syncthreads();
     for (int q = t; q < 2 * ns * (1 << LUT_BITS); q += HT) {
         const int tb = q >> LUT_BITS, e = q & ((1 << LUT_BITS) - 1);
-        Lut& L = luts[tb < ns ? tb : 3 + tb - ns];
+        Lut& L = luts[tb < ns ? tb : NS + tb - ns];
         L.lut[e] = lut_entry(L, e);
     }
     __syncthreads();
     const Lut* dl = luts;
-    const Lut* al = luts + 3;
+    const Lut* al = luts + NS;
     int flags = 0;
     const int k = d.k;
     const long nmcu = (long)mcux * d.mcuy;
@@ -822,7 +885,7 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
             DecState st{s0 * 8, 0, 0};
             const long m0 = (long)s * d.ent.ri, m1 = m0 + d.ent.ri < nmcu ? m0 + d.ent.ri : nmcu;
             const long want = (m1 - m0) * bpm;
-            int dcs[3] = {0, 0, 0}, pred[3] = {0, 0, 0}, f = 0;
+            int dcs[NS] = {}, pred[NS] = {}, f = 0;
             const int nb = decode_run(s_bi, bpm, mcux, s_zz, dl, al, rd, st, -1, (int)want, dcs, &f, ws, m0 * bpm, m1 * bpm, pred);
             flags |= f;
             if (nb != want || st.p > rd.E) flags |= ST_EOD;
@@ -833,7 +896,8 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
         const bool mine = t < nch;
         int c0 = 0, c1 = 0, E = 0;
         s_cnt[t] = 0;
-        s_dc[t][0] = s_dc[t][1] = s_dc[t][2] = 0;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) s_dc[t][c] = 0;
         if (mine) {
             const int s0 = s ? seg[s - 1] : 0, s1 = seg[s];
             const int len = s1 > s0 ? s1 - s0 : 0;
@@ -856,12 +920,11 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
             if (mine && s_need[t] && j != k - 1) {
                 Reader rd{un, cap, E, -1000, 0};
                 DecState st{s_np[t], s_nz[t], s_nb[t]};
-                int dcs[3] = {0, 0, 0}, f = 0;
+                int dcs[NS] = {}, f = 0;
                 const int nb = decode_run(s_bi, bpm, mcux, s_zz, dl, al, rd, st, c1 * 8, 0x7fffffff, dcs, &f, nullptr, 0, 0, nullptr);
                 s_cnt[t] = nb;
-                s_dc[t][0] = dcs[0];
-                s_dc[t][1] = dcs[1];
-                s_dc[t][2] = dcs[2];
+#pragma unroll
+                for (int c = 0; c < NS; ++c) s_dc[t][c] = dcs[c];
                 if (st.p != s_ep[t] || st.z != s_ez[t] || st.b != s_eb[t]) {
                     s_ep[t] = st.p;
                     s_ez[t] = st.z;
@@ -888,34 +951,37 @@ __global__ __launch_bounds__(HT) void huff_kernel(const JDesc* __restrict__ desc
         if (!converged) flags |= ST_COUNT;
         // first block and DC predictors of every chunk: an exclusive scan of the block counts and DC sums over the chunks before it in its segment
         // (segmented Hillis-Steele: chunk t - o is in the same segment iff j >= o; the last chunk's own sums are 0 and nothing follows it)
-        const int own0 = s_cnt[t], own1 = s_dc[t][0], own2 = s_dc[t][1], own3 = s_dc[t][2];
+        const int own0 = s_cnt[t];
+        int own[NS];
+#pragma unroll
+        for (int c = 0; c < NS; ++c) own[c] = s_dc[t][c];
         for (int o = 1; o < HT; o <<= 1) {
             const bool take = mine && j >= o;
-            int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+            int a0 = 0, a[NS] = {};
             if (take) {
                 a0 = s_cnt[t - o];
-                a1 = s_dc[t - o][0];
-                a2 = s_dc[t - o][1];
-                a3 = s_dc[t - o][2];
+#pragma unroll
+                for (int c = 0; c < NS; ++c) a[c] = s_dc[t - o][c];
             }
             __syncthreads();
             if (take) {
                 s_cnt[t] += a0;
-                s_dc[t][0] += a1;
-                s_dc[t][1] += a2;
-                s_dc[t][2] += a3;
+#pragma unroll
+                for (int c = 0; c < NS; ++c) s_dc[t][c] += a[c];
             }
             __syncthreads();
         }
         // the final pass
         if (mine) {
             const long first = s_cnt[t] - own0;
-            int pred[3] = {s_dc[t][0] - own1, s_dc[t][1] - own2, s_dc[t][2] - own3};
+            int pred[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) pred[c] = s_dc[t][c] - own[c];
             const long m0 = (long)s * d.ent.ri, m1 = m0 + d.ent.ri < nmcu ? m0 + d.ent.ri : nmcu;
             const long want = (m1 - m0) * bpm;
             Reader rd{un, cap, E, -1000, 0};
             DecState st{s_np[t], s_nz[t], s_nb[t]};
-            int dcs[3] = {0, 0, 0}, f = 0;
+            int dcs[NS] = {}, f = 0;
             // every chunk stops at the segment's last block: the chunk that completes it must not have read past the segment's end, and the last
             // chunk must complete it (a chunk past the data's end may have counted blocks in the padding: its successors then have nothing left)
             const long left = want - first;
@@ -1207,7 +1273,7 @@ __global__ __launch_bounds__(64) void idct_kernel(const JDesc* __restrict__ desc
     }
     if (c >= d.nc) return;
     const int16_t* cf = reinterpret_cast<const int16_t*>(ws + d.ws_coef[c]) + i * 64;
-    const uint16_t* q = d.qt[c];
+    const uint16_t* q = c < 3 ? d.qt[c] : reinterpret_cast<const JExt*>(ws + d.ws_ext)->qt;
     int ws8[64];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {          // pass 1: column u
@@ -1238,9 +1304,17 @@ __global__ __launch_bounds__(64) void idct_kernel(const JDesc* __restrict__ desc
 
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// chroma sample (x, y) of the upsampled plane: jdsample.c h2v1 / h2v2 fancy (edges replicated at dw x dh), or plain replication for dw <= 2
+// sample (x, y) of the upsampled plane of a component behind the first (chroma, K): jdsample.c's fancy upsampling h2v1 / h2v2 (edges replicated at
+// dw x dh; plain replication for dw <= 2) and h1v2 (whatever dw is), plain replication for 4x1 and 1x4
 __device__ inline int chroma(const uint8_t* p, long pw, int x, int y, int hs, int vs, int dw, int dh) {
-    if (hs == 1) return p[(long)y * pw + x];
+    if (hs == 1) {
+        if (vs == 1) return p[(long)y * pw + x];
+        if (vs == 4) return p[(long)(y >> 2) * pw + x];
+        const int ry = y >> 1;
+        const int ny = (y & 1) ? clampi(ry + 1, 0, dh - 1) : clampi(ry - 1, 0, dh - 1);
+        return (3 * p[(long)ry * pw + x] + p[(long)ny * pw + x] + ((y & 1) ? 2 : 1)) >> 2;
+    }
+    if (hs == 4) return p[(long)y * pw + (x >> 2)];
     const int i = x >> 1;
     const int ry = vs == 2 ? y >> 1 : y;
     if (dw <= 2) return p[(long)ry * pw + i];
@@ -1256,6 +1330,12 @@ __device__ inline int chroma(const uint8_t* p, long pw, int x, int y, int hs, in
     return (x & 1) ? (3 * cs + cn + 7) >> 4 : (3 * cs + cn + 8) >> 4;
 }
 
+// Pillow's MULDIV255: a * b / 255, rounded
+__device__ inline int muldiv255(int a, int b) {
+    const int t = a * b + 128;
+    return ((t >> 8) + t) >> 8;
+}
+
 // grid (ceil(max w / 256), max h, B)
 __global__ __launch_bounds__(256) void color_kernel(const JDesc* __restrict__ descs, const uint8_t* __restrict__ ws, uint8_t* __restrict__ out) {
     const JDesc& d = descs[blockIdx.z];
@@ -1269,29 +1349,47 @@ __global__ __launch_bounds__(256) void color_kernel(const JDesc* __restrict__ de
         return;
     }
     const long pwc = (long)d.bw[1] * 8;
-    const int cb = chroma(ws + d.ws_plane[1], pwc, x, y, d.hs, d.vs, d.dw, d.dh) - 128;
-    const int cr = chroma(ws + d.ws_plane[2], pwc, x, y, d.hs, d.vs, d.dw, d.dh) - 128;
-    // jdcolor.c: FIX(1.40200) = 91881, FIX(1.77200) = 116130, FIX(0.71414) = 46802, FIX(0.34414) = 22554, ONE_HALF = 32768
-    const int r = Y + ((91881 * cr + 32768) >> 16);
-    const int g = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-    const int b = Y + ((116130 * cb + 32768) >> 16);
-    o[0] = (uint8_t)clampi(r, 0, 255);
-    o[1] = (uint8_t)clampi(g, 0, 255);
-    o[2] = (uint8_t)clampi(b, 0, 255);
+    const int c1 = chroma(ws + d.ws_plane[1], pwc, x, y, d.hs, d.vs, d.dw, d.dh);
+    const int c2 = chroma(ws + d.ws_plane[2], pwc, x, y, d.hs, d.vs, d.dw, d.dh);
+    int r = Y, g = c1, b = c2;          // CT_RGB: the planes as they are
+    if (d.ct == CT_YCC || d.ct == CT_YCCK) {
+        const int cb = c1 - 128, cr = c2 - 128;
+        // jdcolor.c: FIX(1.40200) = 91881, FIX(1.77200) = 116130, FIX(0.71414) = 46802, FIX(0.34414) = 22554, ONE_HALF = 32768
+        r = clampi(Y + ((91881 * cr + 32768) >> 16), 0, 255);
+        g = clampi(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0, 255);
+        b = clampi(Y + ((116130 * cb + 32768) >> 16), 0, 255);
+    }
+    if (d.nc == 4) {
+        // libjpeg's C, M, Y are the planes (CMYK) or 255 - R, 255 - G, 255 - B (YCCK), its K the fourth plane; Pillow inverts all four and
+        // convert("RGB") gives clip(nk - MULDIV255(c, nk)) with nk = 255 - k: in libjpeg's values, nk = K and c = 255 - C
+        const int k = chroma(ws + d.ws_plane[3], pwc, x, y, d.hs, d.vs, d.dw, d.dh);
+        if (d.ct == CT_CMYK) {
+            r = 255 - r;
+            g = 255 - g;
+            b = 255 - b;
+        }
+        r = clampi(k - muldiv255(r, k), 0, 255);
+        g = clampi(k - muldiv255(g, k), 0, 255);
+        b = clampi(k - muldiv255(b, k), 0, 255);
+    }
+    o[0] = (uint8_t)r;
+    o[1] = (uint8_t)g;
+    o[2] = (uint8_t)b;
 }
 
 }  // namespace
 
 extern "C" int lpi_jpeg_info_x(int flags, const void* data, long nbytes, long* info) {
-    if (!data || !info || nbytes < 0 || (flags & ~LPI_JPEG_PROGRESSIVE)) return LPI_EINVAL;
+    if (!data || !info || nbytes < 0 || (flags & ~LPI_JPEG_FLAGS)) return LPI_EINVAL;
     Header hd;
     if (parse_headers(static_cast<const uint8_t*>(data), nbytes, hd, flags) != 0) return LPI_EINVAL;
     info[0] = hd.gpu ? 1 : 0;
     info[1] = hd.w;
     info[2] = hd.h;
     info[3] = hd.nc;
-    info[4] = hd.nc == 3 ? hd.ch[0] : 1;
-    info[5] = hd.nc == 3 ? hd.cv[0] : 1;
+    const bool sampled = hd.nc == 3 || (hd.nc == 4 && (flags & LPI_JPEG_LAYOUTS));
+    info[4] = sampled ? hd.ch[0] : 1;
+    info[5] = sampled ? hd.cv[0] : 1;
     info[6] = hd.ri;
     info[7] = hd.ent;
     info[8] = hd.prog ? 1 : 0;
@@ -1348,14 +1446,22 @@ extern "C" int lpi_jpeg_decode_u8_x(int flags, int B, const void* host, const lo
         e = hipMemcpyAsync(static_cast<char*>(ws) + pl.ws_scans, scans.data(), scans.size() * sizeof(PScan), hipMemcpyHostToDevice, s);
         if (e != hipSuccess) return (int)e;
     }
+    if (!pl.exts.empty()) {
+        e = hipMemcpyAsync(static_cast<char*>(ws) + pl.ws_exts, pl.exts.data(), pl.exts.size() * sizeof(JExt), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return (int)e;
+    }
     e = hipMemsetAsync(static_cast<char*>(ws) + pl.zero_lo, 0, (size_t)(pl.zero_hi - pl.zero_lo), s);
     if (e != hipSuccess) return (int)e;
     const JDesc* dd = static_cast<const JDesc*>(ws);
     uint8_t* w8 = static_cast<uint8_t*>(ws);
     LPI_LAUNCH(unstuff_kernel, dim3(B), dim3(NT), 0, s, dd, (const uint8_t*)src, w8, status);
     LPI_CHECK_LAST();
-    LPI_LAUNCH(huff_kernel, dim3(B), dim3(HT), 0, s, dd, w8, status);
+    LPI_LAUNCH(huff_kernel<3>, dim3(B), dim3(HT), 0, s, dd, w8, status);
     LPI_CHECK_LAST();
+    if (!pl.exts.empty()) {
+        LPI_LAUNCH(huff_kernel<4>, dim3(B), dim3(HT), 0, s, dd, w8, status);
+        LPI_CHECK_LAST();
+    }
     if (!scans.empty()) {
         // progressive files: their scans' bytes unstuffed, then one launch per round of scans that may run side by side
         const PScan* ps = reinterpret_cast<const PScan*>(w8 + pl.ws_scans);

@@ -116,10 +116,16 @@ def resample_decoded(batch, size=None, device="cuda", stream=None, threads=8, fi
 JPEG_INFO = 8       # int64 fields lpi_jpeg_info fills (include/lpi_hip.h LPI_JPEG_INFO)
 JPEG_INFO_X = 10    # ... and lpi_jpeg_info_x (LPI_JPEG_INFO_X: + {parsed as progressive, scans})
 JPEG_PROGRESSIVE = 1        # LPI_JPEG_PROGRESSIVE: progressive files with a complete scan script are inside the envelope
+JPEG_LAYOUTS = 4            # LPI_JPEG_LAYOUTS: baseline 4:4:0, 4:1:1, 1x4, RGB, CMYK and YCCK files are inside the envelope
 
 
-def _flags(progressive):
-    return JPEG_PROGRESSIVE if progressive else 0       # the flags word of the lpi_jpeg_*_x calls
+def _flags(progressive=False, layouts=False):
+    """The flags word of the lpi_jpeg_*_x calls: the public keywords are booleans, everything below them carries this word."""
+    return (JPEG_PROGRESSIVE if progressive else 0) | (JPEG_LAYOUTS if layouts else 0)
+
+
+def _batch_flags(batch):
+    return _flags(getattr(batch, "progressive", False), getattr(batch, "layouts", False))
 
 
 def _u8(data):
@@ -129,14 +135,14 @@ def _u8(data):
     return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
 
 
-def jpeg_info(data, progressive=False):
+def jpeg_info(data, progressive=False, layouts=False):
     """(gpu, width, height) of one file from its headers (lpi_jpeg_info_x: host only, it never touches the GPU, so forked loader workers may call it):
     gpu = the file is inside lpi_jpeg_decode_u8's envelope or, with progressive=True, inside that of LPI_JPEG_PROGRESSIVE (the parser then walks a
-    progressive file to its end).  None when the headers have a structural error; (False, 0, 0) for a file that is not a JPEG.  The envelope is
+    progressive file to its end), with layouts=True inside that of LPI_JPEG_LAYOUTS (baseline 4:4:0, 4:1:1, 1x4, RGB, CMYK, YCCK).  None when the headers have a structural error; (False, 0, 0) for a file that is not a JPEG.  The envelope is
     decided there and only there."""
     a = _u8(data)
     info = (ctypes.c_long * JPEG_INFO_X)()
-    rc = _lib.load().lpi_jpeg_info_x(_flags(progressive), a.ctypes.data if a.size else None, int(a.size), ctypes.addressof(info))
+    rc = _lib.load().lpi_jpeg_info_x(_flags(progressive, layouts), a.ctypes.data if a.size else None, int(a.size), ctypes.addressof(info))
     if rc != 0:
         return None
     return bool(info[0]), int(info[1]), int(info[2])
@@ -151,24 +157,32 @@ def pil_decode(data):
         return torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8))
 
 
-def jpeg_workspace_bytes(host, offsets, progressive=False):
+def jpeg_workspace_bytes(host, offsets, progressive=False, layouts=False):
     """Device workspace lpi_jpeg_decode_u8_x needs for the files packed in host (uint8 numpy) at offsets ([n + 1] int64); LpiError when a file is
-    outside the envelope (progressive: that of LPI_JPEG_PROGRESSIVE) or has a structural error."""
+    outside the envelope (progressive: that of LPI_JPEG_PROGRESSIVE; layouts: that of LPI_JPEG_LAYOUTS) or has a structural error."""
+    return _workspace_x(_flags(progressive, layouts), host, offsets)
+
+
+def _workspace_x(flags, host, offsets):
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     out = ctypes.c_long(0)
-    rc = _lib.load().lpi_jpeg_decode_workspace_x(_flags(progressive), int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
+    rc = _lib.load().lpi_jpeg_decode_workspace_x(int(flags), int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
                                                  ctypes.addressof(out))
     if rc != 0:
         raise _lib.LpiError(f"lpi_jpeg_decode_workspace_x failed with code {rc} (a file outside the envelope or with a broken header)")
     return int(out.value)
 
 
-def jpeg_launch(host, offsets, src, out_off, out, status, ws, stream, progressive=False):
+def jpeg_launch(host, offsets, src, out_off, out, status, ws, stream, progressive=False, layouts=False):
     """lpi_jpeg_decode_u8_x on `stream`: the files of host / src (its device copy) at offsets into out at out_off (host int64), statuses into status;
-    progressive: with LPI_JPEG_PROGRESSIVE (flags = 0 is lpi_jpeg_decode_u8)."""
+    progressive: with LPI_JPEG_PROGRESSIVE, layouts: with LPI_JPEG_LAYOUTS (neither: flags = 0, which is lpi_jpeg_decode_u8)."""
+    _launch_x(_flags(progressive, layouts), host, offsets, src, out_off, out, status, ws, stream)
+
+
+def _launch_x(flags, host, offsets, src, out_off, out, status, ws, stream):
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     out_off = np.ascontiguousarray(out_off, dtype=np.int64)
-    rc = _lib.load().lpi_jpeg_decode_u8_x(_flags(progressive), int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
+    rc = _lib.load().lpi_jpeg_decode_u8_x(int(flags), int(offsets.size - 1), host.ctypes.data, offsets.ctypes.data,
                                           src.data_ptr(), int(src.numel()), out_off.ctypes.data, out.data_ptr(), int(out.numel()), status.data_ptr(),
                                           ws.data_ptr(), int(ws.numel()), stream.cuda_stream)
     if rc != 0:
@@ -224,10 +238,10 @@ def _issue_decode(batch, device, stream, bufs=None):
             sub = host[lo:hi]
             src = bufs("src", hi - lo, "device")[:hi - lo]
             src.copy_(data[lo:hi], non_blocking=True)
-            progressive = bool(getattr(batch, "progressive", False))
-            ws_bytes = jpeg_workspace_bytes(sub, sub_off, progressive)
+            flags = _batch_flags(batch)
+            ws_bytes = _workspace_x(flags, sub, sub_off)
             ws = bufs("ws", ws_bytes, "device")[:ws_bytes]
-            jpeg_launch(sub, sub_off, src, d.offsets[gpu], d.pixels, status_dev, ws, stream, progressive)
+            _launch_x(flags, sub, sub_off, src, d.offsets[gpu], d.pixels, status_dev, ws, stream)
             d.status[:len(gpu)].copy_(status_dev[:len(gpu)], non_blocking=True)
         d.ready = torch.cuda.Event()
         d.ready.record(stream)

@@ -132,7 +132,7 @@ class BatchPipeline:
         host = self._dec_buffer(slot, "host", n, pin_memory=True)
         host[:n].copy_(images.data)
         return EncodedBatch(host[:n], images.offsets, images.params, images.wh, images.size, images.fallback, filter=images.filter,
-                            progressive=images.progressive)
+                            progressive=images.progressive, layouts=images.layouts)
 
     def _issue_encoded(self, slot, images):
         """Device half, on the side stream: H2D of the file bytes, lpi_jpeg_decode_u8, lpi_image_resample_u8 into the uint8 output slot.  The statuses are

@@ -87,10 +87,17 @@ def _check_jpeg_progressive(args):
         raise ValueError(f"jpeg_progressive widens the envelope of pixel_format='jpeg': it cannot go with pixel_format={args.get('pixel_format', 'f32')!r}")
 
 
+def _check_jpeg_layouts(args):
+    """jpeg_layouts widens the envelope of pixel_format = 'jpeg' (LPI_JPEG_LAYOUTS): with any other pixel format it is a ValueError."""
+    if args.get('jpeg_layouts') and args.get('pixel_format', 'f32') != 'jpeg':
+        raise ValueError(f"jpeg_layouts widens the envelope of pixel_format='jpeg': it cannot go with pixel_format={args.get('pixel_format', 'f32')!r}")
+
+
 class SPrompts(BaseLearner):
     def __init__(self, args):
         super().__init__(args)
         _check_jpeg_progressive(args)           # a conflicting key fails here, beside the preprocessing keys, not at the first task
+        _check_jpeg_layouts(args)
         if args["net_type"] == "slip":
             self._network = SliNet(args)
         else:
@@ -119,6 +126,7 @@ class SPrompts(BaseLearner):
 
     def _datasets(self, i):
         _check_jpeg_progressive(self.args)
+        _check_jpeg_layouts(self.args)
         impl = self.args.get("dataset_impl")
         if impl is None:
             impl = "coco" if os.path.isdir(str(self.args.get("image_root", ""))) else "synthetic"
@@ -141,6 +149,9 @@ class SPrompts(BaseLearner):
             # (LPI_JPEG_PROGRESSIVE); the datasets refuse the key with any other pixel format
             if 'jpeg_progressive' in self.args:
                 kw['jpeg_progressive'] = bool(self.args['jpeg_progressive'])
+            # jpeg_layouts = true: the same for baseline 4:4:0, 4:1:1, 1x4, RGB, CMYK and YCCK files (LPI_JPEG_LAYOUTS)
+            if 'jpeg_layouts' in self.args:
+                kw['jpeg_layouts'] = bool(self.args['jpeg_layouts'])
             return (Coco(image_root=self.args['image_root'], ann_file=self.args['annotation_train_root'], tasks=[i], pixel_format=pf, **kw),
                     CocoEval(image_root=self.args['image_root'], ann_file=self.args['annotation_val_root'], tasks=np.arange(0, i + 1),
                              eval_transform=self.args.get('eval_transform', 'center'), pixel_format=pf, **kw, **ekw))
@@ -148,6 +159,8 @@ class SPrompts(BaseLearner):
             raise ValueError(f"unknown dataset_impl {impl!r} (coco | synthetic)")
         if self.args.get('jpeg_progressive'):
             raise ValueError("jpeg_progressive widens the envelope of pixel_format='jpeg', which needs image files: the synthetic datasets have none")
+        if self.args.get('jpeg_layouts'):
+            raise ValueError("jpeg_layouts widens the envelope of pixel_format='jpeg', which needs image files: the synthetic datasets have none")
         res = self._network.clip_cfg.image_resolution
         n_train = int(self.args.get("synthetic_train_size", 4 * self.batch_size))
         n_eval = int(self.args.get("synthetic_eval_images_per_task", 16))

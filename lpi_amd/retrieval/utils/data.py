@@ -115,9 +115,9 @@ def _rebuild(cls, filter, *args):
     return cls(*args, filter=filter)
 
 
-def _rebuild_encoded(cls, filter, progressive, *args):
-    """Unpickles EncodedImage / EncodedBatch: filter and progressive are keyword arguments."""
-    return cls(*args, filter=filter, progressive=progressive)
+def _rebuild_encoded(cls, filter, progressive, layouts, *args):
+    """Unpickles EncodedImage / EncodedBatch: filter, progressive and layouts are keyword arguments."""
+    return cls(*args, filter=filter, progressive=progressive, layouts=layouts)
 
 
 class DecodedImage:
@@ -178,11 +178,12 @@ class EncodedImage:
     DESCRIPTOR_FIELDS tuple of train_crop_params / test_crop_params of the frame size), the output size S (``size``), the frame size (``wh``) and
     the resampling filter (``filter``: 'bilinear' | 'bicubic' | 'box').
     The file is inside lpi_jpeg_decode_u8's envelope (lpi_amd.imageops.jpeg_info) or, with ``progressive`` = True, inside the wider one of
-    LPI_JPEG_PROGRESSIVE (lpi_jpeg_decode_u8_x); lpi_amd.imageops.resample_encoded decodes and resamples it on the GPU."""
-    __slots__ = ("data", "params", "size", "wh", "filter", "progressive")
+    LPI_JPEG_PROGRESSIVE and, with ``layouts`` = True, of LPI_JPEG_LAYOUTS (lpi_jpeg_decode_u8_x); lpi_amd.imageops.resample_encoded decodes and
+    resamples it on the GPU."""
+    __slots__ = ("data", "params", "size", "wh", "filter", "progressive", "layouts")
 
-    def __init__(self, data, params, size, wh, *, filter="bilinear", progressive=False):
-        self.progressive = bool(progressive)
+    def __init__(self, data, params, size, wh, *, filter="bilinear", progressive=False, layouts=False):
+        self.progressive, self.layouts = bool(progressive), bool(layouts)
         if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 1:
             raise ValueError("EncodedImage.data must be a 1-D uint8 tensor (the file's bytes)")
         w, h = (int(v) for v in wh)
@@ -191,7 +192,7 @@ class EncodedImage:
         self.params = resample_descriptor(w, h, (x0, y0, x1, y1), (rw, rh), (ox, oy), flip, size)
 
     def __reduce__(self):
-        return (_rebuild_encoded, (EncodedImage, self.filter, self.progressive, self.data, self.params, self.size, self.wh))
+        return (_rebuild_encoded, (EncodedImage, self.filter, self.progressive, self.layouts, self.data, self.params, self.size, self.wh))
 
 
 class EncodedBatch:
@@ -199,12 +200,12 @@ class EncodedBatch:
     offsets[i+1]], empty for a host-decoded item), ``offsets`` [B+1] int64, ``params`` the [B, 9] int64 descriptor table, ``wh`` [B, 2] int64 frame
     sizes, ``size`` S, ``fallback`` {batch index: HWC uint8 pixels} of the items Pillow decoded in the worker (files outside the envelope),
     ``filter`` the one resampling filter of the batch, ``progressive`` whether its files were admitted by the envelope of LPI_JPEG_PROGRESSIVE (the
-    decode then goes through lpi_jpeg_decode_u8_x with that flag)."""
-    __slots__ = ("data", "offsets", "params", "wh", "size", "fallback", "filter", "progressive")
+    decode then goes through lpi_jpeg_decode_u8_x with that flag), ``layouts`` the same for LPI_JPEG_LAYOUTS."""
+    __slots__ = ("data", "offsets", "params", "wh", "size", "fallback", "filter", "progressive", "layouts")
 
-    def __init__(self, data, offsets, params, wh, size, fallback=None, *, filter="bilinear", progressive=False):
+    def __init__(self, data, offsets, params, wh, size, fallback=None, *, filter="bilinear", progressive=False, layouts=False):
         self.data, self.offsets, self.params, self.wh, self.size = data, offsets, params, wh, int(size)
-        self.progressive = bool(progressive)
+        self.progressive, self.layouts = bool(progressive), bool(layouts)
         self.fallback = dict(fallback or {})
         self.filter = _check_filter(filter)
 
@@ -216,11 +217,12 @@ class EncodedBatch:
         return self.data[int(self.offsets[i]):int(self.offsets[i + 1])]
 
     def __reduce__(self):
-        return (_rebuild_encoded, (EncodedBatch, self.filter, self.progressive, self.data, self.offsets, self.params, self.wh, self.size, self.fallback))
+        return (_rebuild_encoded, (EncodedBatch, self.filter, self.progressive, self.layouts, self.data, self.offsets, self.params, self.wh, self.size,
+                                   self.fallback))
 
     def pin_memory(self, device=None):
         return EncodedBatch(self.data.pin_memory(), self.offsets, self.params, self.wh, self.size, {i: p.pin_memory() for i, p in self.fallback.items()},
-                            filter=self.filter, progressive=self.progressive)
+                            filter=self.filter, progressive=self.progressive, layouts=self.layouts)
 
 
 def collate_encoded(batch):
@@ -248,8 +250,11 @@ def collate_encoded(batch):
             wh.append((int(d.pixels.shape[1]), int(d.pixels.shape[0])))
     params = torch.tensor([d.params for d in imgs], dtype=torch.int64).view(len(imgs), len(DESCRIPTOR_FIELDS))
     progressive = any(isinstance(d, EncodedImage) and d.progressive for d in imgs)
+    layouts = {d.layouts for d in imgs if isinstance(d, EncodedImage)}
+    if len(layouts) > 1:
+        raise ValueError("collate_encoded: the items of one batch must share the layouts setting (the envelope their files were admitted by)")
     return [EncodedBatch(data, offsets, params, torch.tensor(wh, dtype=torch.int64).view(len(imgs), 2), size, fallback, filter=filter,
-                         progressive=progressive)] + \
+                         progressive=progressive, layouts=True in layouts)] + \
         [default_collate(list(c)) for c in cols[1:]]
 
 
@@ -469,16 +474,17 @@ def decoded_transform(form, size=224, resize=256, interpolation="bilinear"):
     return transform
 
 
-def encoded_transform(form, size=224, resize=256, interpolation="bilinear", progressive=False):
+def encoded_transform(form, size=224, resize=256, interpolation="bilinear", progressive=False, layouts=False):
     """The transform of pixel_format='jpeg': file bytes -> EncodedImage (inside the envelope; lpi_jpeg_info gives the frame size, host only) or, for
     any other file, Pillow's decode as a DecodedImage, right here (decoded_transform).  The crop draws are decoded_transform's, in its order.
-    progressive: the envelope of LPI_JPEG_PROGRESSIVE (progressive files with a complete scan script are the GPU's too)."""
+    progressive: the envelope of LPI_JPEG_PROGRESSIVE (progressive files with a complete scan script are the GPU's too); layouts: that of
+    LPI_JPEG_LAYOUTS (baseline 4:4:0, 4:1:1, 1x4, RGB, CMYK and YCCK files are the GPU's too)."""
     fallback = decoded_transform(form, size, resize, interpolation)
-    progressive = bool(progressive)
+    progressive, layouts = bool(progressive), bool(layouts)
 
     def transform(data):
         from lpi_amd.imageops import jpeg_info
-        info = jpeg_info(data, progressive=progressive)
+        info = jpeg_info(data, progressive=progressive, layouts=layouts)
         if info is None or not info[0]:
             import io
             Image = _pil()
@@ -486,7 +492,8 @@ def encoded_transform(form, size=224, resize=256, interpolation="bilinear", prog
                 return fallback(im.convert("RGB"))
         _, w, h = info
         desc = train_crop_params(w, h, size) if form == "train" else test_crop_params(w, h, resize, size)
-        return EncodedImage(torch.frombuffer(bytearray(data), dtype=torch.uint8), desc, size, (w, h), filter=interpolation, progressive=progressive)
+        return EncodedImage(torch.frombuffer(bytearray(data), dtype=torch.uint8), desc, size, (w, h), filter=interpolation, progressive=progressive,
+                            layouts=layouts)
     return transform
 
 
@@ -494,6 +501,12 @@ def _check_jpeg_progressive(jpeg_progressive, pixel_format):
     if jpeg_progressive and pixel_format != "jpeg":
         raise ValueError(f"jpeg_progressive widens the envelope of pixel_format='jpeg': it cannot go with pixel_format={pixel_format!r}")
     return bool(jpeg_progressive)
+
+
+def _check_jpeg_layouts(jpeg_layouts, pixel_format):
+    if jpeg_layouts and pixel_format != "jpeg":
+        raise ValueError(f"jpeg_layouts widens the envelope of pixel_format='jpeg': it cannot go with pixel_format={pixel_format!r}")
+    return bool(jpeg_layouts)
 
 
 PREPROCESS = ("reference", "clip")
@@ -551,10 +564,11 @@ class Coco(Dataset):
     """Training pairs of the given tasks (utils/data.py:308-382): item = (image, prompt + pre_caption(caption), 0, task)."""
 
     def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, prompt='', tasks=(0,), replay_list=(), pixel_format="f32",
-                 size=224, interpolation="bilinear", normalize="imagenet", jpeg_progressive=False):
+                 size=224, interpolation="bilinear", normalize="imagenet", jpeg_progressive=False, jpeg_layouts=False):
         _pil()
         _check_pixel_format(pixel_format)
         self.jpeg_progressive = _check_jpeg_progressive(jpeg_progressive, pixel_format)
+        self.jpeg_layouts = _check_jpeg_layouts(jpeg_layouts, pixel_format)
         _check_filter(interpolation)
         norm_stats(normalize)
         # interpolation / normalize: of the default transforms (an explicit `transform` wins); 'u8', 'decoded' and 'jpeg' items are normalised on the
@@ -568,7 +582,7 @@ class Coco(Dataset):
             transform = decoded_transform("train", size, interpolation=interpolation)
         self._encoded = transform is None and pixel_format == "jpeg"     # the transform then takes the file's bytes
         if self._encoded:
-            transform = encoded_transform("train", size, interpolation=interpolation, progressive=self.jpeg_progressive)
+            transform = encoded_transform("train", size, interpolation=interpolation, progressive=self.jpeg_progressive, layouts=self.jpeg_layouts)
         self.pixel_format, self.interpolation, self.normalize = pixel_format, interpolation, normalize
         with open(ann_file, 'r') as f:
             records = json.load(f)
@@ -600,10 +614,11 @@ class CocoEval(Dataset):
     (utils/data.py:186-306; sprompt.py:433-548): text, text_cat, image, txt2img, img2txt; item = (image, image index, task)."""
 
     def __init__(self, transform=None, image_root=None, ann_file=None, max_words=30, tasks=(0,), eval_transform='center', pixel_format="f32",
-                 size=224, resize=256, interpolation="bilinear", normalize="imagenet", jpeg_progressive=False):
+                 size=224, resize=256, interpolation="bilinear", normalize="imagenet", jpeg_progressive=False, jpeg_layouts=False):
         _pil()
         _check_pixel_format(pixel_format)
         self.jpeg_progressive = _check_jpeg_progressive(jpeg_progressive, pixel_format)
+        self.jpeg_layouts = _check_jpeg_layouts(jpeg_layouts, pixel_format)
         _check_filter(interpolation)
         norm_stats(normalize)
         plain = (interpolation, normalize) == ("bilinear", "imagenet") and (size, resize) == (224, 256)
@@ -622,7 +637,8 @@ class CocoEval(Dataset):
             transform = decoded_transform("center" if eval_transform == 'center' else "train", size, resize, interpolation)
         self._encoded = transform is None and pixel_format == "jpeg" and eval_transform in ('center', 'reference')
         if self._encoded:
-            transform = encoded_transform("center" if eval_transform == 'center' else "train", size, resize, interpolation, self.jpeg_progressive)
+            transform = encoded_transform("center" if eval_transform == 'center' else "train", size, resize, interpolation, self.jpeg_progressive,
+                                          self.jpeg_layouts)
         self.pixel_format, self.interpolation, self.normalize = pixel_format, interpolation, normalize
         with open(ann_file, 'r') as f:
             records = json.load(f)
