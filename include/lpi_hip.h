@@ -700,7 +700,33 @@ int lpi_bpe_tokenize(void* handle, const char* const* texts, int n, int context_
 #define LPI_GEMM_K_256_TAIL 2   /* gemm256_tail_kernel: 256x256 tiles, short last round as halves */
 #define LPI_GEMM_K_256X128 3    /* gemm256x128_kernel                                             */
 #define LPI_GEMM_K_ROWS 4       /* gemm_rows_kernel: few-row GEMM, 32x32 tiles over the whole K   */
+#define LPI_GEMM_K_MX8 5        /* gemm_mx8_kernel: MX-FP8 operands, 128x128 tiles (lpi_gemm_nt_mx8) */
 int lpi_gemm_last_kernel(void);
+
+/* ---- MX-FP8 forward (csrc/gemm_mx8.hip, csrc/mx8_rows.hip): the four block GEMMs of the no-grad forwards on the block-scaled FP8 matrix instruction ----
+ * replaces (EngineOptions.mx8_forward, train=False only): models/clip/model.py:172-177 (ln_1 -> in_proj, out_proj, ln_2 -> c_fc -> QuickGELU -> c_proj).
+ * THE FORMAT.  Elements: OCP e4m3fn bytes (torch.float8_e4m3fn; not MI300X's fnuz), round to nearest even, subnormals kept.  Scales: one E8M0 byte
+ * (value 2^(byte - 127)) per 32 consecutive K elements, stored [rows, K/32] row-major with a leading dimension.  Block scale: for the block maximum amax
+ * the exponent is e = floor(log2 amax) - 8, raised by one if amax 2^-e > 448, clamped to [-127, 127]; byte = e + 127; element = y 2^-e rounded.  No
+ * element ever saturates (a deliberate departure from the OCP floor rule): |deq - y| <= max(2^-4 |y|, 2^-10 S) with S the block's scale.  An all-zero
+ * block is byte 0 and zero elements.  NaN / Inf inputs are out of contract.
+ * LPI_MX8 as lpi_gemm_nt_mx8's c_dtype: C is e4m3 bytes [M, ldc] and c_scales [M, ldcs >= N/32] receives the scales along N. */
+#define LPI_MX8 3
+/* 1 if lpi_gemm_nt_mx8 takes the shape (M, N, K positive multiples of 128), else 0.  Host only: no GPU call. */
+int lpi_gemm_mx8_ok(int M, int N, int K);
+/* C[M,N] = epi(alpha * A[M,K] . B[N,K]^T + bias) (+ residual), A / B e4m3 with scales a_scales [M, ldas] / b_scales [N, ldbs] (ld* multiples of 4, 4-byte
+ * aligned), f32 accumulation.  c_dtype LPI_F32 | LPI_BF16 | LPI_F16 | LPI_MX8.  Epilogues LPI_EPI_NONE and LPI_EPI_QUICKGELU (no aux); residual (LPI_EPI_NONE
+ * only) has C's type: fp16 with LPI_F16, f32 with LPI_F32 (LPI_ENOSYS with bf16, LPI_EINVAL with LPI_MX8).  bias f32 or NULL.  LPI_EINVAL before any launch
+ * for any other shape, a NULL scale pointer of an MX operand or output, or a misaligned argument.  Attributed to LPI_GEMM_K_MX8. */
+int lpi_gemm_nt_mx8(int c_dtype, int M, int N, int K, const void* A, int lda, const void* a_scales, int ldas, const void* B, int ldb,
+                    const void* b_scales, int ldbs, void* C, int ldc, void* c_scales, int ldcs, const float* bias, const void* residual, int ldr,
+                    int epilogue, float alpha, void* stream);
+/* rows of x (`x_dtype`: LPI_F32 | LPI_BF16 | LPI_F16, [rows, ldx]) -> q (e4m3 [rows, ldq]) + scales ([rows, lds >= K/32]); K a multiple of 32. */
+int lpi_mx8_quantize(int x_dtype, int rows, int K, const void* x, int ldx, void* q, int ldq, void* scales, int lds, void* stream);
+/* LayerNorm (f32 two-sweep statistics in registers, eps 1e-5, affine in f32) of the rows of the residual stream x (`x_dtype`: LPI_F16 | LPI_F32) written
+ * straight as MX-FP8: LN(x) never exists in a 2-byte type.  d a multiple of 32, <= 1024.  mean / rstd (f32 [rows]) are optional outputs (NULL: not written). */
+int lpi_layernorm_mx8_fwd(int x_dtype, int rows, int d, const void* x, int ldx, const float* gamma, const float* beta, void* q, int ldq,
+                          void* scales, int lds, float* mean, float* rstd, void* stream);
 
 
 #ifdef __cplusplus

@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LPI_LIB") or os.path.join(_HERE, "csrc", "liblpi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
+MX8 = 3      # lpi_gemm_nt_mx8's c_dtype for an MX-FP8 output (e4m3 bytes + E8M0 scales along N)
+GEMM_K_MX8 = 5      # LPI_GEMM_K_MX8 of lpi_gemm_last_kernel
 EPI_NONE, EPI_QUICKGELU, EPI_DQUICKGELU, EPI_LN, EPI_LN_QUICKGELU, EPI_RES_ROWSTATS = 0, 1, 2, 3, 4, 5
 
 
@@ -45,6 +47,11 @@ SIGNATURES = {
     "lpi_ln_stats_finalize_pair": [_I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P, _F, _P],
     "lpi_gemm_nt_rows": [_I, _I, _I, _F, _I, _P, _P],
     "lpi_gemm_nt_rows_supported": [_I, _I, _I, _I],
+    # MX-FP8 forward (gemm_mx8.hip, mx8_rows.hip)
+    "lpi_gemm_mx8_ok": [_I, _I, _I],
+    "lpi_gemm_nt_mx8": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _F, _P],
+    "lpi_mx8_quantize": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
+    "lpi_layernorm_mx8_fwd": [_I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
     "lpi_layernorm_fwd": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],
     "lpi_layernorm_bwd": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P],
     "lpi_layernorm_fwd_pair": [_I, _I, _P, _P],
@@ -151,7 +158,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_bpe_create": c_void_p, "lpi_bpe_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 609
+EXPECTED_ABI = 610
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -77,7 +77,12 @@ class EngineOptions:
         98.4 -> 96.5 us, step 22.27 ms both: profiles/r06_experiments.md) although the kernels alone gain 7 % — kept as the tested proof of that.
     pixel_norm: the ToTensor + Normalize statistics lpi_patchify_u8 applies to uint8 pixels ('u8', 'decoded' and 'jpeg' items): 'imagenet' (the
         reference's retrieval loader), 'clip' (CLIP's own, models/clip/clip.py:77 of the reference) or a (mean, std) pair of three floats each.  f32
-        images arrive normalised by the loader and are not touched."""
+        images arrive normalised by the loader and are not touched.
+    mx8_forward: the four GEMMs (in_proj, out_proj, c_fc, c_proj) of every FULL block take MX-FP8 operands (OCP e4m3 elements, one E8M0 scale per 32
+        elements along K: include/lpi_hip.h) in the train=False forwards of both towers — the un-prompted encodes of clustering and the two passes of
+        retrieval evaluation, which never need a gradient.  LayerNorm writes the MX operand directly (lpi_layernorm_mx8_fwd), c_fc's QuickGELU epilogue
+        writes c_proj's; attention, the fp16 residual stream, the patch embedding, the pooled last block and the heads are what the 2-byte mode runs.
+        train=True forwards and every backward are untouched.  2-byte modes only (ValueError with dtype 'f32'); +1 byte per parameter of the block matrices."""
     residual_f16: bool = True
     ln_fold: int = 2
     rowstats: int = 2
@@ -87,6 +92,7 @@ class EngineOptions:
     l0_prompt_rows: bool = True
     qkv_grouped: bool = False
     pixel_norm: object = "imagenet"
+    mx8_forward: bool = False
 
     def __post_init__(self):
         if self.ln_fold not in (0, 1, 2) or self.rowstats not in (0, 1, 2):
@@ -102,6 +108,11 @@ class EngineOptions:
             object.__setattr__(self, "pixel_norm", pair)
         elif self.pixel_norm not in PIXEL_NORMS:
             raise ValueError(f"pixel_norm is 'imagenet', 'clip' or a (mean, std) pair, not {self.pixel_norm!r}")
+
+    def check_dtype(self, dtype: str):
+        """Refusals that depend on the engine's operand type; raised before anything touches the GPU."""
+        if self.mx8_forward and _DT[dtype] == F32:
+            raise ValueError("mx8_forward is an option of the 2-byte modes ('bf16', 'f16'): the f32 parity mode has no reduced-precision path")
 
     def pixel_stats(self):
         """(mean, std) of pixel_norm; (None, None) for 'imagenet' (make_pixel_lut's defaults)."""
@@ -140,7 +151,7 @@ def _require_gpu(device):
 class Linear:
     """A frozen nn.Linear prepared for the NT GEMM: W [out,in] and W^T [in,out] in the operand dtype, f32 bias."""
 
-    def __init__(self, w: torch.Tensor, b: Optional[torch.Tensor], dt: int, device, k_pad: Optional[int] = None):
+    def __init__(self, w: torch.Tensor, b: Optional[torch.Tensor], dt: int, device, k_pad: Optional[int] = None, mx8: bool = False):
         w = w.to(device=device, dtype=torch.float32)
         if k_pad is not None and k_pad != w.shape[1]:
             w = torch.nn.functional.pad(w, (0, k_pad - w.shape[1]))
@@ -148,6 +159,22 @@ class Linear:
         self.w = w.to(_TORCH_DT[dt]).contiguous()                                         # forward operand
         self.wt = w.t().contiguous().to(_TORCH_DT[_grad_dtype(dt)]).contiguous()          # dgrad operand (W^T, K-contiguous)
         self.b = None if b is None else b.to(device=device, dtype=torch.float32).contiguous()
+        if mx8:      # EngineOptions.mx8_forward: the MX-FP8 copy of the forward operand, quantised on the device from the f32 weight
+            if self.out_features % 128 or self.in_features % 128:
+                raise ValueError(f"mx8_forward: a [{self.out_features}, {self.in_features}] weight is not whole 128 x 128 tiles")
+            self.w8, self.w8s = mx8_quantize(w.contiguous())
+
+
+def mx8_quantize(x: torch.Tensor, q: Optional[torch.Tensor] = None, sc: Optional[torch.Tensor] = None, rows: Optional[int] = None):
+    """Rows of x ([R, K] f32 / bf16 / f16 on the device, K a multiple of 32) as MX-FP8 (include/lpi_hip.h): -> (e4m3 bytes [R, K], E8M0 scale bytes [R, K/32]),
+    uint8 tensors (view(torch.float8_e4m3fn) gives the elements).  q / sc: write into these; rows: only the first `rows` rows."""
+    R, K = x.shape
+    if q is None:
+        q = torch.empty(R, K, dtype=torch.uint8, device=x.device)
+    if sc is None:
+        sc = torch.empty(R, K // 32, dtype=torch.uint8, device=x.device)
+    call("lpi_mx8_quantize", _cdt(x), R if rows is None else rows, K, x, x.stride(0), q, q.stride(0), sc, sc.stride(0), _stream())
+    return q, sc
 
 
 class LnLinear:
@@ -354,6 +381,30 @@ class PoolAttnReq(Req):
                  q["ldctx"], q["lse"], q["causal"], _stream())
 
 
+class Mx8Req(Req):
+    """A launch of the MX-FP8 forward (EngineOptions.mx8_forward): `name` = lpi_layernorm_mx8_fwd | lpi_mx8_quantize | lpi_gemm_nt_mx8, args = its arguments
+    before the stream.  Untagged: run_lockstep issues it alone and only its tower advances (the towers meet again at the attention request)."""
+    __slots__ = ("tag", "name", "args", "m_real")
+    optional = True
+
+    def __init__(self, name, *args, m_real=None):
+        self.tag, self.name, self.args, self.m_real = None, name, args, m_real
+
+    def issue(self):
+        prof = GEMM_PROFILE if self.name == "lpi_gemm_nt_mx8" else None
+        if prof is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        call(self.name, *self.args, _stream())
+        if prof is not None:
+            e1.record()
+            cdt, M, N, K = self.args[:4]
+            mr = self.m_real or M
+            csz = {F32: 4, _lib.MX8: 1 + 1 / 32}.get(cdt, 2)
+            nbytes = (mr * K + N * K) * (1 + 1 / 32) + mr * N * csz * (2 if self.args[17] is not None else 1)
+            prof.append((e0, e1, 2.0 * mr * N * K, nbytes, int(_lib.load().lpi_gemm_last_kernel())))
+
+
 def _cdt(c):
     return F32 if c.dtype == torch.float32 else (F16 if c.dtype == torch.float16 else BF16)
 
@@ -523,6 +574,11 @@ class Tower:
         # interleaved order (the pooled-row kernels read K and V as the rows d .. 3 d of the weight).  EngineOptions.qkv_grouped: OFF by default (in the step
         # it measured nothing: see there).
         self.qkv_grouped = bool(opt.qkv_grouped and dt != F32 and not spec.causal and spec.layers > 1)
+        if opt.mx8_forward and dt == F32:
+            raise ValueError("mx8_forward is an option of the 2-byte modes")
+        self.mx8 = mx8 = bool(opt.mx8_forward)
+        if mx8 and spec.width % 128:
+            raise ValueError(f"mx8_forward: tower width {spec.width} is not a multiple of 128")
         d_, H_ = spec.width, spec.heads
         self.qkv_lay = (3 * 64, 64, 64)                                 # (head stride, q -> k -> v stride, ctx head stride) of a grouped block
         perm = torch.arange(3 * d_).view(3, H_, 64).permute(1, 0, 2).reshape(-1)      # new feature h*192 + w*64 + c  <-  old w*d + h*64 + c
@@ -533,11 +589,11 @@ class Tower:
             if grouped:
                 wq, bq = wq[perm.to(wq.device)], bq[perm.to(bq.device)]
             blk = {
-                "qkv": Linear(wq, bq, dt, device),
+                "qkv": Linear(wq, bq, dt, device, mx8=mx8),
                 "grouped": grouped,
-                "out": Linear(f(p + "attn.out_proj.weight"), f(p + "attn.out_proj.bias"), dt, device),
-                "fc": Linear(f(p + "mlp.c_fc.weight"), f(p + "mlp.c_fc.bias"), dt, device),
-                "proj": Linear(f(p + "mlp.c_proj.weight"), f(p + "mlp.c_proj.bias"), dt, device),
+                "out": Linear(f(p + "attn.out_proj.weight"), f(p + "attn.out_proj.bias"), dt, device, mx8=mx8),
+                "fc": Linear(f(p + "mlp.c_fc.weight"), f(p + "mlp.c_fc.bias"), dt, device, mx8=mx8),
+                "proj": Linear(f(p + "mlp.c_proj.weight"), f(p + "mlp.c_proj.bias"), dt, device, mx8=mx8),
             }
             for nm in ("ln_1", "ln_2"):
                 blk[nm + ".w"] = f(p + nm + ".weight").to(device=device, dtype=torch.float32).contiguous()
@@ -651,6 +707,10 @@ class Tower:
             })
         if train:
             ws["du"], ws["c_du"] = ws["g"].view(TG), ws["c_g"].view(TG)
+        if self.mx8 and not train:
+            # MX-FP8 operands of the no-grad forward: LN(x) (h), the attention output (ctx) and QuickGELU(c_fc) (g) as e4m3 bytes + E8M0 scales per 32 columns
+            u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=dev)  # noqa: E731
+            ws["mx"] = {"h": u8(Mp, d), "hs": u8(Mp, d // 32), "ctx": u8(Mp, d), "ctxs": u8(Mp, d // 32), "g": u8(Mp, 4 * d), "gs": u8(Mp, 4 * d // 32)}
         # "stat"[i] = (ln1 mean, ln1 rstd, ln2 mean, ln2 rstd) of layer i: views into the LN blocks
         ws["stat"] = [(b[0, :Mp], b[0, Mp:2 * Mp], b[1, :Mp], b[1, Mp:2 * Mp]) for b in ws["lnblk"]]
         ws["ln_ld"] = Mp
@@ -703,6 +763,25 @@ class Tower:
                 so = (st[0], st[1]) if have_ln1 else (None, None)
                 yield RowReq(f"{lt}.padd", [_lib.row_job(_lib.ROWOP_PROMPT_ADD, B=Bq, L=Lq, row_start=rsq, P=P, d=d, dt_a=xdt, out=x_in,
                                                          a=prompts.view(-1)[i * P * d:], bstride=prompt_bstride, mean=so[0], rstd=so[1])], optional=True)
+            if self.mx8 and not train and not (i == len(self.blocks) - 1 and POOLED_LAST):
+                # MX-FP8 forward of a full block (EngineOptions.mx8_forward): LN -> MX, four block-scaled GEMMs, attention on the 2-byte q / k / v
+                m, xc = ws["mx"], _cdt(x_in)
+                G = "lpi_gemm_nt_mx8"
+                qw, ow, fw, pw = blk["qkv"], blk["out"], blk["fc"], blk["proj"]
+                yield Mx8Req("lpi_layernorm_mx8_fwd", xdt, M, d, x_in, d, blk["ln_1.w"], blk["ln_1.b"], m["h"], d, m["hs"], d // 32, None, None)
+                yield Mx8Req(G, _cdt(qkv), Mp, 3 * d, d, m["h"], d, m["hs"], d // 32, qw.w8, d, qw.w8s, d // 32, qkv, 3 * d, None, 0, qw.b, None, 0,
+                             EPI_NONE, 1.0, m_real=M)
+                yield AttnFwdReq(f"{lt}.attn", dt, B, L, rs, H, qkv, 3 * d, ctx, d, lse, int(sp.causal), pre, self.qkv_lay if blk["grouped"] else None)
+                yield Mx8Req("lpi_mx8_quantize", dt, M, d, ctx, d, m["ctx"], d, m["ctxs"], d // 32)
+                yield Mx8Req(G, xc, Mp, d, d, m["ctx"], d, m["ctxs"], d // 32, ow.w8, d, ow.w8s, d // 32, xmid, d, None, 0, ow.b, x_in, d, EPI_NONE, 1.0,
+                             m_real=M)
+                yield Mx8Req("lpi_layernorm_mx8_fwd", xdt, M, d, xmid, d, blk["ln_2.w"], blk["ln_2.b"], m["h"], d, m["hs"], d // 32, None, None)
+                yield Mx8Req(G, _lib.MX8, Mp, 4 * d, d, m["h"], d, m["hs"], d // 32, fw.w8, d, fw.w8s, d // 32, m["g"], 4 * d, m["gs"], 4 * d // 32, fw.b,
+                             None, 0, EPI_QUICKGELU, 1.0, m_real=M)
+                yield Mx8Req(G, xc, Mp, d, 4 * d, m["g"], 4 * d, m["gs"], 4 * d // 32, pw.w8, 4 * d, pw.w8s, 4 * d // 32, x_out, d, None, 0, pw.b, xmid, d,
+                             EPI_NONE, 1.0, m_real=M)
+                have_ln1 = False      # no row-statistics epilogue on this path: the next block (the pooled last one) takes its statistics pass
+                continue
             # LayerNorm folded into the GEMM behind it (LnLinear): a statistics pass over the stream, then the GEMM reads the stream itself
             fold = "qkv_ln" in blk and _ln_fold_ok(Mp, d)
             lnb, ln_ld = ws["lnblk"][i], ws["ln_ld"]
@@ -896,6 +975,7 @@ class DualEncoder:
         """options: an EngineOptions (None = EngineOptions.from_env(): the defaults with the three documented environment fall-backs applied)."""
         self.cfg = cfg
         self.opt = options if options is not None else EngineOptions.from_env()
+        self.opt.check_dtype(dtype)
         self.device = torch.device(device)
         _require_gpu(self.device)
         _lib.load()
