@@ -13,6 +13,7 @@
  *   - `dtype` selects the storage type of activations/weights fed to the matrix cores:
  *       LPI_F32  : f32 in, f32 accumulate (v_mfma_f32_16x16x4_f32)     — parity mode
  *       LPI_BF16 : bf16 in, f32 accumulate (v_mfma_f32_16x16x32_bf16) — throughput mode
+ *       LPI_F32X3: f32 in, split into hi + lo bf16 in registers, three bf16 products, f32 accumulate — GEMMs of the f32 mode only
  *     the residual stream, LayerNorm statistics, losses and prompt factors are always f32;
  *   - token rows are batch-major: row(b, l) = b * L + l (the reference permutes to [L, B, d] for
  *     nn.MultiheadAttention, models/clip/model.py:253; the arithmetic is layout independent);
@@ -33,6 +34,14 @@ extern "C" {
 #define LPI_F16 2          /* STORAGE type of the residual stream in bf16 mode (the reference's own activation type: it runs fp16 end to
                             * end, model.py:371-392); never an MFMA operand type.  Accepted where a parameter is named x_dtype, and as
                             * lpi_gemm_nt's c_dtype together with a residual of the same type. */
+
+#define LPI_F32X3 4        /* lpi_gemm_nt / lpi_gemm_nt_grouped `dtype` only: f32 operands in memory (A, B, C, residual, aux all f32; c_dtype must be
+                            * LPI_F32), multiplied as SPLIT bf16 ("bf16x3"): each operand element x becomes hi = RNE_bf16(x), lo = RNE_bf16(x - hi)
+                            * in registers and a product is hi.hi + hi.lo + lo.hi on v_mfma_f32_16x16x32_bf16 with f32 accumulation (lo.lo dropped:
+                            * about 2^-16 per product where f32 has 2^-24 and bf16 2^-8).  Epilogues LPI_EPI_NONE (+- bias, +- residual),
+                            * LPI_EPI_QUICKGELU (+- aux) and LPI_EPI_DQUICKGELU; shapes as LPI_F32 (M, N % 128, K % 32); anything else is LPI_ENOSYS /
+                            * LPI_EINVAL before any launch.  NaN / Inf operands are out of contract; a subnormal lo may flush.  Attributed to
+                            * LPI_GEMM_K_X3.  lpi_gemm_nt_rows does not take it: few-row GEMMs stay exact f32. */
 
 #define LPI_EINVAL (-22)   /* bad shape / alignment / null pointer */
 #define LPI_ENOSYS (-38)   /* combination not built */
@@ -701,6 +710,7 @@ int lpi_bpe_tokenize(void* handle, const char* const* texts, int n, int context_
 #define LPI_GEMM_K_256X128 3    /* gemm256x128_kernel                                             */
 #define LPI_GEMM_K_ROWS 4       /* gemm_rows_kernel: few-row GEMM, 32x32 tiles over the whole K   */
 #define LPI_GEMM_K_MX8 5        /* gemm_mx8_kernel: MX-FP8 operands, 128x128 tiles (lpi_gemm_nt_mx8) */
+#define LPI_GEMM_K_X3 6         /* gemm_nt_kernel / gemm256_kernel on split-bf16 operands (LPI_F32X3) */
 int lpi_gemm_last_kernel(void);
 
 /* ---- MX-FP8 forward (csrc/gemm_mx8.hip, csrc/mx8_rows.hip): the four block GEMMs of the no-grad forwards on the block-scaled FP8 matrix instruction ----

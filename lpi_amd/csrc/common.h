@@ -163,6 +163,16 @@ template <> __device__ __forceinline__ void mma_chunk<f16_t>(f32x4& acc, const C
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hh, b.hh, acc, 0, 0, 0);
 }
 
+// bf16x3 (LPI_F32X3): f32 elements in memory, each split in registers into hi + lo bf16 and multiplied as hi.hi + hi.lo + lo.hi on the bf16 matrix
+// instruction.  An element TAG of size 4: staging, swizzle and pointer arithmetic see a 4-byte element; C, bias, residual and aux stay f32.
+struct f32x3_t { float v; };
+template <typename T> inline constexpr bool kIsX3 = false;
+template <> inline constexpr bool kIsX3<f32x3_t> = true;
+template <> struct Elem<f32x3_t> {
+    static constexpr int DT = LPI_F32X3;
+    static constexpr int EPC = 4;
+};
+
 // two floats -> one dword of T (round to nearest even): v_cvt_pk_bf16_f32 / v_cvt_pkrtz... (f16: v_cvt_pk via two v_cvt_f16_f32)
 template <typename T> __device__ __forceinline__ uint32_t pack2_t(float a, float b);
 template <> __device__ __forceinline__ uint32_t pack2_t<bf16_t>(float a, float b) {
@@ -177,6 +187,23 @@ template <> __device__ __forceinline__ uint32_t pack2_t<f16_t>(float a, float b)
 }
 template <> __device__ __forceinline__ void st4_nt<bf16_t>(bf16_t* p, f32x4 v) { st_stream8(p, pack2_t<bf16_t>(v[0], v[1]), pack2_t<bf16_t>(v[2], v[3])); }
 template <> __device__ __forceinline__ void st4_nt<f16_t>(f16_t* p, f32x4 v) { st_stream8(p, pack2_t<f16_t>(v[0], v[1]), pack2_t<f16_t>(v[2], v[3])); }
+// bf16x3 split of a lane's fragment: the two f32 chunks `c0`, `c1` of one staged row (8 k-values: exactly one 16x16x32 instruction's share of this
+// lane) become, IN PLACE, c0 = the 8 values' hi = RNE_bf16(x) and c1 = their lo = RNE_bf16(x - float(hi)); the subtraction is exact in f32.  Both
+// operands are split by the same function, so element j of hi and of lo is the same k for both.  6 vector instructions per two values.
+__device__ __forceinline__ void split_bf16x3(Chunk& c0, Chunk& c1) {
+    const f32x4 x0 = c0.f, x1 = c1.f;
+    uint32_t hi[4], lo[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float a = i < 2 ? x0[2 * i] : x1[2 * i - 4], b = i < 2 ? x0[2 * i + 1] : x1[2 * i - 3];
+        hi[i] = pack2_t<bf16_t>(a, b);
+        lo[i] = pack2_t<bf16_t>(a - __uint_as_float(hi[i] << 16), b - __uint_as_float(hi[i] & 0xFFFF0000u));
+    }
+    c0.u = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+    c1.u = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+}
+// The three products of a tile are term t = 0, 1, 2 -> (weight plane t >> 1, activation plane t & 1) with plane 0 = hi, 1 = lo: hi.hi, hi.lo, lo.hi;
+// lo.lo is dropped.  The tile loops run t outermost, so the three dependent instructions of one accumulator are a whole sweep of tiles apart.
 // element e (0..7) of a chunk of T as float
 template <typename T> __device__ __forceinline__ float chunk_elem(const Chunk& c, int e);
 template <> __device__ __forceinline__ float chunk_elem<bf16_t>(const Chunk& c, int e) { return (float)c.h[e]; }

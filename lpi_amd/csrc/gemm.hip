@@ -8,6 +8,8 @@
 //  * block tile 128x128, 4 waves as 2x2, each wave 64x64 = 4x4 MFMA 16x16 tiles (64 accumulator VGPRs);
 //  * both operands are K-contiguous, so one LDS tile row = 128 bytes = 8 x 16-byte chunks for either element
 //    type (bf16: BK=64, f32: BK=32); the same staging/fragment code serves both, only mma_chunk differs;
+//    bf16x3 (T = f32x3_t, LPI_F32X3) stages f32 rows the same way and splits each fragment into hi + lo bf16 in registers: a K tile of 32 is
+//    one v_mfma_f32_16x16x32_bf16 triple (hi.hi + hi.lo + lo.hi) per 16x16 tile;
 //  * global -> LDS by `global_load_lds_dwordx4` (16 B/lane, no VGPR round trip), double buffered, one barrier
 //    per K tile; the LDS image is lane-linear so the bank swizzle chunk ^= (row>>1)&7 is applied to the
 //    per-lane SOURCE address and again on the ds_read_b128 (conflict-free for the 16x16 fragment pattern);
@@ -105,18 +107,41 @@ __device__ __forceinline__ void gemm_nt_tile(
         __syncthreads();                                  // ... and everyone's; buffer (kt+1)&1 is free again
         if (kt + 1 < nk) stage(kt + 1, (kt + 1) & 1);
         const char* buf = smem + (kt & 1) * STAGE_BYTES;
+        if constexpr (kIsX3<T>) {
+            // bf16x3: a lane's two chunks of a row are one 16x16x32 instruction's 8 k-values; split each fragment once, then 3 x 16 instructions
+            Chunk fa[4][2], fb[4][2];
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            Chunk fa[4], fb[4];
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    fa[i][ks].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                    fb[i][ks].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                fa[i].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
-                fb[i].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                split_bf16x3(fa[i][0], fa[i][1]);
+                split_bf16x3(fb[i][0], fb[i][1]);
             }
 #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
+            for (int t = 0; t < 3; ++t)
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) mma_chunk<T>(acc[ni][mi], fb[ni], fa[mi]);
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) mma_chunk<bf16_t>(acc[ni][mi], fb[ni][t >> 1], fa[mi][t & 1]);
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                Chunk fa[4], fb[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    fa[i].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                    fb[i].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                }
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) mma_chunk<T>(acc[ni][mi], fb[ni], fa[mi]);
+            }
         }
     }
 
@@ -157,7 +182,7 @@ int launch_impl(int M, int N, int K, const void* A, int lda, const void* B, int 
     auto kern = gemm_nt_kernel<T, TC, EPI, RES, SAVE_U>;
     static LdsOnce once;
     if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES)) return e;
-    lpi_note_gemm_kernel(LPI_GEMM_K_128);
+    lpi_note_gemm_kernel(kIsX3<T> ? LPI_GEMM_K_X3 : LPI_GEMM_K_128);
     LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHREADS), 2 * STAGE_BYTES, s, M, N, K, (const T*)A, lda, (const T*)B, ldb,
                        (TC*)C, ldc, bias, residual, ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn);
     LPI_CHECK_LAST();
@@ -216,7 +241,11 @@ static int gemm_nt_check(int dtype, int c_dtype, int M, int N, int K, const void
                          const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux)
 {
 
-    const int esz = dtype == LPI_F32 ? 4 : 2;
+    if (dtype == LPI_F32X3) {      // bf16x3: everything in memory is f32; the epilogues of the f32 mode
+        if (c_dtype != LPI_F32) return LPI_ENOSYS;
+        if (epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_QUICKGELU && epilogue != LPI_EPI_DQUICKGELU) return LPI_ENOSYS;
+    }
+    const int esz = dtype == LPI_F32 || dtype == LPI_F32X3 ? 4 : 2;
     const int csz = c_dtype == LPI_F32 ? 4 : 2;
     if (epilogue == LPI_EPI_RES_ROWSTATS) {      // the fp16 residual epilogue + the row statistics of its output: aux = f32 slots, N/128 x 2 x ldaux
         if (c_dtype != LPI_F16 || dtype == LPI_F32) return LPI_ENOSYS;
@@ -259,17 +288,20 @@ extern "C" int lpi_gemm_nt(int dtype, int c_dtype, int M, int N, int K, const vo
     }
     // Half-empty launches: fewer than tuning key 5 (default 160) 256x256 tiles -> 256x128 tiles, twice the workgroups (bf16 only:
     // the f32 path is MFMA-bound at any tile size).  Key 5 = 0 disables it.
-    if (dtype != LPI_F32 && g_lpi_tuning[5] > 0 && lpi_gemm256_eligible(dtype, M, N, K) && (M / 256) * (N / 256) < g_lpi_tuning[5] &&
+    const bool f32_rows = dtype == LPI_F32 || dtype == LPI_F32X3;      // 4-byte elements in memory
+    if (!f32_rows && g_lpi_tuning[5] > 0 && lpi_gemm256_eligible(dtype, M, N, K) && (M / 256) * (N / 256) < g_lpi_tuning[5] &&
         (M / 256) * (N / 256) >= 16 && lpi_gemm256x128_eligible(dtype, M, N, K)) {
         const int rc = lpi_gemm256x128_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s,
                                               g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8);
         if (rc != LPI_ENOSYS) return rc;
     }
     // 256x256 8-phase kernel when the shape gives it enough tiles to fill the chip (tuning keys 0 / 1 = minimum tile count for bf16 / f32)
-    if (lpi_gemm256_eligible(dtype, M, N, K) && (M / 256) * (N / 256) >= g_lpi_tuning[dtype == LPI_F32 ? 1 : 0])
+    if (lpi_gemm256_eligible(dtype, M, N, K) && (M / 256) * (N / 256) >= g_lpi_tuning[f32_rows ? 1 : 0])
         return lpi_gemm256_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s);
     if (dtype == LPI_F32 && c_dtype == LPI_F32)
         return dispatch_epi<float, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
+    if (dtype == LPI_F32X3 && c_dtype == LPI_F32)
+        return dispatch_epi<f32x3_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
     if (dtype == LPI_BF16 && c_dtype == LPI_BF16)
         return dispatch_epi<bf16_t, bf16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
     if (dtype == LPI_BF16 && c_dtype == LPI_F32)
@@ -303,7 +335,7 @@ extern "C" int lpi_gemm_nt_grouped(int dtype, int c_dtype, int epilogue, float a
                                   (const float*)d[i].residual, d[i].ldr, epilogue, d[i].aux, d[i].ldaux)) return e;
     // one persistent launch: two bf16 / f16 problems that the 256x256 kernel takes, with an epilogue the persistent kernel has (store-only,
     // or a 2-byte side tile), together at least a round of tiles (tuning key 8 != 0 = never group: A/B switch)
-    bool group = count == 2 && dtype != LPI_F32 && g_lpi_tuning[2] >= 0 && g_lpi_tuning[8] == 0;
+    bool group = count == 2 && dtype != LPI_F32 && dtype != LPI_F32X3 && g_lpi_tuning[2] >= 0 && g_lpi_tuning[8] == 0;
     if (group) {
         int tiles = 0;
         for (int i = 0; i < 2 && group; ++i) {

@@ -112,6 +112,7 @@ int launch256_impl(int M, int N, int K, const void* A, int lda, const void* B, i
     const int gm = g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8;
     // a short last round (<= 128 of 256 CUs busy) runs as 256x128 half tiles inside the same launch (tuning key 6, default on;
     // bf16 operands only: the f32 path is MFMA-bound and its K-tile count per 128-byte row differs)
+    if constexpr (!kIsX3<T>)      // (no 256x128 tile for bf16x3: its rows are f32)
     if (sizeof(T) == 2 && g_lpi_tuning[6] != 0 && n_full >= 256 && rem > 0 && rem <= 128 && K / (ROWB / (int)sizeof(T)) >= 2) {
         auto tk = gemm256_tail_kernel<T, TC, EPI, RES, SAVE_U>;
         constexpr int LDS_TAIL = t128::LDS_BYTES > LDS_BYTES ? t128::LDS_BYTES : LDS_BYTES;
@@ -128,7 +129,7 @@ int launch256_impl(int M, int N, int K, const void* A, int lda, const void* B, i
     auto kern = gemm256_kernel<T, TC, EPI, RES, SAVE_U>;
     static LdsOnce once;
     if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES)) return e;
-    lpi_note_gemm_kernel(LPI_GEMM_K_256);
+    lpi_note_gemm_kernel(kIsX3<T> ? LPI_GEMM_K_X3 : LPI_GEMM_K_256);
     LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES, s, M, N, K, (const T*)A, lda, (const T*)B, ldb, (TC*)C, ldc, bias, residual,
                ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn, 0, g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8);
     LPI_CHECK_LAST();
@@ -171,7 +172,7 @@ int dispatch256(int epi, int M, int N, int K, const void* A, int lda, const void
 
 // true if the 256x256 kernel can take this shape
 bool lpi_gemm256_eligible(int dtype, int M, int N, int K) {
-    const int bk = ROWB / (dtype == LPI_F32 ? 4 : 2);
+    const int bk = ROWB / (dtype == LPI_F32 || dtype == LPI_F32X3 ? 4 : 2);
     if (M % T256 || N % T256 || K % bk) return false;
     const int nk = K / bk;
     return nk >= 2 && (nk % 2) == 0;
@@ -192,12 +193,14 @@ int lpi_gemm256_launch(int dtype, int c_dtype, int M, int N, int K, const void* 
     // Tuning key 2: -1 one tile per workgroup everywhere; 2 persistent for store-only epilogues only (A/B).
     const bool loads_in_epilogue = residual != nullptr || epilogue == LPI_EPI_DQUICKGELU;
     const bool side16 = (residual != nullptr && c_dtype == LPI_F16) || epilogue == LPI_EPI_DQUICKGELU;
-    if (dtype != LPI_F32 && g_lpi_tuning[2] >= 0 && (!loads_in_epilogue || (side16 && g_lpi_tuning[2] != 2))) {
+    if (dtype != LPI_F32 && dtype != LPI_F32X3 && g_lpi_tuning[2] >= 0 && (!loads_in_epilogue || (side16 && g_lpi_tuning[2] != 2))) {
         const int rc = lpi_gemm256p_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s);
         if (rc != LPI_ENOSYS) return rc;
     }
     if (dtype == LPI_F32 && c_dtype == LPI_F32)
         return dispatch256<float, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
+    if (dtype == LPI_F32X3 && c_dtype == LPI_F32)
+        return dispatch256<f32x3_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
     if (dtype == LPI_BF16 && c_dtype == LPI_BF16)
         return dispatch256<bf16_t, bf16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
     if (dtype == LPI_BF16 && c_dtype == LPI_F32)

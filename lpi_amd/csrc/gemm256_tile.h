@@ -87,14 +87,37 @@ __device__ __forceinline__ void tile(int m0, int n0, int K, const T* __restrict_
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) fb[ni][ks].u = *reinterpret_cast<const uint4*>(half + b_base + ni * 16 * ROWB + foff[ks]);
     };
+    // bf16x3 (T = f32x3_t): a fragment's two f32 chunks [.][0], [.][1] are one 16x16x32 instruction's 8 k-values of this lane; split once per read, in
+    // place, into [.][0] = hi and [.][1] = lo (after the phase's lgkmcnt(0)); the B fragments stay split across both phases of a K-tile.
+    auto split_A = [&]() {
+        if constexpr (kIsX3<T>) {
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) split_bf16x3(fa[mi][0], fa[mi][1]);
+        }
+    };
+    auto split_B = [&](Chunk (&fb)[2][2]) {
+        if constexpr (kIsX3<T>) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) split_bf16x3(fb[ni][0], fb[ni][1]);
+        }
+    };
     auto mma_quadrant = [&](f32x4 (&c)[2][2][2][4], int nh, int mh, const Chunk (&fb)[2][2]) {
         __builtin_amdgcn_s_setprio(1);
+        if constexpr (kIsX3<T>) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
+            for (int t = 0; t < 3; ++t)      // hi.hi, hi.lo, lo.hi: (weight plane t >> 1, activation plane t & 1)
 #pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
+                for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) mma_chunk<T>(c[nh][ni][mh][mi], fb[ni][ks], fa[mi][ks]);
+                    for (int mi = 0; mi < 4; ++mi) mma_chunk<bf16_t>(c[nh][ni][mh][mi], fb[ni][t >> 1], fa[mi][t & 1]);
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) mma_chunk<T>(c[nh][ni][mh][mi], fb[ni][ks], fa[mi][ks]);
+        }
         __builtin_amdgcn_s_setprio(0);
     };
 // lgkmcnt(0) BEFORE the barrier: with the two wave groups staggered by one barrier (below), the other group restages a half
@@ -136,6 +159,7 @@ __device__ __forceinline__ void tile(int m0, int n0, int K, const T* __restrict_
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         PHASE_SYNC_IN();
+        split_B(fb0); split_B(fb1); split_A();
         mma_quadrant(acc, 0, 0, fb0);
         mma_quadrant(acc, 1, 0, fb1);
         PHASE_SYNC_OUT();
@@ -150,11 +174,13 @@ __device__ __forceinline__ void tile(int m0, int n0, int K, const T* __restrict_
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         PHASE_SYNC_IN();
+        split_A();
         mma_quadrant(acc, 1, 1, fb1);
         mma_quadrant(acc, 0, 1, fb0);
         PHASE_SYNC_OUT();
     };
 #else
+    static_assert(!kIsX3<T>, "bf16x3 is built for the two-phase schedule only");
     // prologue: K-tile 0 (4 halves) -> buffer 0, first three halves of K-tile 1 -> buffer 1
     stage_A(0, 0, 0); stage_B(0, 0, 0); stage_B(0, 1, 0); stage_A(0, 1, 0);
     stage_A(1, 0, 1); stage_B(1, 0, 1); stage_B(1, 1, 1);

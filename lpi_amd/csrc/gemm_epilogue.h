@@ -6,6 +6,7 @@
 // it is read only by the BACKWARD's gelu'(u) epilogue, whose operands (gradients) are bf16 (they do not fit fp16's range).
 template <typename T> struct AuxT { typedef T type; };
 template <> struct AuxT<f16_t> { typedef bf16_t type; };
+template <> struct AuxT<f32x3_t> { typedef float type; };      // bf16x3: everything in memory is f32
 
 // RES (residual present) and SAVE_U (QuickGELU pre-activation wanted) are COMPILE-TIME: a run-time "pointer or not" test per
 // element makes hipcc branch around every load and wait vmcnt(0) each time — 32 serial HBM round trips per lane

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import BF16, EPI_DQUICKGELU, EPI_LN, EPI_LN_QUICKGELU, EPI_NONE, EPI_QUICKGELU, EPI_RES_ROWSTATS, F16, F32, call
+from ._lib import BF16, EPI_DQUICKGELU, EPI_LN, EPI_LN_QUICKGELU, EPI_NONE, EPI_QUICKGELU, EPI_RES_ROWSTATS, F16, F32, F32X3, call
 from .synth import ClipConfig
 
 import ctypes
@@ -82,7 +82,12 @@ class EngineOptions:
         elements along K: include/lpi_hip.h) in the train=False forwards of both towers — the un-prompted encodes of clustering and the two passes of
         retrieval evaluation, which never need a gradient.  LayerNorm writes the MX operand directly (lpi_layernorm_mx8_fwd), c_fc's QuickGELU epilogue
         writes c_proj's; attention, the fp16 residual stream, the patch embedding, the pooled last block and the heads are what the 2-byte mode runs.
-        train=True forwards and every backward are untouched.  2-byte modes only (ValueError with dtype 'f32'); +1 byte per parameter of the block matrices."""
+        train=True forwards and every backward are untouched.  2-byte modes only (ValueError with dtype 'f32'); +1 byte per parameter of the block matrices.
+    gemm_bf16x3: the f32 mode's GEMMs of both towers (forward and dgrad, train=True and train=False, the patch embedding by the same rule of shape) that go
+        to lpi_gemm_nt go out with the operand code LPI_F32X3: every operand element is split in registers into hi + lo bf16 and a product is
+        hi.hi + hi.lo + lo.hi on the bf16 matrix instruction with f32 accumulation — about 2^-16 per product where f32 has 2^-24 and bf16 2^-8.  Memory
+        formats stay f32: weights (no extra copy), attention, LayerNorm, row kernels, the few-row GEMMs (lpi_gemm_nt_rows), losses and the optimiser are
+        the f32 mode's, workspace and launch count unchanged.  f32 mode only (ValueError with 'bf16' / 'f16')."""
     residual_f16: bool = True
     ln_fold: int = 2
     rowstats: int = 2
@@ -93,6 +98,7 @@ class EngineOptions:
     qkv_grouped: bool = False
     pixel_norm: object = "imagenet"
     mx8_forward: bool = False
+    gemm_bf16x3: bool = False
 
     def __post_init__(self):
         if self.ln_fold not in (0, 1, 2) or self.rowstats not in (0, 1, 2):
@@ -112,7 +118,9 @@ class EngineOptions:
     def check_dtype(self, dtype: str):
         """Refusals that depend on the engine's operand type; raised before anything touches the GPU."""
         if self.mx8_forward and _DT[dtype] == F32:
-            raise ValueError("mx8_forward is an option of the 2-byte modes ('bf16', 'f16'): the f32 parity mode has no reduced-precision path")
+            raise ValueError("mx8_forward is an option of the 2-byte modes ('bf16', 'f16'): the f32 mode's reduced-precision path is gemm_bf16x3")
+        if self.gemm_bf16x3 and _DT[dtype] != F32:
+            raise ValueError("gemm_bf16x3 is an option of the f32 mode: the 2-byte modes ('bf16', 'f16') already multiply on the bf16 / fp16 matrix instruction")
 
     def pixel_stats(self):
         """(mean, std) of pixel_norm; (None, None) for 'imagenet' (make_pixel_lut's defaults)."""
@@ -211,9 +219,18 @@ def _few_rows(dt, M, N, K):
     return M <= 512 and M % 128 == 0 and N % 128 == 0 and K % (32 if dt == F32 else 64) == 0
 
 
+def _gemm_code(dt, opt):
+    """The operand code a tower's GemmReqs carry: F32X3 for the f32 operands of an engine with EngineOptions.gemm_bf16x3, else dt itself."""
+    return F32X3 if (opt.gemm_bf16x3 and dt == F32) else dt
+
+
 def gemm(dt, a, b, c, M, N, K, bias=None, residual=None, epi=EPI_NONE, aux=None, alpha=1.0, m_real=None, ldr=None):
     """c[M,N] = epi(alpha * a[M,K] @ b[N,K]^T + bias) + residual   (all row-major, contiguous rows).
-    m_real: un-padded row count, used only for algorithmic-FLOP accounting."""
+    m_real: un-padded row count, used only for algorithmic-FLOP accounting.
+    dt = F32X3 (EngineOptions.gemm_bf16x3): f32 tensors; lpi_gemm_nt multiplies them as split bf16, a few-row GEMM stays the exact f32 kernel."""
+    nt_dt = dt
+    if dt == F32X3:
+        dt = F32
     cdt = F32 if c.dtype == torch.float32 else (F16 if c.dtype == torch.float16 else BF16)
     prof = GEMM_PROFILE
     if prof is not None:
@@ -225,7 +242,7 @@ def gemm(dt, a, b, c, M, N, K, bias=None, residual=None, epi=EPI_NONE, aux=None,
     if (cdt != F16 or dt == F16) and not ln and epi != EPI_RES_ROWSTATS and _few_rows(dt, M, N, K):
         _lib.gemm_rows(dt, cdt, epi, alpha, [dict(M=M, N=N, K=K, a=a, b=b, c=c, bias=bias, residual=residual, aux=aux, ldr=ldr)], _stream())
     else:
-        call("lpi_gemm_nt", dt, cdt, M, N, K, a, a.stride(0), b, b.stride(0), c, c.stride(0), bias, residual,
+        call("lpi_gemm_nt", nt_dt, cdt, M, N, K, a, a.stride(0), b, b.stride(0), c, c.stride(0), bias, residual,
              ldr, epi, aux, aux.stride(0) if aux is not None else 0,
              float(alpha), _stream())
     if prof is not None:
@@ -462,7 +479,7 @@ def _issue_pair(r0: GemmReq, r1: GemmReq):
             r1.issue()
         return
     k0, k1 = r0.kw, r1.kw
-    same = (r0.dt == r1.dt and r0.dt != F32 and r0.c.dtype == r1.c.dtype and k0.get("epi", EPI_NONE) == k1.get("epi", EPI_NONE)
+    same = (r0.dt == r1.dt and r0.dt not in (F32, F32X3) and r0.c.dtype == r1.c.dtype and k0.get("epi", EPI_NONE) == k1.get("epi", EPI_NONE)
             and (k0.get("residual") is None) == (k1.get("residual") is None) and (k0.get("aux") is None) == (k1.get("aux") is None)
             and (k0.get("bias") is None) == (k1.get("bias") is None) and k0.get("alpha", 1.0) == k1.get("alpha", 1.0)
             )
@@ -740,6 +757,7 @@ class Tower:
 
         prompts: f32 tensor whose element (b, layer, p, :) sits at  b*prompt_bstride + (layer*P + p)*d."""
         sp, dt, xdt, s = self.spec, self.dt, self.xdt, _stream()
+        mdt = _gemm_code(dt, self.opt)      # what the GemmReqs carry: dt, or F32X3 (EngineOptions.gemm_bf16x3)
         POOLED_LAST, LN_FOLD = self.opt.pooled_last, self.opt.ln_fold
         d, H = sp.width, sp.heads
         B, L, Mp, M = ws["B"], ws["L"], ws["Mp"], ws["M"]
@@ -803,11 +821,11 @@ class Tower:
                     ql = blk["qkv_ln"]
                     yield GemmReq(f"{lt}.kv", F16, x_in, ql.w[d:], qkv[:, d:], Mp, 2 * d, d, bias=ql.c2[d:], residual=lnb[0], ldr=ln_ld, epi=EPI_LN, m_real=M)
                 else:
-                    yield GemmReq(f"{lt}.kv", dt, ws["h"], wq[d:], qkv[:, d:], Mp, 2 * d, d, bias=bq[d:], m_real=M)
+                    yield GemmReq(f"{lt}.kv", mdt, ws["h"], wq[d:], qkv[:, d:], Mp, 2 * d, d, bias=bq[d:], m_real=M)
                 # ln_1 of the pooled rows and the rows themselves (f32: the residual operand of the pooled out_proj) in one job
                 yield RowReq(f"{lt}.pln1", [_lib.row_job(_lib.ROWOP_POOL_LN_FWD, B=B, L=Lx, d=d, dt_a=xdt, dt_b=dt, a=x_in, idx=pidx, gamma=blk["ln_1.w"],
                                                          beta=blk["ln_1.b"], out=ws["c_h"], ld_c=d, mean=cst1[0], rstd=cst1[1], out2=ws["c_xin"])])
-                yield GemmReq(f"{lt}.cq", dt, ws["c_h"], wq[:d], ws["c_q"], Bp, d, d, bias=bq[:d], m_real=B)
+                yield GemmReq(f"{lt}.cq", mdt, ws["c_h"], wq[:d], ws["c_q"], Bp, d, d, bias=bq[:d], m_real=B)
                 if spool:
                     x_sp, st_sp = x_in, st      # (bound now: the generator's loop variables move on)
                     yield SoloReq(f"{lt}.pattn", lambda: call("lpi_spool_attn_fwd", dt, B, L, H, ws["c_q"], d, wq, d, blk["qkv_wT"], 3 * d, bq, x_sp, d, st_sp[0], st_sp[1], blk["ln_1.w"],
@@ -815,25 +833,25 @@ class Tower:
                 else:
                     yield PoolAttnReq(f"{lt}.pattn", dt, False, B=B, L=L, row_start=rs, H=H, q=ws["c_q"], ldq=d, qkv=qkv, ldqkv=3 * d, idx=pool_idx, ctx=ws["c_ctx"],
                                       ldctx=d, lse=ws["c_lse"], causal=int(sp.causal), shared_rows=pre)
-                yield GemmReq(f"{lt}.cout", dt, ws["c_ctx"], blk["out"].w, ws["c_xmid"], Bp, d, d, bias=blk["out"].b, residual=ws["c_xin"], m_real=B)
+                yield GemmReq(f"{lt}.cout", mdt, ws["c_ctx"], blk["out"].w, ws["c_xmid"], Bp, d, d, bias=blk["out"].b, residual=ws["c_xin"], m_real=B)
                 yield RowReq(f"{lt}.pln2", [_lib.row_job(_lib.ROWOP_POOL_LN_FWD, B=B, L=1, d=d, dt_a=F32, dt_b=dt, a=ws["c_xmid"], gamma=blk["ln_2.w"],
                                                          beta=blk["ln_2.b"], out=ws["c_h"], ld_c=d, mean=cst[0], rstd=cst[1])])
-                yield GemmReq(f"{lt}.cfc", dt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=ws["c_u"], m_real=B)
-                yield GemmReq(f"{lt}.cproj", dt, ws["c_g"], blk["proj"].w, ws["c_xout"], Bp, d, 4 * d, bias=blk["proj"].b, residual=ws["c_xmid"], m_real=B)
+                yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=ws["c_u"], m_real=B)
+                yield GemmReq(f"{lt}.cproj", mdt, ws["c_g"], blk["proj"].w, ws["c_xout"], Bp, d, 4 * d, bias=blk["proj"].b, residual=ws["c_xmid"], m_real=B)
                 return ws["c_xout"]
             if fold:
                 ql = blk["qkv_ln"]
                 yield GemmReq(f"{lt}.qkv", F16, x_in, ql.w, qkv, Mp, 3 * d, d, bias=ql.c2, residual=lnb[0], ldr=ln_ld, epi=EPI_LN, m_real=M)
             else:
-                yield GemmReq(f"{lt}.qkv", dt, ws["h"], blk["qkv"].w, qkv, Mp, 3 * d, d, bias=blk["qkv"].b, m_real=M)
+                yield GemmReq(f"{lt}.qkv", mdt, ws["h"], blk["qkv"].w, qkv, Mp, 3 * d, d, bias=blk["qkv"].b, m_real=M)
             yield AttnFwdReq(f"{lt}.attn", dt, B, L, rs, H, qkv, 3 * d, ctx, d, lse, int(sp.causal), pre, self.qkv_lay if blk["grouped"] else None)
             ln2_stats = rowstats >= 1 and LN_FOLD >= 2 and not (i == len(self.blocks) - 1 and POOLED_LAST)
             if ln2_stats:      # x + attn(..) and the slot sums of its rows in one epilogue; ln_2's mean / rstd from them
-                yield GemmReq(f"{lt}.out", dt, ctx, blk["out"].w, xmid, Mp, d, d, bias=blk["out"].b, residual=x_in, m_real=M, epi=EPI_RES_ROWSTATS,
+                yield GemmReq(f"{lt}.out", mdt, ctx, blk["out"].w, xmid, Mp, d, d, bias=blk["out"].b, residual=x_in, m_real=M, epi=EPI_RES_ROWSTATS,
                               aux=ws["rstat"])
                 yield StatFinReq(f"{lt}.fin2", M, d, ws["rstat"], ws["rstat"].stride(0), st[2], st[3])
             else:
-                yield GemmReq(f"{lt}.out", dt, ctx, blk["out"].w, xmid, Mp, d, d, bias=blk["out"].b, residual=x_in, m_real=M)
+                yield GemmReq(f"{lt}.out", mdt, ctx, blk["out"].w, xmid, Mp, d, d, bias=blk["out"].b, residual=x_in, m_real=M)
             # the next block's ln_1 statistics come out of c_proj's epilogue; rows that deep prompts rewrite first get theirs from prompt_add (above)
             nxt = i + 1
             have_ln1 = rowstats >= 2 and nxt < len(self.blocks) and "qkv_ln" in self.blocks[nxt]
@@ -847,8 +865,8 @@ class Tower:
                 yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, 4 * d, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN_QUICKGELU, aux=u, m_real=M)
             else:
                 yield LnReq(f"{lt}.ln2", "fwd", (dt, xdt), M, d, xmid, d, blk["ln_2.w"], blk["ln_2.b"], ws["h"], d, st[2], st[3], optional=True)
-                yield GemmReq(f"{lt}.fc", dt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=u, m_real=M)
-            yield GemmReq(f"{lt}.proj", dt, ws["g"], blk["proj"].w, x_out, Mp, d, 4 * d, **proj_kw)
+                yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=u, m_real=M)
+            yield GemmReq(f"{lt}.proj", mdt, ws["g"], blk["proj"].w, x_out, Mp, d, 4 * d, **proj_kw)
             if have_ln1:
                 nst = ws["stat"][nxt]
                 yield StatFinReq(f"{lt}.fin1", M, d, ws["rstat"], ws["rstat"].stride(0), nst[0], nst[1])
@@ -865,6 +883,7 @@ class Tower:
         dprompts: f32 [Lyr, P, d]; rows of layers 1..depth-1 receive the batch-summed deep-prompt gradients (acc = 1: ADDED to what the rows hold — the
         alignment-loss gradient the step seeded them with, DualEncoder.seed_prompt_grads)."""
         sp, dt, xdt, s = self.spec, self.gdt, self.xdt, _stream()        # dt: the BACKWARD's operand / storage type from here on
+        mdt = _gemm_code(dt, self.opt)
         adt = F16 if self.dt == F16 else dt       # attention backward: F16 = "saved q, k, v, ctx are fp16; gradients and operands bf16"
         POOLED_LAST, L0_PROMPT_ROWS = self.opt.pooled_last, self.opt.l0_prompt_rows
         d, H = sp.width, sp.heads
@@ -891,15 +910,15 @@ class Tower:
                 Bp, cst = ws["Bp"], ws["c_stat"]
                 c_dx = ws["c_dx"]
                 c_dxT = ws["c_dxT"] if dt != F32 else c_dx
-                yield GemmReq(f"{lt}.cdproj", dt, c_dxT, blk["proj"].wt, ws["c_du"], Bp, 4 * d, d, epi=EPI_DQUICKGELU, aux=ws["c_u"], m_real=B)
-                yield GemmReq(f"{lt}.cdfc", dt, ws["c_du"], blk["fc"].wt, ws["c_dh"], Bp, d, 4 * d, m_real=B)
+                yield GemmReq(f"{lt}.cdproj", mdt, c_dxT, blk["proj"].wt, ws["c_du"], Bp, 4 * d, d, epi=EPI_DQUICKGELU, aux=ws["c_u"], m_real=B)
+                yield GemmReq(f"{lt}.cdfc", mdt, ws["c_du"], blk["fc"].wt, ws["c_dh"], Bp, d, 4 * d, m_real=B)
                 yield RowReq(f"{lt}.cdln2", [_lib.row_job(_lib.ROWOP_LN_BWD, B=B, d=d, dt_a=dt, dt_b=dt, a=ws["c_dh"], ld_a=d, b=ws["c_xmid"], ld_b=d,
                                                           gamma=blk["ln_2.w"], mean_in=cst[0], rstd_in=cst[1], out=c_dx, out2=None if dt == F32 else c_dxT,
                                                           ld_c=d, flag=1)])
                 # ... and, on the same pooled rows, the attention branch:
                 # attention branch of the pooled rows: dctx, dQ on B rows; dK, dV on every row; d(LN1 out) = dKV.Wkv (+ dQ.Wq at the pooled rows)
                 wqt = blk["qkv"].wt
-                yield GemmReq(f"{lt}.cdout", dt, c_dxT, blk["out"].wt, ws["c_dctx"], Bp, d, d, m_real=B)
+                yield GemmReq(f"{lt}.cdout", mdt, c_dxT, blk["out"].wt, ws["c_dctx"], Bp, d, d, m_real=B)
                 if rs is None and not pre and ws.get("sp_scratch") is not None and self._stream_pool_shape(L):
                     # the forward ran without K and V (forward_gen): d LN1(x_l) of every row and the pooled queries' gradient from two passes over the stream
                     yield SoloReq(f"{lt}.pdattn", lambda: call("lpi_spool_attn_bwd", B, L, H, blk["qkv_wb"], d, blk["qkv"].wt, 3 * d, x_in, d, st[0], st[1], blk["ln_1.w"],
@@ -909,8 +928,8 @@ class Tower:
                     yield PoolAttnReq(f"{lt}.pdattn", adt, True, B=B, L=L, row_start=rs, H=H, q=ws["c_q"], ldq=d, qkv=qkv, ldqkv=3 * d, idx=pool_idx,
                                       dctx=ws["c_dctx"], lddctx=d, lse=ws["c_lse"], dq=ws["c_dq"], lddq=d, dqkv=dqkv, lddqkv=3 * d, causal=int(sp.causal),
                                       shared_rows=pre, shared_dkv=ws.get("shared_dkv") if pre else None)
-                    yield GemmReq(f"{lt}.dkv", dt, dqkv[:, d:], wqt[:, d:], dh, Mp, d, 2 * d, m_real=M)
-                yield GemmReq(f"{lt}.cdq", dt, ws["c_dq"], wqt[:, :d], ws["c_dh"], Bp, d, d, m_real=B)
+                    yield GemmReq(f"{lt}.dkv", mdt, dqkv[:, d:], wqt[:, d:], dh, Mp, d, 2 * d, m_real=M)
+                yield GemmReq(f"{lt}.cdq", mdt, ws["c_dq"], wqt[:, :d], ws["c_dh"], Bp, d, d, m_real=B)
                 yield RowReq(f"{lt}.sadd1", [_lib.row_job(_lib.ROWOP_SCATTER_ADD, B=B, L=Lx, d=d, dt_a=dt, a=ws["c_dh"], ld_a=d, idx=pidx, out=dh, ld_c=d)])
                 # the gradient stream starts here: LN1's backward WRITES it (no zero-fill of the [M, d] stream), then the residual
                 # path of the pooled rows is added
@@ -922,11 +941,11 @@ class Tower:
                 continue
             if not (i == len(self.blocks) - 1 and POOLED_LAST):
                 du = ws["du"]
-                yield GemmReq(f"{lt}.dproj", dt, dxT, blk["proj"].wt, du, Mp, 4 * d, d, epi=EPI_DQUICKGELU, aux=u, m_real=M)          # d c_proj, * gelu'
-                yield GemmReq(f"{lt}.dfc", dt, du, blk["fc"].wt, dh, Mp, d, 4 * d, m_real=M)                                         # d c_fc
+                yield GemmReq(f"{lt}.dproj", mdt, dxT, blk["proj"].wt, du, Mp, 4 * d, d, epi=EPI_DQUICKGELU, aux=u, m_real=M)          # d c_proj, * gelu'
+                yield GemmReq(f"{lt}.dfc", mdt, du, blk["fc"].wt, dh, Mp, d, 4 * d, m_real=M)                                         # d c_fc
                 yield LnReq(f"{lt}.dln2", "bwd", (dt, dt, xdt), M, d, dh, d, xmid, d, blk["ln_2.w"], st[2], st[3], dx, d,
                             None if dt == F32 else dxT, d, 1)      # dx is None in bf16 mode: dxT accumulates in place
-            yield GemmReq(f"{lt}.dout", dt, dxT, blk["out"].wt, dctx, Mp, d, d, m_real=M)                                         # d out_proj
+            yield GemmReq(f"{lt}.dout", mdt, dxT, blk["out"].wt, dctx, Mp, d, d, m_real=M)                                         # d out_proj
             l0_rows = i == 0 and L0_PROMPT_ROWS and prompts is not None and 0 < P <= 32 and len(self.blocks) > 1
             # first block: only dQ / dK / dV of the prompt rows 1 .. P are read below -> the attention backward skips the row blocks behind them
             if pre:
@@ -948,7 +967,7 @@ class Tower:
                 esz = 4 if dt == F32 else 2
                 yield RowReq(f"{lt}.gath", [_lib.row_job(_lib.ROWOP_GATHER_BATCH_ROWS, B=Bq, L=Lq, row_start=rsq, row0=1, P=P, d=3 * d * esz // 16, a=dqkv,
                                                          ld_a=3 * d * esz // 16, out=pq, ld_c=3 * d * esz // 16)])
-                yield GemmReq(f"{lt}.dqkv_p", dt, pq, blk["qkv"].wt, ph, _pad(Bq * P, 256), d, 3 * d, m_real=Bq * P)
+                yield GemmReq(f"{lt}.dqkv_p", mdt, pq, blk["qkv"].wt, ph, _pad(Bq * P, 256), d, 3 * d, m_real=Bq * P)
                 if dt == BF16 and xdt == F16 and d % 8 == 0:      # the 16-byte half-wave kernel, with the towers' launches paired
                     yield RowReq(f"{lt}.dln1p", [_lib.row_job(_lib.ROWOP_LN_BWD_ROWS_H16, B=Bq, L=Lq, row_start=rsq, row0=1, P=P, d=d, a=ph, ld_a=d, b=x_in, ld_b=d,
                                                               gamma=blk["ln_1.w"], mean_in=st[0], rstd_in=st[1], out2=dxT, ld_c=d, flag=1)])
@@ -956,7 +975,7 @@ class Tower:
                     call("lpi_layernorm_bwd_rows_varlen", dt, dt, xdt, Bq, Lq, rsq, 1, P, d, ph, d, x_in, d, blk["ln_1.w"], st[0], st[1], dx, d,
                          None if dt == F32 else dxT, d, 1, s)
                 continue
-            yield GemmReq(f"{lt}.dqkv", dt, dqkv, blk["qkv"].wt, dh, Mp, d, 3 * d, m_real=M)                                      # d in_proj
+            yield GemmReq(f"{lt}.dqkv", mdt, dqkv, blk["qkv"].wt, dh, Mp, d, 3 * d, m_real=M)                                      # d in_proj
             yield LnReq(f"{lt}.dln1", "bwd", (dt, dt, xdt), M, d, dh, d, x_in, d, blk["ln_1.w"], st[0], st[1], dx, d,
                         None if dt == F32 else dxT, d, 1)
             if prompts is not None and dprompts is not None and 0 < i < depth:
@@ -1114,6 +1133,7 @@ class DualEncoder:
     def encode_image_gen(self, image, prompts=None, depth=1, train=False, normalise=True):
         """GENERATOR form of encode_image (yields its GEMMs, see GemmReq); returns (features, backward context)."""
         cfg, dt, s = self.cfg, self.dt, _stream()
+        mdt = _gemm_code(dt, self.opt)
         self._guard_begin()
         B = image.shape[0]
         u8 = image.dtype == torch.uint8      # decoded pixels: ToTensor + Normalize happen inside the im2col kernel (pixel_lut)
@@ -1132,7 +1152,7 @@ class DualEncoder:
             call("lpi_patchify_u8", dt, B, cfg.image_resolution, cfg.vision_patch_size, image, self.pixel_lut(*self.opt.pixel_stats()), fe["cols"], self.kp, s)
         else:
             call("lpi_patchify", dt, B, cfg.image_resolution, cfg.vision_patch_size, image, fe["cols"], self.kp, s)
-        yield GemmReq(None, dt, fe["cols"], self.conv.w, fe["pe"], fe["cols"].shape[0], d, self.kp, m_real=B * G2)
+        yield GemmReq(None, mdt, fe["cols"], self.conv.w, fe["pe"], fe["cols"].shape[0], d, self.kp, m_real=B * G2)
         call("lpi_vis_assemble_fwd", self.vis.xdt, B, G2, P, d, fe["pe"], d, self.cls, self.vpos, pr, pbs, self.ln_pre[0], self.ln_pre[1],
              ws["x"][0], fe["stat"][0], fe["stat"][1], *self.vis.ln1_stats_out(ws), s)
         xo = yield from self.vis.forward_gen(ws, pr, pbs, depth, train, None, ln1_ready=self.vis.ln1_stats_out(ws)[0] is not None)      # pooled (CLS) rows [Bp, d]
@@ -1146,10 +1166,11 @@ class DualEncoder:
     def _head_fwd_gen(self, hw, xo, ln, proj, B, d, normalise):
         """ln_post / ln_final on the pooled rows, the projection, the L2 normalisation (model.py:255-257, prompt_learner.py:57-63, slinet.py:122,133)."""
         cfg, dt = self.cfg, self.dt
+        mdt = _gemm_code(dt, self.opt)
         E_ = cfg.embed_dim
         yield RowReq("head.ln", [_lib.row_job(_lib.ROWOP_POOL_LN_FWD, B=B, L=1, d=d, dt_a=F32, dt_b=dt, a=xo, gamma=ln[0], beta=ln[1], out=hw["pooled"], ld_c=d,
                                               mean=hw["stat"][0], rstd=hw["stat"][1])])
-        yield GemmReq("head", dt, hw["pooled"], proj.w, hw["feat"], hw["pooled"].shape[0], E_, d)
+        yield GemmReq("head", mdt, hw["pooled"], proj.w, hw["feat"], hw["pooled"].shape[0], E_, d)
         out = torch.empty(B, E_, device=self.device)
         if normalise:
             yield RowReq("head.l2", [_lib.row_job(_lib.ROWOP_L2NORM_FWD, B=B, d=E_, a=hw["feat"], ld_a=E_, out=out, ld_c=E_, mean=hw["inv"])])
@@ -1160,12 +1181,13 @@ class DualEncoder:
     def _head_bwd_gen(self, hw, ws, out, dout, ln, proj, B, d):
         """The backward of _head_fwd_gen: leaves dL/d(pooled output rows) in ws['c_dx'] (and its bf16 copy in ws['c_dxT'])."""
         dt, E_ = self.gdt, self.cfg.embed_dim
+        mdt = _gemm_code(dt, self.opt)
         dout = dout.contiguous().float()
         # L2-norm backward; in the 2-byte modes the same job leaves the bf16 operand of the dgrad GEMM (no separate cast launch)
         yield RowReq("dhead.l2", [_lib.row_job(_lib.ROWOP_L2NORM_BWD, B=B, d=E_, a=out, ld_a=E_, b=dout, ld_b=E_, mean_in=hw["inv"], out=hw["dfeat"], ld_c=E_,
                                                out2=None if dt == F32 else hw["dfeatT"], dt_b=BF16)])
         dfe = hw["dfeat"] if dt == F32 else hw["dfeatT"]
-        yield GemmReq("dhead", dt, dfe, proj.wt, hw["dpooled"], dfe.shape[0], d, E_)
+        yield GemmReq("dhead", mdt, dfe, proj.wt, hw["dpooled"], dfe.shape[0], d, E_)
         yield RowReq("dhead.ln", [_lib.row_job(_lib.ROWOP_POOL_LN_BWD, B=B, L=1, d=d, dt_b=dt, a=hw["dpooled"], ld_a=d, b=ws["c_xout"], gamma=ln[0],
                                                mean_in=hw["stat"][0], rstd_in=hw["stat"][1], out=ws["c_dx"], out2=None if dt == F32 else ws["c_dxT"])])
 
@@ -1234,6 +1256,7 @@ class DualEncoder:
     def encode_text_gen(self, ids, prompts=None, depth=1, train=False, use_ctx=True, normalise=True):
         """GENERATOR form of encode_text; returns (features, backward context)."""
         cfg, dt, s = self.cfg, self.dt, _stream()
+        mdt = _gemm_code(dt, self.opt)
         self._guard_begin()
         packed = ids if isinstance(ids, PackedIds) else None
         if packed is not None:
