@@ -19,6 +19,19 @@
  *     nn.MultiheadAttention, models/clip/model.py:253; the arithmetic is layout independent);
  *   - matrices handed to lpi_gemm_nt are padded by the caller: M % 128 == 0, N % 128 == 0,
  *     K % (128 / sizeof(element)) == 0, all leading dimensions 16-byte aligned.
+ *   - DEAD REGIONS.  A call is often handed more memory than it may use; what it does not use may hold anything, NaN included, and no
+ *     live output depends on it (tests/test_dead_memory_gpu.py fills each of these with NaN and asks for the same bits):
+ *       token rows behind the batch: rows >= B*L (ragged: >= row_start[B]) of qkv, ctx, dctx, x, mean, rstd — arenas are padded to 256 rows;
+ *       ragged batches: the lse / delta entries l >= L_b of sample b, and ids[b, l >= L_b] of lpi_txt_embed_fwd_varlen;
+ *       `delta` of every attention backward on entry, `scratch` of lpi_spool_attn_fwd on entry, and its second quarter and second half
+ *         on entry to lpi_spool_attn_bwd;
+ *       lpi_attn_pooled_*: columns 0..d of qkv (q arrives separately) and, with causal != 0, the K / V rows j > idx[b] of sample b;
+ *       the LN operand block: entries M..ldr-1 of its mean and rstd segments; lpi_ln_stats_finalize: entries rows..ld-1 of every slot;
+ *       kernels with a row map (row0 / P, or idx): every row of x, mean, rstd, dx0, src that the map does not name;
+ *       padded matrices: rows and columns >= n of the logits of lpi_clip_loss_local / lpi_ce_rows_fwd_bwd, the columns between n_cols / E
+ *         and the leading dimension of lpi_retrieval_rank, lpi_topk and lpi_l1_task_id.
+ *     PRESERVED (never written): the rows of dx, dx_cast, dst, out_mean / out_rstd that a row map does not name; columns 0..d of the pooled
+ *     backward's dqkv; rows of x0 behind row_start[B]; columns >= n and rows >= nloc (rows >= `rows`) of g, gt and dlogits.
  */
 #ifndef LPI_HIP_H
 #define LPI_HIP_H

@@ -667,7 +667,9 @@ class Tower:
             return ws
         # an arena serves any batch of its mode that FITS it (B <= its batch capacity, L <= its token capacity): the odd last batch of an epoch
         # (DataLoader drop_last=False) and a shorter longest caption only re-bind row counts — every [M, *] buffer is used by its first rows,
-        # the per-sample ones as flat storage; rows past the bound batch hold stale but finite data that no kernel reads into a live row.
+        # the per-sample ones as flat storage; what lies past the bound batch (rows >= M, samples >= B, the statistics and lse / delta entries that
+        # go with them) is stale and may hold anything, NaN included: no kernel reads it into a live value (tests/test_dead_memory_gpu.py fills it
+        # with NaN between a 4-sample and a 3-sample step and asks for the bits of a fresh encoder).
         for (bcap, tr), ws in self._ws.items():
             if tr == train and bcap >= B and ws["Lcap"] >= L:
                 return bind(ws, L)
