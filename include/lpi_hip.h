@@ -724,6 +724,7 @@ int lpi_bpe_tokenize(void* handle, const char* const* texts, int n, int context_
 #define LPI_GEMM_K_ROWS 4       /* gemm_rows_kernel: few-row GEMM, 32x32 tiles over the whole K   */
 #define LPI_GEMM_K_MX8 5        /* gemm_mx8_kernel: MX-FP8 operands, 128x128 tiles (lpi_gemm_nt_mx8) */
 #define LPI_GEMM_K_X3 6         /* gemm_nt_kernel / gemm256_kernel on split-bf16 operands (LPI_F32X3) */
+#define LPI_GEMM_K_MX8_256 7    /* gemm256_mx8_kernel: MX-FP8 operands, phased 256x256 tiles (lpi_gemm_nt_mx8_256) */
 int lpi_gemm_last_kernel(void);
 
 /* ---- MX-FP8 forward (csrc/gemm_mx8.hip, csrc/mx8_rows.hip): the four block GEMMs of the no-grad forwards on the block-scaled FP8 matrix instruction ----
@@ -744,6 +745,16 @@ int lpi_gemm_mx8_ok(int M, int N, int K);
 int lpi_gemm_nt_mx8(int c_dtype, int M, int N, int K, const void* A, int lda, const void* a_scales, int ldas, const void* B, int ldb,
                     const void* b_scales, int ldbs, void* C, int ldc, void* c_scales, int ldcs, const float* bias, const void* residual, int ldr,
                     int epilogue, float alpha, void* stream);
+/* 1 if lpi_gemm_nt_mx8_256 takes the shape: M, N positive multiples of 256 and K a positive multiple of 256 (an even number >= 2 of K-tiles of 128 elements),
+ * else 0.  Host only: no GPU call. */
+int lpi_gemm_mx8_256_ok(int M, int N, int K);
+/* lpi_gemm_nt_mx8 on the phased 256x256 tile (csrc/gemm256_tile.h on one-byte elements: LDS-DMA ring with counted waits, the scale bytes by LDS-DMA beside
+ * the elements): the same arguments, meaning, epilogues, outputs and refusals, and the SAME BITS — each output element is the same sequence of block-scaled
+ * instructions over K.  LPI_EINVAL before any launch for a shape lpi_gemm_mx8_256_ok refuses.  One launch, one tile per workgroup, attributed to
+ * LPI_GEMM_K_MX8_256.  lpi_gemm_nt_mx8 itself always runs the 128x128 kernel. */
+int lpi_gemm_nt_mx8_256(int c_dtype, int M, int N, int K, const void* A, int lda, const void* a_scales, int ldas, const void* B, int ldb,
+                        const void* b_scales, int ldbs, void* C, int ldc, void* c_scales, int ldcs, const float* bias, const void* residual, int ldr,
+                        int epilogue, float alpha, void* stream);
 /* rows of x (`x_dtype`: LPI_F32 | LPI_BF16 | LPI_F16, [rows, ldx]) -> q (e4m3 [rows, ldq]) + scales ([rows, lds >= K/32]); K a multiple of 32. */
 int lpi_mx8_quantize(int x_dtype, int rows, int K, const void* x, int ldx, void* q, int ldq, void* scales, int lds, void* stream);
 /* LayerNorm (f32 two-sweep statistics in registers, eps 1e-5, affine in f32) of the rows of the residual stream x (`x_dtype`: LPI_F16 | LPI_F32) written

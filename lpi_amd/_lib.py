@@ -18,6 +18,7 @@ GEMM_K_128, GEMM_K_256, GEMM_K_256_TAIL, GEMM_K_256X128, GEMM_K_ROWS = 0, 1, 2, 
 GEMM_K_MX8 = 5      # LPI_GEMM_K_MX8 of lpi_gemm_last_kernel
 F32X3 = 4      # LPI_F32X3: lpi_gemm_nt(_grouped)'s dtype for f32 operands multiplied as split bf16 (hi.hi + hi.lo + lo.hi); c_dtype F32
 GEMM_K_X3 = 6      # LPI_GEMM_K_X3 of lpi_gemm_last_kernel
+GEMM_K_MX8_256 = 7      # LPI_GEMM_K_MX8_256 of lpi_gemm_last_kernel
 EPI_NONE, EPI_QUICKGELU, EPI_DQUICKGELU, EPI_LN, EPI_LN_QUICKGELU, EPI_RES_ROWSTATS = 0, 1, 2, 3, 4, 5
 
 
@@ -53,6 +54,8 @@ SIGNATURES = {
     # MX-FP8 forward (gemm_mx8.hip, mx8_rows.hip)
     "lpi_gemm_mx8_ok": [_I, _I, _I],
     "lpi_gemm_nt_mx8": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _F, _P],
+    "lpi_gemm_mx8_256_ok": [_I, _I, _I],
+    "lpi_gemm_nt_mx8_256": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _F, _P],
     "lpi_mx8_quantize": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "lpi_layernorm_mx8_fwd": [_I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
     "lpi_layernorm_fwd": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],
@@ -161,7 +164,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_bpe_create": c_void_p, "lpi_bpe_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 611
+EXPECTED_ABI = 612
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -28,6 +28,24 @@ namespace {
 
 using namespace t256;
 
+// workgroup id -> origin of its tile: the bijective XCD remap (blocks that share an XCD, bid % 8, get a contiguous run of tiles), then groups of
+// group_m row tiles walked column by column
+__device__ __forceinline__ void tile_origin(int tiles_m, int tiles_n, int group_m, int& m0, int& n0)
+{
+    const int nwg = tiles_m * tiles_n;
+    int bid = blockIdx.x;
+    {
+        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    const int group = bid / (group_m * tiles_n);
+    const int first_m = group * group_m;
+    const int gsz = min(tiles_m - first_m, group_m);
+    const int in_group = bid - group * group_m * tiles_n;
+    m0 = (first_m + in_group % gsz) * T256;
+    n0 = (in_group / gsz) * T256;
+}
+
 template <typename T, typename TC, int EPI, bool RES, bool SAVE_U>
 __global__ __launch_bounds__(NTHR, 2) void gemm256_kernel(
     int M, int N, int K, const T* __restrict__ A, int lda, const T* __restrict__ B, int ldb,
@@ -44,22 +62,22 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_kernel(
     if (stagger > 0 && blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {
         for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
     }
-    const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {   // bijective XCD remap: blocks that share an XCD (bid % 8) get a contiguous run of tiles
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int GROUP_M = group_m;
-    const int group = bid / (GROUP_M * tiles_n);
-    const int first_m = group * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int in_group = bid - group * GROUP_M * tiles_n;
-    const int tm = first_m + in_group % gsz;
-    const int tn = in_group / gsz;
-    const int m0 = tm * T256, n0 = tn * T256;
-
+    int m0, n0;
+    tile_origin(tiles_m, tiles_n, group_m, m0, n0);
     t256::tile<T, TC, EPI, RES, SAVE_U>(m0, n0, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, smem);
+}
+
+// The same launch on MX-FP8 operands (lpi_gemm_nt_mx8_256): one tile per workgroup, no stagger, no aux; the scale arrays travel in `mx`, which the other
+// element types' kernel does not have.
+template <typename TC, int EPI, bool RES>
+__global__ __launch_bounds__(NTHR, 2) void gemm256_mx8_kernel(
+    int K, const mx8_t* __restrict__ A, int lda, const mx8_t* __restrict__ B, int ldb, TC* __restrict__ C, int ldc, const float* __restrict__ bias,
+    const float* __restrict__ residual, int ldr, float alpha, int tiles_m, int tiles_n, int group_m, Mx8Side mx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int m0, n0;
+    tile_origin(tiles_m, tiles_n, group_m, m0, n0);
+    t256::tile<mx8_t, TC, EPI, RES, false>(m0, n0, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, nullptr, 0, alpha, smem, mx);
 }
 
 // Hybrid launch for tile counts that leave a short last round: the first n_full (a multiple of 256) tiles run as 256x256 tiles,
@@ -132,6 +150,21 @@ int launch256_impl(int M, int N, int K, const void* A, int lda, const void* B, i
     lpi_note_gemm_kernel(kIsX3<T> ? LPI_GEMM_K_X3 : LPI_GEMM_K_256);
     LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES, s, M, N, K, (const T*)A, lda, (const T*)B, ldb, (TC*)C, ldc, bias, residual,
                ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn, 0, g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8);
+    LPI_CHECK_LAST();
+    return 0;
+}
+
+template <typename TC, int EPI, bool RES>
+int launch256_mx8(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias, const void* residual, int ldr,
+                  float alpha, const Mx8Side& mx, hipStream_t s)
+{
+    const int tm = M / T256, tn = N / T256;
+    auto kern = gemm256_mx8_kernel<TC, EPI, RES>;
+    static LdsOnce once;
+    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES_MX8)) return e;
+    lpi_note_gemm_kernel(LPI_GEMM_K_MX8_256);
+    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES_MX8, s, K, (const mx8_t*)A, lda, (const mx8_t*)B, ldb, (TC*)C, ldc, bias, (const float*)residual, ldr,
+               alpha, tm, tn, g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8, mx);
     LPI_CHECK_LAST();
     return 0;
 }
@@ -212,4 +245,43 @@ int lpi_gemm256_launch(int dtype, int c_dtype, int M, int N, int K, const void* 
     if (dtype == LPI_F16 && c_dtype == LPI_F32)
         return dispatch256<f16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
     return LPI_ENOSYS;
+}
+
+// ---- MX-FP8 operands on the 256x256 tile (include/lpi_hip.h) ----
+extern "C" int lpi_gemm_mx8_256_ok(int M, int N, int K)
+{
+    if (M <= 0 || N <= 0 || K <= 0 || M % T256 || N % T256 || K % ROWB) return 0;      // a staged row is ROWB = 128 elements of K
+    const int nk = K / ROWB;
+    return nk >= 2 && (nk % 2) == 0 ? 1 : 0;
+}
+
+extern "C" int lpi_gemm_nt_mx8_256(int c_dtype, int M, int N, int K, const void* A, int lda, const void* a_scales, int ldas, const void* B, int ldb,
+                                   const void* b_scales, int ldbs, void* C, int ldc, void* c_scales, int ldcs, const float* bias, const void* residual,
+                                   int ldr, int epilogue, float alpha, void* stream)
+{
+    if (!lpi_gemm_mx8_256_ok(M, N, K)) return LPI_EINVAL;
+    if (int e = mx8_gemm_check_args(c_dtype, N, K, A, lda, a_scales, ldas, B, ldb, b_scales, ldbs, C, ldc, c_scales, ldcs, bias, residual, ldr, epilogue))
+        return e;
+    const Mx8Side mx = {(const uint8_t*)a_scales, ldas, (const uint8_t*)b_scales, ldbs, (uint8_t*)c_scales, ldcs};
+    hipStream_t s = (hipStream_t)stream;
+#define MXG(TC, EPI, RES) return launch256_mx8<TC, EPI, RES>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, alpha, mx, s)
+    const bool gelu = epilogue == LPI_EPI_QUICKGELU;
+    switch (c_dtype) {
+    case LPI_F32:
+        if (gelu) MXG(float, LPI_EPI_QUICKGELU, false);
+        if (residual) MXG(float, LPI_EPI_NONE, true);
+        MXG(float, LPI_EPI_NONE, false);
+    case LPI_BF16:
+        if (gelu) MXG(bf16_t, LPI_EPI_QUICKGELU, false);
+        MXG(bf16_t, LPI_EPI_NONE, false);
+    case LPI_F16:
+        if (gelu) MXG(f16_t, LPI_EPI_QUICKGELU, false);
+        if (residual) MXG(f16_t, LPI_EPI_NONE, true);
+        MXG(f16_t, LPI_EPI_NONE, false);
+    case LPI_MX8:
+        if (gelu) MXG(mx8_out_t, LPI_EPI_QUICKGELU, false);
+        MXG(mx8_out_t, LPI_EPI_NONE, false);
+    }
+#undef MXG
+    return LPI_EINVAL;
 }

@@ -207,19 +207,8 @@ extern "C" int lpi_gemm_nt_mx8(int c_dtype, int M, int N, int K, const void* A, 
                                int ldr, int epilogue, float alpha, void* stream)
 {
     if (!lpi_gemm_mx8_ok(M, N, K)) return LPI_EINVAL;
-    if (!A || !B || !C || !a_scales || !b_scales) return LPI_EINVAL;
-    if (epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_QUICKGELU) return LPI_EINVAL;
-    if (c_dtype != LPI_F32 && c_dtype != LPI_BF16 && c_dtype != LPI_F16 && c_dtype != LPI_MX8) return LPI_EINVAL;
-    if (lda < K || ldb < K || (lda & 15) || (ldb & 15) || ldas < K / 32 || ldbs < K / 32 || (ldas & 3) || (ldbs & 3) || ldc < N) return LPI_EINVAL;
-    if ((((uintptr_t)A | (uintptr_t)B) & 15) || (((uintptr_t)a_scales | (uintptr_t)b_scales) & 3)) return LPI_EINVAL;
-    if (bias && ((uintptr_t)bias & 15)) return LPI_EINVAL;
-    const int csz = c_dtype == LPI_F32 ? 4 : c_dtype == LPI_MX8 ? 1 : 2;
-    if (((uintptr_t)C & 15) || (ldc * csz) % (4 * csz)) return LPI_EINVAL;
-    if (c_dtype == LPI_MX8 && (!c_scales || ldcs < N / 32 || residual)) return LPI_EINVAL;
-    if (residual) {      // the residual has C's type: fp16 with an fp16 C (the residual stream of the 2-byte modes), f32 with an f32 C
-        if (epilogue != LPI_EPI_NONE || c_dtype == LPI_BF16) return LPI_ENOSYS;
-        if (ldr < N || (ldr & 3) || ((uintptr_t)residual & 15)) return LPI_EINVAL;
-    }
+    if (int e = mx8_gemm_check_args(c_dtype, N, K, A, lda, a_scales, ldas, B, ldb, b_scales, ldbs, C, ldc, c_scales, ldcs, bias, residual, ldr, epilogue))
+        return e;
     hipStream_t s = (hipStream_t)stream;
 #define MXG(TC, EPI, RES) return launch<TC, EPI, RES>(M, N, K, A, lda, a_scales, ldas, B, ldb, b_scales, ldbs, C, ldc, c_scales, ldcs, bias, residual, ldr, alpha, s)
     const bool gelu = epilogue == LPI_EPI_QUICKGELU;

@@ -7,6 +7,41 @@
 // no element exceeds 448, so the conversion never saturates.
 #pragma once
 #include "common.h"
+#include "gemm_epilogue.h"
+
+// Element TAG of size 1 for the phased 256x256 tile (gemm256_tile.h): staging, swizzle and pointer arithmetic see a one-byte element, so a staged
+// 128-byte row is 128 elements = one block-scaled instruction's K.  mx8_out_t is the C type tag of an MX output (e4m3 bytes + scales along N).
+struct mx8_t { uint8_t v; };
+struct mx8_out_t { uint8_t v; };
+template <typename T> inline constexpr bool kIsMx8 = false;
+template <> inline constexpr bool kIsMx8<mx8_t> = true;
+template <> struct Elem<mx8_t> {
+    static constexpr int DT = LPI_MX8;
+    static constexpr int EPC = 16;
+};
+template <> struct AuxT<mx8_t> { typedef bf16_t type; };      // no MX epilogue takes an aux: the type only completes the shared signatures
+// what an MX GEMM carries beside the element pointers: the operands' scale arrays and, for an MX output, C's
+struct Mx8Side {
+    const uint8_t* a_scales; int ldas;
+    const uint8_t* b_scales; int ldbs;
+    uint8_t* c_scales; int ldcs;
+};
+typedef __attribute__((ext_vector_type(8))) int mx8_i32x8;
+// acc += W (x) X over 128 K elements: `w`, `x` = mx8_operand of the lane's chunks g and 4 + g of the weight / activation row, e4m3 both; the scale a lane holds
+// is that of row l & 15, K block l >> 4 (gemm_mx8.hip has the measured operand map).
+__device__ __forceinline__ mx8_i32x8 mx8_operand(const Chunk& c0, const Chunk& c1) {
+    return mx8_i32x8{(int)c0.u.x, (int)c0.u.y, (int)c0.u.z, (int)c0.u.w, (int)c1.u.x, (int)c1.u.y, (int)c1.u.z, (int)c1.u.w};
+}
+// `ws`, `xs`: the registers that hold the lane's scale bytes, the instruction's in byte `wsel` / `xsel` (opsel: an immediate, hence the switch — the callers'
+// loops are unrolled and it folds)
+__device__ __forceinline__ void mx8_mma(f32x4& acc, const mx8_i32x8& w, const mx8_i32x8& x, int wsel, int ws, int xsel, int xs) {
+#define LPI_MX8_MMA(I) case I: acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, acc, 0, 0, (I) >> 2, ws, (I) & 3, xs); break;
+    switch (wsel * 4 + xsel) {
+        LPI_MX8_MMA(0) LPI_MX8_MMA(1) LPI_MX8_MMA(2) LPI_MX8_MMA(3) LPI_MX8_MMA(4) LPI_MX8_MMA(5) LPI_MX8_MMA(6) LPI_MX8_MMA(7)
+        LPI_MX8_MMA(8) LPI_MX8_MMA(9) LPI_MX8_MMA(10) LPI_MX8_MMA(11) LPI_MX8_MMA(12) LPI_MX8_MMA(13) LPI_MX8_MMA(14) LPI_MX8_MMA(15)
+    }
+#undef LPI_MX8_MMA
+}
 
 __device__ __forceinline__ int mx8_scale_byte(float amax) {
     const uint32_t b = __float_as_uint(amax);      // amax >= 0
@@ -28,4 +63,25 @@ __device__ __forceinline__ float mx8_max8(float v) {
     v = fmaxf(v, dpp_move<0x4E>(v));
     v = fmaxf(v, dpp_move<0x141>(v));
     return v;
+}
+
+// Host: everything lpi_gemm_nt_mx8 and lpi_gemm_nt_mx8_256 check beside their shape predicates; 0 or the code to return before any launch.
+inline int mx8_gemm_check_args(int c_dtype, int N, int K, const void* A, int lda, const void* a_scales, int ldas, const void* B, int ldb,
+                               const void* b_scales, int ldbs, const void* C, int ldc, const void* c_scales, int ldcs, const float* bias,
+                               const void* residual, int ldr, int epilogue)
+{
+    if (!A || !B || !C || !a_scales || !b_scales) return LPI_EINVAL;
+    if (epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_QUICKGELU) return LPI_EINVAL;
+    if (c_dtype != LPI_F32 && c_dtype != LPI_BF16 && c_dtype != LPI_F16 && c_dtype != LPI_MX8) return LPI_EINVAL;
+    if (lda < K || ldb < K || (lda & 15) || (ldb & 15) || ldas < K / 32 || ldbs < K / 32 || (ldas & 3) || (ldbs & 3) || ldc < N) return LPI_EINVAL;
+    if ((((uintptr_t)A | (uintptr_t)B) & 15) || (((uintptr_t)a_scales | (uintptr_t)b_scales) & 3)) return LPI_EINVAL;
+    if (bias && ((uintptr_t)bias & 15)) return LPI_EINVAL;
+    const int csz = c_dtype == LPI_F32 ? 4 : c_dtype == LPI_MX8 ? 1 : 2;
+    if (((uintptr_t)C & 15) || (ldc * csz) % (4 * csz)) return LPI_EINVAL;
+    if (c_dtype == LPI_MX8 && (!c_scales || ldcs < N / 32 || residual)) return LPI_EINVAL;
+    if (residual) {      // the residual has C's type: fp16 with an fp16 C (the residual stream of the 2-byte modes), f32 with an f32 C
+        if (epilogue != LPI_EPI_NONE || c_dtype == LPI_BF16) return LPI_ENOSYS;
+        if (ldr < N || (ldr & 3) || ((uintptr_t)residual & 15)) return LPI_EINVAL;
+    }
+    return 0;
 }

@@ -83,6 +83,10 @@ class EngineOptions:
         retrieval evaluation, which never need a gradient.  LayerNorm writes the MX operand directly (lpi_layernorm_mx8_fwd), c_fc's QuickGELU epilogue
         writes c_proj's; attention, the fp16 residual stream, the patch embedding, the pooled last block and the heads are what the 2-byte mode runs.
         train=True forwards and every backward are untouched.  2-byte modes only (ValueError with dtype 'f32'); +1 byte per parameter of the block matrices.
+    mx8_tile256 (means something only with mx8_forward): the MX GEMMs whose padded (M, N, K) lpi_gemm_mx8_256_ok takes — M, N and K multiples of 256 — go
+        out as lpi_gemm_nt_mx8_256, the phased 256x256 tile, instead of lpi_gemm_nt_mx8's 128x128 one; every other one stays there.  The same bits (each
+        output element is the same sequence of block-scaled instructions over K), the same launches and workspace.  False issues lpi_gemm_nt_mx8 everywhere
+        (the other arm of the exactness test).
     gemm_bf16x3: the f32 mode's GEMMs of both towers (forward and dgrad, train=True and train=False, the patch embedding by the same rule of shape) that go
         to lpi_gemm_nt go out with the operand code LPI_F32X3: every operand element is split in registers into hi + lo bf16 and a product is
         hi.hi + hi.lo + lo.hi on the bf16 matrix instruction with f32 accumulation — about 2^-16 per product where f32 has 2^-24 and bf16 2^-8.  Memory
@@ -98,6 +102,7 @@ class EngineOptions:
     qkv_grouped: bool = False
     pixel_norm: object = "imagenet"
     mx8_forward: bool = False
+    mx8_tile256: bool = True
     gemm_bf16x3: bool = False
 
     def __post_init__(self):
@@ -399,7 +404,7 @@ class PoolAttnReq(Req):
 
 
 class Mx8Req(Req):
-    """A launch of the MX-FP8 forward (EngineOptions.mx8_forward): `name` = lpi_layernorm_mx8_fwd | lpi_mx8_quantize | lpi_gemm_nt_mx8, args = its arguments
+    """A launch of the MX-FP8 forward (EngineOptions.mx8_forward): `name` = lpi_layernorm_mx8_fwd | lpi_mx8_quantize | lpi_gemm_nt_mx8 | lpi_gemm_nt_mx8_256, args = its arguments
     before the stream.  Untagged: run_lockstep issues it alone and only its tower advances (the towers meet again at the attention request)."""
     __slots__ = ("tag", "name", "args", "m_real")
     optional = True
@@ -408,7 +413,7 @@ class Mx8Req(Req):
         self.tag, self.name, self.args, self.m_real = None, name, args, m_real
 
     def issue(self):
-        prof = GEMM_PROFILE if self.name == "lpi_gemm_nt_mx8" else None
+        prof = GEMM_PROFILE if self.name in ("lpi_gemm_nt_mx8", "lpi_gemm_nt_mx8_256") else None
         if prof is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -594,6 +599,7 @@ class Tower:
         if opt.mx8_forward and dt == F32:
             raise ValueError("mx8_forward is an option of the 2-byte modes")
         self.mx8 = mx8 = bool(opt.mx8_forward)
+        self.mx8_tile256 = bool(opt.mx8_tile256)
         if mx8 and spec.width % 128:
             raise ValueError(f"mx8_forward: tower width {spec.width} is not a multiple of 128")
         d_, H_ = spec.width, spec.heads
@@ -786,19 +792,20 @@ class Tower:
             if self.mx8 and not train and not (i == len(self.blocks) - 1 and POOLED_LAST):
                 # MX-FP8 forward of a full block (EngineOptions.mx8_forward): LN -> MX, four block-scaled GEMMs, attention on the 2-byte q / k / v
                 m, xc = ws["mx"], _cdt(x_in)
-                G = "lpi_gemm_nt_mx8"
+                ok256 = _lib.load().lpi_gemm_mx8_256_ok if self.mx8_tile256 else (lambda *shape: 0)
+                G = lambda N, K: "lpi_gemm_nt_mx8_256" if ok256(Mp, N, K) else "lpi_gemm_nt_mx8"      # the same arguments, the same bits
                 qw, ow, fw, pw = blk["qkv"], blk["out"], blk["fc"], blk["proj"]
                 yield Mx8Req("lpi_layernorm_mx8_fwd", xdt, M, d, x_in, d, blk["ln_1.w"], blk["ln_1.b"], m["h"], d, m["hs"], d // 32, None, None)
-                yield Mx8Req(G, _cdt(qkv), Mp, 3 * d, d, m["h"], d, m["hs"], d // 32, qw.w8, d, qw.w8s, d // 32, qkv, 3 * d, None, 0, qw.b, None, 0,
+                yield Mx8Req(G(3 * d, d), _cdt(qkv), Mp, 3 * d, d, m["h"], d, m["hs"], d // 32, qw.w8, d, qw.w8s, d // 32, qkv, 3 * d, None, 0, qw.b, None, 0,
                              EPI_NONE, 1.0, m_real=M)
                 yield AttnFwdReq(f"{lt}.attn", dt, B, L, rs, H, qkv, 3 * d, ctx, d, lse, int(sp.causal), pre, self.qkv_lay if blk["grouped"] else None)
                 yield Mx8Req("lpi_mx8_quantize", dt, M, d, ctx, d, m["ctx"], d, m["ctxs"], d // 32)
-                yield Mx8Req(G, xc, Mp, d, d, m["ctx"], d, m["ctxs"], d // 32, ow.w8, d, ow.w8s, d // 32, xmid, d, None, 0, ow.b, x_in, d, EPI_NONE, 1.0,
+                yield Mx8Req(G(d, d), xc, Mp, d, d, m["ctx"], d, m["ctxs"], d // 32, ow.w8, d, ow.w8s, d // 32, xmid, d, None, 0, ow.b, x_in, d, EPI_NONE, 1.0,
                              m_real=M)
                 yield Mx8Req("lpi_layernorm_mx8_fwd", xdt, M, d, xmid, d, blk["ln_2.w"], blk["ln_2.b"], m["h"], d, m["hs"], d // 32, None, None)
-                yield Mx8Req(G, _lib.MX8, Mp, 4 * d, d, m["h"], d, m["hs"], d // 32, fw.w8, d, fw.w8s, d // 32, m["g"], 4 * d, m["gs"], 4 * d // 32, fw.b,
+                yield Mx8Req(G(4 * d, d), _lib.MX8, Mp, 4 * d, d, m["h"], d, m["hs"], d // 32, fw.w8, d, fw.w8s, d // 32, m["g"], 4 * d, m["gs"], 4 * d // 32, fw.b,
                              None, 0, EPI_QUICKGELU, 1.0, m_real=M)
-                yield Mx8Req(G, xc, Mp, d, 4 * d, m["g"], 4 * d, m["gs"], 4 * d // 32, pw.w8, 4 * d, pw.w8s, 4 * d // 32, x_out, d, None, 0, pw.b, xmid, d,
+                yield Mx8Req(G(d, 4 * d), xc, Mp, d, 4 * d, m["g"], 4 * d, m["gs"], 4 * d // 32, pw.w8, 4 * d, pw.w8s, 4 * d // 32, x_out, d, None, 0, pw.b, xmid, d,
                              EPI_NONE, 1.0, m_real=M)
                 have_ln1 = False      # no row-statistics epilogue on this path: the next block (the pooled last one) takes its statistics pass
                 continue

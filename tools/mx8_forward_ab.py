@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
 """EngineOptions.mx8_forward against the 2-byte forward, one process, one GPU, random non-zero data (synth weights and images, ViT-B/16, 256 pairs):
 
-  rate    the forward-only encode (both towers in lock step + the cosine matrix, as bench.py --fwd-only runs it) with the option off and on,
-          interleaved off / on / off / on in ONE process (boxes differ by several percent: only a same-box comparison means anything);
-  gemm    HIP-event times of the four block GEMM shapes alone, bf16 kernel against MX kernel with the epilogues the engine uses, and the GB/s of the
-          stand-alone quantiser and of LayerNorm -> MX;
-  error   the features of the option (and of plain bf16 mode) against the f32 engine on the same inputs.
+  rate    the forward-only encode (both towers in lock step + the cosine matrix, as bench.py --fwd-only runs it) in three arms — option off, on with
+          mx8_tile256=False (the 128x128 MX kernel everywhere), on (the 256x256 MX kernel where the engine's rule sends it) — interleaved round by
+          round in ONE process (boxes differ by several percent: only a same-box comparison means anything);
+  gemm    HIP-event times of the four block GEMM shapes alone, bf16 kernel / MX 128x128 (lpi_gemm_nt_mx8) / MX 256x256 (lpi_gemm_nt_mx8_256) with the
+          epilogues the engine uses, the three arms interleaved round by round, and the GB/s of the stand-alone quantiser and of LayerNorm -> MX;
+  error   the features of the option (and of plain bf16 mode) against the f32 engine on the same inputs, and whether the two MX arms give the same bits.
 
     python tools/mx8_forward_ab.py [--batch 256] [--rounds 4] [--steps 10]
 
-writes profiles/mx8_forward_ab.json.  Every step is a child process under its own `timeout -k 10`; the first one that fails ends the run."""
+writes profiles/mx8_tile256_ab.json (profiles/mx8_forward_ab.json is the two-arm record of the run that introduced the option).  Every step is a child process under its own `timeout -k 10`; the first one that fails ends the run."""
 import argparse
 import json
 import os
@@ -43,7 +44,8 @@ def step_rate(a):
     cfg, img, ids, fac, PackedIds = _inputs(a.batch)
     sd = synth.clip_state_dict(cfg)
     pids = PackedIds(ids, 17).to(DEV)
-    encs = {on: DualEncoder(cfg, sd, dtype="bf16", device=DEV, options=EngineOptions(mx8_forward=on)) for on in (False, True)}
+    arms = {"off": EngineOptions(), "on_128": EngineOptions(mx8_forward=True, mx8_tile256=False), "on": EngineOptions(mx8_forward=True)}
+    encs = {k: DualEncoder(cfg, sd, dtype="bf16", device=DEV, options=o) for k, o in arms.items()}
 
     def run(enc, n):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
@@ -55,15 +57,17 @@ def step_rate(a):
         torch.cuda.synchronize()
         return [ev[i].elapsed_time(ev[i + 1]) for i in range(n)]
 
-    for on in (False, True):
-        run(encs[on], 3)
-    ms = {False: [], True: []}
+    for k in arms:
+        run(encs[k], 3)
+    ms = {k: [] for k in arms}
     for _ in range(a.rounds):
-        for on in (False, True):
-            ms[on].append(float(np.median(run(encs[on], a.steps))))
-    rec = {("on" if on else "off"): {"median_ms_per_round": [round(v, 3) for v in ms[on]], "median_ms": round(float(np.median(ms[on])), 3),
-                                     "pairs_per_s": round(a.batch / (1e-3 * float(np.median(ms[on]))), 1)} for on in (False, True)}
+        for k in arms:
+            ms[k].append(float(np.median(run(encs[k], a.steps))))
+    rec = {k: {"median_ms_per_round": [round(v, 3) for v in ms[k]], "median_ms": round(float(np.median(ms[k])), 3),
+               "pairs_per_s": round(a.batch / (1e-3 * float(np.median(ms[k]))), 1)} for k in arms}
     rec["speedup_on_over_off"] = round(rec["off"]["median_ms"] / rec["on"]["median_ms"], 4)
+    rec["speedup_on_128_over_off"] = round(rec["off"]["median_ms"] / rec["on_128"]["median_ms"], 4)
+    rec["speedup_on_over_on_128"] = round(rec["on_128"]["median_ms"] / rec["on"]["median_ms"], 4)
     rec["workload"] = f"{MODEL}, {a.batch} pairs, depth 3, r 4, packed text with 17 shared positions, forward-only encode + cosine matrix, bf16 mode"
     return rec
 
@@ -90,7 +94,8 @@ def step_gemm(a):
         torch.cuda.synchronize()
         return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(n)]))
 
-    out = {"M": M, "shapes": {}}
+    lib = _lib.load()
+    out = {"M": M, "rounds": a.rounds, "launches_per_round": a.steps, "shapes": {}}
     for name, N, K, epi, res, cdt in (("in_proj", 3 * d, d, E.EPI_NONE, False, torch.bfloat16), ("out_proj", d, d, E.EPI_NONE, True, torch.float16),
                                       ("c_fc", 4 * d, d, E.EPI_QUICKGELU, False, torch.bfloat16), ("c_proj", d, 4 * d, E.EPI_NONE, True, torch.float16)):
         x = torch.randn(M, K, generator=g, device=DEV)
@@ -99,20 +104,32 @@ def step_gemm(a):
         r = torch.randn(M, N, generator=g, device=DEV).half() if res else None
         xb, wb = x.bfloat16(), w.bfloat16()
         c = torch.zeros(M, N, dtype=cdt, device=DEV)
-        t16 = timed(lambda: E.gemm(BF16, xb, wb, c, M, N, K, bias=bias, residual=r, epi=epi))
-        k16 = int(_lib.load().lpi_gemm_last_kernel())
         xq, xs = E.mx8_quantize(x)
         wq, wsc = E.mx8_quantize(w)
         mx_out = name == "c_fc"      # the engine's c_fc writes c_proj's MX operand
         cq = torch.zeros(M, N, dtype=torch.uint8, device=DEV) if mx_out else c
         cs = torch.zeros(M, N // 32, dtype=torch.uint8, device=DEV) if mx_out else None
         cd = MX8 if mx_out else (F16 if cdt == torch.float16 else BF16)
-        t8 = timed(lambda: call("lpi_gemm_nt_mx8", cd, M, N, K, xq, K, xs, K // 32, wq, K, wsc, K // 32, cq, N, cs, N // 32 if mx_out else 0, bias, r,
-                                N if res else 0, epi, 1.0, st()))
+
+        def mx(entry):
+            return lambda: call(entry, cd, M, N, K, xq, K, xs, K // 32, wq, K, wsc, K // 32, cq, N, cs, N // 32 if mx_out else 0, bias, r, N if res else 0,
+                                epi, 1.0, st())
+        arms = {"bf16": lambda: E.gemm(BF16, xb, wb, c, M, N, K, bias=bias, residual=r, epi=epi), "mx8_128": mx("lpi_gemm_nt_mx8"),
+                "mx8_256": mx("lpi_gemm_nt_mx8_256")}
+        ms, kinds = {k: [] for k in arms}, {}
+        for _ in range(a.rounds):      # the arms interleaved round by round: a drift of the box falls on all three
+            for k, fn in arms.items():
+                ms[k].append(timed(fn, a.steps))
+                kinds[k] = int(lib.lpi_gemm_last_kernel())
         fl = 2.0 * M * N * K
-        out["shapes"][name] = {"N": N, "K": K, "bf16_ms": round(t16, 4), "bf16_tflops": round(fl / t16 / 1e9, 1), "bf16_kernel": k16,
-                               "mx8_ms": round(t8, 4), "mx8_tflops": round(fl / t8 / 1e9, 1), "mx8_output": "mx8" if mx_out else str(cdt).split(".")[-1],
-                               "speedup": round(t16 / t8, 3)}
+        rec = {"N": N, "K": K, "mx8_output": "mx8" if mx_out else str(cdt).split(".")[-1]}
+        for k in arms:
+            t = float(np.median(ms[k]))
+            rec[k] = {"ms": round(t, 4), "ms_per_round": [round(v, 4) for v in ms[k]], "tflops": round(fl / t / 1e9, 1), "kernel": kinds[k]}
+        rec["mx8_256_over_bf16"] = round(rec["bf16"]["ms"] / rec["mx8_256"]["ms"], 3)
+        rec["mx8_256_over_mx8_128"] = round(rec["mx8_128"]["ms"] / rec["mx8_256"]["ms"], 3)
+        rec["mx8_128_over_bf16"] = round(rec["bf16"]["ms"] / rec["mx8_128"]["ms"], 3)
+        out["shapes"][name] = rec
     ctx = torch.randn(M, d, generator=g, device=DEV).bfloat16()
     q, s = E.mx8_quantize(ctx)
     t = timed(lambda: E.mx8_quantize(ctx, q, s))
@@ -133,8 +150,9 @@ def step_error(a):
     cfg, img, ids, fac, PackedIds = _inputs(a.batch)
     sd = synth.clip_state_dict(cfg)
     feats = {}
-    for name, dtype, on in (("f32", "f32", False), ("bf16", "bf16", False), ("mx8", "bf16", True)):
-        enc = DualEncoder(cfg, sd, dtype=dtype, device=DEV, options=EngineOptions(mx8_forward=on))
+    for name, dtype, opts in (("f32", "f32", {}), ("bf16", "bf16", {}), ("mx8", "bf16", {"mx8_forward": True}),
+                              ("mx8_128", "bf16", {"mx8_forward": True, "mx8_tile256": False})):
+        enc = DualEncoder(cfg, sd, dtype=dtype, device=DEV, options=EngineOptions(**opts))
         with torch.no_grad():
             _, fi, ft, _, _ = forward_loss(enc, img, PackedIds(ids, 17).to(DEV), fac, 3)
         torch.cuda.synchronize()
@@ -148,6 +166,7 @@ def step_error(a):
         lg = [feats[n][0] @ feats[n][1].T for n in (name, "f32")]
         rec[name] = {"max_abs_feature_error": float(f"{err:.4g}"), "min_cosine": round(cos, 6), "max_abs_cosine_matrix_error": float(f"{np.abs(lg[0] - lg[1]).max():.4g}"),
                      "top1_i2t_agreement": round(float((lg[0].argmax(1) == lg[1].argmax(1)).mean()), 4)}
+    rec["mx8_tile256_same_bits_as_128x128"] = bool(all(np.array_equal(g, r) for g, r in zip(feats["mx8"], feats["mx8_128"])))
     return rec
 
 
@@ -160,7 +179,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--step", choices=sorted(STEPS), help="(internal) run one step in this process and print its JSON record")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "mx8_forward_ab.json"))
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "mx8_tile256_ab.json"))
     a = ap.parse_args()
     if a.step:
         print("MX8_AB " + json.dumps(STEPS[a.step][0](a)))
