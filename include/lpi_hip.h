@@ -18,7 +18,14 @@
  *   - token rows are batch-major: row(b, l) = b * L + l (the reference permutes to [L, B, d] for
  *     nn.MultiheadAttention, models/clip/model.py:253; the arithmetic is layout independent);
  *   - matrices handed to lpi_gemm_nt are padded by the caller: M % 128 == 0, N % 128 == 0,
- *     K % (128 / sizeof(element)) == 0, all leading dimensions 16-byte aligned.
+ *     K % (128 / sizeof(element)) == 0, and EVERY leading dimension (lda, ldb, ldc, ldr, ldaux) a multiple of 16 bytes in its operand's
+ *     own element type, every operand pointer (A, B, C, bias, residual, aux) 16-byte aligned — LPI_EINVAL before any launch otherwise
+ *     (since 613; up to 612 ldc, an fp16 ldr, ldaux and the aux pointer were only held to 8 bytes, which the 16-byte stores and LDS-DMA
+ *     loads of the persistent kernel's epilogues and the f32x4 accesses of an f32 C / aux do not honour: DESIGN.md section 4).
+ *     lpi_gemm_nt_rows has one kernel, whose epilogue moves four elements per lane: lda, ldb 16 bytes; ldc, ldr, ldaux multiples of FOUR
+ *     ELEMENTS (8 bytes for a 2-byte type, 16 for f32), aux aligned likewise.  The LN operand block's ldr and LPI_EPI_RES_ROWSTATS's ldaux
+ *     count f32 entries: multiples of 4.  A leading dimension changes no arithmetic: a strided call gives the bits of the contiguous one, and
+ *     nothing outside the [rows, cols] footprint of an operand is read into a result or written (tests/test_gemm_strides_gpu.py).
  *   - DEAD REGIONS.  A call is often handed more memory than it may use; what it does not use may hold anything, NaN included, and no
  *     live output depends on it (tests/test_dead_memory_gpu.py fills each of these with NaN and asks for the same bits):
  *       token rows behind the batch: rows >= B*L (ragged: >= row_start[B]) of qkv, ctx, dctx, x, mean, rstd — arenas are padded to 256 rows;

@@ -264,11 +264,16 @@ static int gemm_nt_check(int dtype, int c_dtype, int M, int N, int K, const void
     const int bk = ROW_BYTES / esz;
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return LPI_EINVAL;
     if (M % BM || N % BN || K % bk) return LPI_EINVAL;
-    if ((lda * esz) % 16 || (ldb * esz) % 16 || (ldc * csz) % 8 || lda < K || ldb < K || ldc < N) return LPI_EINVAL;
+    // Every row of every operand starts on a 16-byte boundary (include/lpi_hip.h).  Which kernel runs is the dispatcher's choice (tuning keys, CU count), and
+    // the widest access any of them makes decides: most epilogues move four elements per lane (8 bytes of a 2-byte C / residual / aux), but the persistent
+    // kernel stores whole 16-byte pieces of a 2-byte C row (half-width staging) and brings the 2-byte residual / gelu' tiles to LDS 16 bytes per lane, and an
+    // f32 C / residual / aux moves as f32x4 everywhere ("Leading dimensions of the GEMM family").
+    const int rsz = c_dtype == LPI_F16 ? 2 : 4;      // the residual tile has C's type on the fp16 stream, f32 otherwise
+    if ((lda * esz) % 16 || (ldb * esz) % 16 || (ldc * csz) % 16 || lda < K || ldb < K || ldc < N) return LPI_EINVAL;
     if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return LPI_EINVAL;
-    if (residual && !ln && (ldr < N || (ldr & 3) || ((uintptr_t)residual & 15))) return LPI_EINVAL;
+    if (residual && !ln && (ldr < N || (ldr * rsz) % 16 || ((uintptr_t)residual & 15))) return LPI_EINVAL;
     if (bias && ((uintptr_t)bias & 15)) return LPI_EINVAL;
-    if (aux && (ldaux < N || ((uintptr_t)aux & 7) || (ldaux * esz) % 8)) return LPI_EINVAL;
+    if (aux && (ldaux < N || ((uintptr_t)aux & 15) || (ldaux * esz) % 16)) return LPI_EINVAL;
     if (epilogue == LPI_EPI_DQUICKGELU && !aux) return LPI_EINVAL;
     return 0;
 }

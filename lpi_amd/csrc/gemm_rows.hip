@@ -230,16 +230,17 @@ extern "C" int lpi_gemm_nt_rows(int dtype, int c_dtype, int epilogue, float alph
 {
     if (!d || count < 1 || count > 2) return LPI_EINVAL;
     const int esz = dtype == LPI_F32 ? 4 : 2;
-    const int csz = c_dtype == LPI_F32 ? 4 : 2;
     for (int i = 0; i < count; ++i) {
         const lpi_gemm_desc& q = d[i];
         if (!q.A || !q.B || !q.C) return LPI_EINVAL;
         if (!lpi_gemm_nt_rows_supported(dtype, q.M, q.N, q.K)) return LPI_EINVAL;
-        if ((q.lda * esz) % 16 || (q.ldb * esz) % 16 || (q.ldc * csz) % 8 || q.lda < q.K || q.ldb < q.K || q.ldc < q.N) return LPI_EINVAL;
+        // this entry point has ONE kernel, whose epilogue (gemm_epilogue.h) moves four consecutive elements of C / residual / aux per lane: their rows are
+        // aligned to four elements — 8 bytes for a 2-byte type, 16 for f32 (an f32x4 access)
+        if ((q.lda * esz) % 16 || (q.ldb * esz) % 16 || (q.ldc & 3) || q.lda < q.K || q.ldb < q.K || q.ldc < q.N) return LPI_EINVAL;
         if (((uintptr_t)q.A | (uintptr_t)q.B | (uintptr_t)q.C) & 15) return LPI_EINVAL;
         if (q.residual && (q.ldr < q.N || (q.ldr & 3) || ((uintptr_t)q.residual & 15))) return LPI_EINVAL;
         if (q.bias && ((uintptr_t)q.bias & 15)) return LPI_EINVAL;
-        if (q.aux && (q.ldaux < q.N || ((uintptr_t)q.aux & 7) || (q.ldaux * esz) % 8)) return LPI_EINVAL;
+        if (q.aux && (q.ldaux < q.N || ((uintptr_t)q.aux & (4 * esz - 1)) || (q.ldaux & 3))) return LPI_EINVAL;
     }
     if (c_dtype == LPI_F16 && dtype != LPI_F16) return LPI_ENOSYS;     // bf16 mode: the fp16 residual stream never has this few rows
     hipStream_t s = (hipStream_t)stream;

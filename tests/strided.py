@@ -1,0 +1,102 @@
+"""Strided operands for kernel tests (a plain helper module: no fixtures, no pytest settings; works on the CPU and on the GPU).
+
+A kernel that takes a leading dimension per operand is handed sub-matrix VIEWS: an offset base pointer and a row stride larger than the
+width.  A test that passes contiguous tensors (ld == width, base == start of the allocation) cannot tell `ldc` from `ldr`, `lda` from `K`,
+or a 16-byte store that runs over a row's end from one that does not.  Here every operand of a case lives in a flat ARENA of its own:
+
+    operand(rows, cols, ld, dtype, col0, arena_elems, fill)   a [rows, cols] view with stride (ld, 1) whose first element is arena[col0]
+
+    * every arena element OUTSIDE the view's footprint {col0 + r * ld + c} holds PAD, a NaN (set by bit pattern): read into a result it
+      shows as NaN, written it shows in `check_pads`, which compares the arena's bits with those of before the call;
+    * an INPUT (fill = a [rows, cols] tensor) holds its live values in the footprint;
+    * an OUTPUT (fill = None) holds UNWRITTEN there, a second NaN with other bits: `check_written` finds what the kernel left out.
+
+THE SAFETY RULE (arena sizing).  Within one test case EVERY arena has the same size in bytes, `arena_bytes(...)`, worked out from the
+LARGEST row count, the LARGEST leading dimension and the LARGEST element size of ANY operand of that case, plus the base offset col0:
+
+    bytes = (max_col0 + max_rows * max_ld) * max_esz + SLACK
+
+so whichever leading dimension, row count or element size a wrong kernel applies to whichever pointer of the case — ldr for C, K for lda,
+4-byte elements on a 2-byte operand, a 16-byte access at a row's last 8 bytes — the address stays inside that operand's own allocation.
+A wrong kernel fails an assertion; it never faults.  (Operands that are not matrices — a statistics block, a slot buffer — use `region`
+with an explicit index list and the same arena size.)
+"""
+import torch
+
+from poison import bits
+
+PAD = {torch.float32: 0x7FC00BAD, torch.bfloat16: 0x7FC5, torch.float16: 0x7E05}            # NaNs, told apart by their payloads
+UNWRITTEN = {torch.float32: 0x7FC0F00D, torch.bfloat16: 0x7FCA, torch.float16: 0x7E0A}
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16}
+SLACK = 64      # bytes behind the last row: a 16-byte access that starts inside the last row ends inside the arena
+
+
+def arena_bytes(max_rows, max_ld, max_esz, col0=0):
+    """The one arena size of a test case (see THE SAFETY RULE); col0 = the largest base offset of the case, in elements."""
+    return (col0 + max_rows * max_ld) * max_esz + SLACK
+
+
+class Record:
+    """What `operand` / `region` return: .t the view (hand it to the kernel), .arena the flat allocation, .inside the footprint as a bool
+    mask over the arena, .before the arena's bits after set-up, .output whether the footprint holds UNWRITTEN."""
+
+    def __init__(self, t, arena, inside, output):
+        self.t, self.arena, self.inside, self.output = t, arena, inside, output
+        self.before = bits(arena).clone()
+
+
+def _arena(arena_elems, dtype, device):
+    assert dtype in _INT, dtype
+    return torch.full((arena_elems,), PAD[dtype], dtype=_INT[dtype], device=device).view(dtype)      # every pattern here is below 0x8000 / 2^31
+
+
+def region(index, dtype, arena_elems, fill=None, device="cpu"):
+    """An arena of `arena_elems` elements whose footprint is the explicit element list `index` (int64, distinct): `fill` (as many values, in
+    that order) or UNWRITTEN.  Returns a Record whose .t is the whole arena (the caller hands the kernel .t[first:])."""
+    index = torch.as_tensor(index, dtype=torch.int64, device=device)
+    assert index.numel() > 0 and int(index.min()) >= 0 and int(index.max()) < arena_elems, "the footprint leaves the arena: size every arena with arena_bytes()"
+    arena = _arena(arena_elems, dtype, device)
+    inside = torch.zeros(arena_elems, dtype=torch.bool, device=device)
+    inside[index] = True
+    assert int(inside.sum()) == index.numel(), "footprint elements overlap"
+    if fill is None:
+        arena.view(_INT[dtype])[index] = UNWRITTEN[dtype]
+    else:
+        arena[index] = fill.to(device=device, dtype=dtype).reshape(-1)
+    return Record(arena, arena, inside, fill is None)
+
+
+def operand(rows, cols, ld, dtype, col0, arena_elems, fill=None, device="cpu"):
+    """A [rows, cols] view with stride(0) == ld, stride(1) == 1, first element arena[col0] (so data_ptr() is not the start of the allocation
+    when col0 > 0).  fill: the [rows, cols] live values of an input; None for an output.  Returns a Record (.t is the view)."""
+    assert ld >= cols and col0 >= 0
+    assert col0 + (rows - 1) * ld + cols <= arena_elems, "the footprint leaves the arena: size every arena with arena_bytes()"
+    arena = _arena(arena_elems, dtype, device)
+    view = arena.as_strided((rows, cols), (ld, 1), col0)
+    inside = torch.zeros(arena_elems, dtype=torch.bool, device=device)
+    inside.as_strided((rows, cols), (ld, 1), col0).fill_(True)
+    if fill is None:
+        view.view(_INT[dtype]).fill_(UNWRITTEN[dtype])
+    else:
+        assert tuple(fill.shape) == (rows, cols), (tuple(fill.shape), rows, cols)
+        view.copy_(fill.to(dtype))
+    assert view.stride() == (ld, 1) and view.data_ptr() == arena.data_ptr() + col0 * arena.element_size()
+    return Record(view, arena, inside, fill is None)
+
+
+def check_pads(name, rec):
+    """Every arena element outside the footprint still has the bits it had before the call (integer compare: NaN payloads count)."""
+    now = bits(rec.arena)
+    changed = (now != rec.before) & ~rec.inside
+    n = int(changed.sum())
+    assert n == 0, f"{name}: {n} elements outside the operand's footprint were written (first at arena element {int(changed.nonzero()[0])})"
+    if not rec.output:
+        assert torch.equal(now, rec.before), f"{name}: an input operand was written"
+
+
+def check_written(name, rec):
+    """No footprint element of an output still holds UNWRITTEN."""
+    assert rec.output, name
+    left = (bits(rec.arena) == UNWRITTEN[rec.arena.dtype]) & rec.inside
+    n = int(left.sum())
+    assert n == 0, f"{name}: {n} of {int(rec.inside.sum())} output elements were never written (first at arena element {int(left.nonzero()[0]) if n else -1})"
