@@ -579,6 +579,29 @@ int lpi_retrieval_rank(int n_rows, int n_cols, const float* scores, int ld, cons
                        int32_t* rank, void* stream);
 int lpi_topk(int n_rows, int n_cols, int k, const float* scores, int ld, int32_t* idx, float* val, void* stream);
 
+/* ---- streamed search (search.hip, since 614): the two calls above without the score matrix.  s[i,j] = Q[i,:] . G[j,:] is computed tile by tile on the
+ * matrix cores (exact f32 products, f32 accumulation, one fixed order over E per score) and consumed from the accumulators: memory is O(nq k), not
+ * O(nq ng).  A score's bits depend on its two rows only: not on where the rows sit, on ng, or on how a gallery is cut into calls.
+ * Q f32 [nq, E] (ldq), G f32 [ng, E] (ldg): nq, ng any positive number (edges are masked, the caller pads nothing), E a multiple of 16 and <= 1024,
+ * ldq / ldg >= E and multiples of 4 (16-byte rows, as the GEMM family), Q and G 16-byte aligned, finite values.  Nothing outside the n x E elements
+ * of an operand is read, nothing outside idx / val / rank / ws is written.  ws: lpi_search_workspace(nq, ng, k) bytes (k = 0: the rank form), a host
+ * function that never shrinks when an argument grows; its contents need not survive between calls.  Anything outside the envelope, or a workspace
+ * that is too small, is LPI_EINVAL before any launch.
+ * lpi_search_topk: 1 <= k <= 16 (lpi_topk's range); idx / val [nq, k] in lpi_topk's order (value descending, then index descending); col_base >= 0 is
+ *   added to the indices.  accumulate != 0: idx / val already hold such a list (entries with idx < 0 are empty) and it takes part: a gallery that is
+ *   sharded or larger than the device is searched chunk by chunk, and the result is that of one call, bit for bit.  k <= ng unless accumulate (what the
+ *   held list brings is the caller's statement; a list shorter than k ends with idx = -1, val = -inf).  val must not be NULL.  Two launches.
+ * lpi_search_rank: rank [nq] as lpi_retrieval_rank over the gt list [nq, gt_per_row] (entries < 0 or >= ng are ignored; a row with none gets
+ *   0x7fffffff as there): #{j != g* : s[i,j] > s[i,g*] or (s[i,j] == s[i,g*] and j > g*)} for g* = the row's ground-truth column that is largest in
+ *   the order (score, then index) - equal to the minimum over the list because the count is monotone in that order.  The threshold score comes from a
+ *   first launch of the same tile code over the gathered ground-truth rows, so duplicate gallery rows tie exactly and fall by index.  Two launches.
+ *   After the call ws holds the thresholds: s[i,g*] f32 [nq] (+inf: none), then g* int32 [nq] (-1: none). */
+long lpi_search_workspace(int nq, int ng, int k_or_0);
+int lpi_search_topk(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, int k, int col_base, int accumulate,
+                    int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
+int lpi_search_rank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* gt, int gt_per_row,
+                    int32_t* rank, void* ws, long ws_bytes, void* stream);
+
 /* ---- a6 (host side): CLIP byte-level BPE      replaces: models/clip/simple_tokenizer.py:62-132, clip.py:185-221 ------
  * HOST functions (no GPU work, no stream).  create: `merges_utf8` is the decompressed text of bpe_simple_vocab_16e6.txt(.gz) —
  * third-party data that is not shipped with this library; returns NULL on a malformed table.  encode: pattern split + byte mapping

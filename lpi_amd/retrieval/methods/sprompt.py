@@ -93,11 +93,21 @@ def _check_jpeg_layouts(args):
         raise ValueError(f"jpeg_layouts widens the envelope of pixel_format='jpeg': it cannot go with pixel_format={args.get('pixel_format', 'f32')!r}")
 
 
+def _eval_scores(args):
+    """eval_scores = 'matrix' (default: score_matrix + itm_eval, the reference's shape) | 'streamed' (lpi_amd.search.gt_rank in both directions: no
+    N_img x N_txt matrix is built, and _evaluate_retrieval returns None in the two score slots)."""
+    mode = args.get('eval_scores', 'matrix')
+    if mode not in ('matrix', 'streamed'):
+        raise ValueError(f"unknown eval_scores {mode!r} (matrix | streamed)")
+    return mode
+
+
 class SPrompts(BaseLearner):
     def __init__(self, args):
         super().__init__(args)
         _check_jpeg_progressive(args)           # a conflicting key fails here, beside the preprocessing keys, not at the first task
         _check_jpeg_layouts(args)
+        _eval_scores(args)
         if args["net_type"] == "slip":
             self._network = SliNet(args)
         else:
@@ -434,6 +444,12 @@ class SPrompts(BaseLearner):
             sel = self.get_textual_task_id(text)
             text_feats.append(self._network.textual_interface(text, sel))
         image_feats, text_feats = torch.cat(image_feats), torch.cat(text_feats)
+        if _eval_scores(self.args) == 'streamed':
+            from lpi_amd.search import gt_rank
+            gt_i, gt_t = self._gt_lists(ds.txt2img, ds.img2txt, image_feats.shape[0], num_text)
+            ranks_i = gt_rank(image_feats, text_feats, gt_i).cpu().numpy()
+            ranks_t = gt_rank(text_feats, image_feats, gt_t).cpu().numpy()
+            return None, None, self._recall_per_task(ranks_i, ranks_t, category_i, texts_cat)
         from lpi_amd.engine import score_matrix
         score_i2t, score_t2i = score_matrix(image_feats, text_feats)      # sprompt.py:509: (I @ T^T) and its transpose, f32 MFMA GEMM
         final_res = self.itm_eval(score_i2t, score_t2i, ds.txt2img, ds.img2txt, category_i, texts_cat)
@@ -446,17 +462,27 @@ class SPrompts(BaseLearner):
         s_i2t = torch.as_tensor(scores_i2t, dtype=torch.float32, device=dev).contiguous()
         s_t2i = torch.as_tensor(scores_t2i, dtype=torch.float32, device=dev).contiguous()
         n_img, n_txt = s_i2t.shape
-        gmax = max(len(v) for v in img2txt.values())
-        gt_i = torch.full((n_img, gmax), -1, dtype=torch.int32)
-        for i in range(n_img):
-            gt_i[i, :len(img2txt[i])] = torch.tensor(img2txt[i], dtype=torch.int32)
-        gt_t = torch.tensor([txt2img[t] for t in range(n_txt)], dtype=torch.int32).view(-1, 1)
+        gt_i, gt_t = self._gt_lists(txt2img, img2txt, n_img, n_txt)
+        gmax = gt_i.shape[1]
         r_i = torch.zeros(n_img, dtype=torch.int32, device=dev)
         r_t = torch.zeros(n_txt, dtype=torch.int32, device=dev)
         s = torch.cuda.current_stream().cuda_stream
         _lib.call("lpi_retrieval_rank", n_img, n_txt, s_i2t, n_txt, gt_i.to(dev), gmax, r_i, s)
         _lib.call("lpi_retrieval_rank", n_txt, n_img, s_t2i, n_img, gt_t.to(dev), 1, r_t, s)
-        ranks_i, ranks_t = r_i.cpu().numpy(), r_t.cpu().numpy()
+        return self._recall_per_task(r_i.cpu().numpy(), r_t.cpu().numpy(), category_i, category_t)
+
+    @staticmethod
+    def _gt_lists(txt2img, img2txt, n_img, n_txt):
+        """The ground-truth lists of both directions as int32 tensors: [n_img, longest list] padded with -1, and [n_txt, 1]."""
+        gmax = max(len(v) for v in img2txt.values())
+        gt_i = torch.full((n_img, gmax), -1, dtype=torch.int32)
+        for i in range(n_img):
+            gt_i[i, :len(img2txt[i])] = torch.tensor(img2txt[i], dtype=torch.int32)
+        gt_t = torch.tensor([txt2img[t] for t in range(n_txt)], dtype=torch.int32).view(-1, 1)
+        return gt_i, gt_t
+
+    def _recall_per_task(self, ranks_i, ranks_t, category_i, category_t):
+        """Per-row ranks of the best ground truth -> R@1/5/10 per task in both directions (sprompt.py:600-646): shared by both eval_scores modes."""
         category_i = np.asarray(category_i)
         category_t = np.asarray(category_t)
         task_num = self.cur_id + 1

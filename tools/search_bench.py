@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""The streamed search (lpi_amd.search: lpi_search_rank / lpi_search_topk) against the matrix path (engine.score_matrix + lpi_retrieval_rank / lpi_topk),
+ONE process on one GPU, arms interleaved: time (HIP events, median of `--rounds` rounds' medians of `--steps` calls) and the growth of
+torch.cuda.max_memory_allocated over one call of each arm, at
+
+  i2t    5 000 queries x 25 000 gallery rows x 512 (COCO's test split, images -> captions, 5 ground truths per row)
+  t2i    25 000 x 5 000 x 512 (captions -> images, 1 ground truth per row)
+  eval   both directions of the evaluation as SPrompts._evaluate_retrieval runs them (matrix: ONE score_matrix + two rank searches)
+  train  123 287 x 616 767 x 512 (COCO's training split): three f32 matrices of it are 912 GB, so the matrix arm does not exist; one call of each
+         streamed form, timed once.  --no-large skips it.
+
+The matrix arm of i2t / t2i is what the path does for one direction: score_matrix (the padded GEMM output, its copy and its transpose) + one
+lpi_retrieval_rank.  Rows unit-normalised Gaussian; ranks of the two arms are compared (they may differ where two scores lie within rounding: the GEMM
+kernels sum K in another order) and the count is recorded.
+
+    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large]
+
+writes profiles/search_stream.json.  An error ends the process: nothing further is started.  Run it under a time limit."""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+DEV = "cuda:0"
+
+
+def _unit(n, E, gen):
+    import torch
+    x = torch.randn(n, E, device=DEV, generator=gen)
+    return x / x.norm(dim=1, keepdim=True)
+
+
+def _median_rounds(arms, rounds, steps):
+    import numpy as np
+    import torch
+    for fn in arms.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+            ev[0].record()
+            for i in range(steps):
+                fn()
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            ms[k].append(float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(steps)])))
+    return {k: {"ms": round(float(np.median(v)), 4), "rounds_ms": [round(x, 4) for x in v]} for k, v in ms.items()}
+
+
+def _peak(fn):
+    """Growth of max_memory_allocated over one call, from a state without cached workspaces or results."""
+    import torch
+    from lpi_amd import search
+    search._WS.clear()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del out
+    return int(peak)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--no-large", action="store_true")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "search_stream.json"))
+    a = ap.parse_args()
+    import torch
+    from lpi_amd import _lib, search
+    from lpi_amd.engine import score_matrix
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    E = 512
+    img, txt = _unit(5000, E, gen), _unit(25000, E, gen)
+    gt_i = (torch.arange(5000, device=DEV, dtype=torch.int32)[:, None] * 5 + torch.arange(5, device=DEV, dtype=torch.int32)[None, :]).contiguous()
+    gt_t = (torch.arange(25000, device=DEV, dtype=torch.int32) // 5).view(-1, 1).contiguous()
+    txt[gt_i[:, 0].long()] = torch.nn.functional.normalize(img + 0.05 * torch.randn(5000, E, device=DEV, generator=gen), dim=1)      # some signal
+    st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+
+    def matrix_rank(s, gt):
+        r = torch.empty(s.shape[0], dtype=torch.int32, device=DEV)
+        _lib.call("lpi_retrieval_rank", s.shape[0], s.shape[1], s, s.shape[1], gt, gt.shape[1], r, st())
+        return r
+
+    def matrix_topk(s, k):
+        idx = torch.empty(s.shape[0], k, dtype=torch.int32, device=DEV)
+        val = torch.empty(s.shape[0], k, dtype=torch.float32, device=DEV)
+        _lib.call("lpi_topk", s.shape[0], s.shape[1], k, s, s.shape[1], idx, val, st())
+        return idx, val
+
+    res = {"device": torch.cuda.get_device_name(0), "abi": int(_lib.load().lpi_version()), "rounds": a.rounds, "steps": a.steps, "E": E, "shapes": {}}
+    for name, q, g, gt in (("i2t_5000x25000", img, txt, gt_i), ("t2i_25000x5000", txt, img, gt_t)):
+        arms = {
+            "matrix_rank": lambda q=q, g=g, gt=gt: matrix_rank(score_matrix(q, g)[0], gt),
+            "streamed_rank": lambda q=q, g=g, gt=gt: search.gt_rank(q, g, gt),
+            "matrix_top10": lambda q=q, g=g: matrix_topk(score_matrix(q, g)[0], 10),
+            "streamed_top10": lambda q=q, g=g: search.topk(q, g, 10),
+        }
+        out = _median_rounds(arms, a.rounds, a.steps)
+        for k, fn in arms.items():
+            out[k]["peak_bytes"] = _peak(fn)
+        rm, rs = arms["matrix_rank"](), arms["streamed_rank"]()
+        im, _ = arms["matrix_top10"]()
+        is_, _ = arms["streamed_top10"]()
+        out["rank_rows_differing"] = int((rm != rs).sum())
+        out["top10_rows_differing"] = int((im != is_).any(1).sum())
+        out["rows"] = int(q.shape[0])
+        out["workspace_bytes"] = {"rank": int(_lib.load().lpi_search_workspace(q.shape[0], g.shape[0], 0)),
+                                  "top10": int(_lib.load().lpi_search_workspace(q.shape[0], g.shape[0], 10))}
+        res["shapes"][name] = out
+        print(name, json.dumps(out), flush=True)
+
+    def eval_matrix():
+        s_i2t, s_t2i = score_matrix(img, txt)
+        return matrix_rank(s_i2t, gt_i), matrix_rank(s_t2i, gt_t)
+
+    def eval_streamed():
+        return search.gt_rank(img, txt, gt_i), search.gt_rank(txt, img, gt_t)
+
+    arms = {"matrix": eval_matrix, "streamed": eval_streamed}
+    out = _median_rounds(arms, a.rounds, a.steps)
+    for k, fn in arms.items():
+        out[k]["peak_bytes"] = _peak(fn)
+    res["shapes"]["eval_both_directions_5000x25000"] = out
+    print("eval", json.dumps(out), flush=True)
+
+    if not a.no_large:
+        nq, ng = 123287, 616767
+        del img, txt
+        torch.cuda.empty_cache()
+        q, g = _unit(nq, E, gen), _unit(ng, E, gen)
+        gt = (torch.arange(nq, device=DEV, dtype=torch.int32)[:, None] * 5 + torch.arange(5, device=DEV, dtype=torch.int32)[None, :]).contiguous()
+        out = {"matrix": {"exists": False, "bytes_needed_for_three_f32_matrices": 3 * nq * ng * 4}}
+        for k, fn in (("streamed_rank", lambda: search.gt_rank(q, g, gt)), ("streamed_top10", lambda: search.topk(q, g, 10))):
+            search._WS.clear()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[k] = {"ms": round(e0.elapsed_time(e1), 2), "calls_timed": 1, "peak_bytes": int(torch.cuda.max_memory_allocated() - base),
+                      "tflops": round(2.0 * nq * ng * E / (e0.elapsed_time(e1) * 1e-3) / 1e12, 2)}
+            del r
+            print(k, json.dumps(out[k]), flush=True)
+        out["operand_bytes"] = (nq + ng) * E * 4
+        res["shapes"]["train_123287x616767"] = out
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
