@@ -601,6 +601,18 @@ int lpi_search_topk(int nq, int ng, int E, const float* Q, int ldq, const float*
                     int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
 int lpi_search_rank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* gt, int gt_per_row,
                     int32_t* rank, void* ws, long ws_bytes, void* stream);
+/* The same two calls with the operand type as first argument (search16.hip, since 615).  dt = LPI_F32 forwards to the calls above: their envelope,
+ * their bits.  dt = LPI_BF16 | LPI_F16: Q and G are 2-byte elements of that one type, read in place (no f32 copy is made).  The 2-byte envelope: E a
+ * multiple of 32 and <= 1024, ldq / ldg >= E in elements and multiples of 8 (16-byte rows), Q and G 16-byte aligned, finite values; everything else
+ * (nq, ng, k, col_base, accumulate, gt, idx, val, rank, ws and lpi_search_workspace, which does not depend on the type) as above.  val and the
+ * thresholds left in ws are f32.  A score is the f32 accumulation, in one fixed order over E, of the exact products of the 2-byte values
+ * (v_mfma_f32_16x16x32_bf16 / _f16), so every property above holds: a score's bits depend on its two rows only, a chunked search equals one call bit
+ * for bit, duplicate rows tie exactly and fall by index, the rank threshold carries the sweep's bits.  Any other dt, LPI_F32X3 included, is
+ * LPI_EINVAL before any launch. */
+int lpi_search_topk_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, int k, int col_base, int accumulate,
+                      int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
+int lpi_search_rank_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, const int32_t* gt, int gt_per_row,
+                      int32_t* rank, void* ws, long ws_bytes, void* stream);
 
 /* ---- a6 (host side): CLIP byte-level BPE      replaces: models/clip/simple_tokenizer.py:62-132, clip.py:185-221 ------
  * HOST functions (no GPU work, no stream).  create: `merges_utf8` is the decompressed text of bpe_simple_vocab_16e6.txt(.gz) —

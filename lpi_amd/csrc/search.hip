@@ -6,289 +6,11 @@
 // replaces: `score_matrix` + lpi_topk / lpi_retrieval_rank where only neighbours or ranks are wanted (the evaluation's
 // (image_feats @ text_feats.t()) of methods/sprompt.py:509 followed by the np.argsort rank search of :558-599): O(N k) memory, not O(N M).
 //
-// Design:
-//  * the main loop is gemm.hip's f32 one: 128x128 tile, 4 waves as 2x2, K-contiguous operands staged 32 k-values at a time by
-//    `global_load_lds_dwordx4`, double buffered, swizzled on the source address; exact f32 products on v_mfma_f32_16x16x4_f32.  Every score is one
-//    accumulator chain over K in a fixed order, so its bits depend on its two rows only: not on the tile position, the gallery split or the chunking;
-//  * a workgroup owns 128 query rows and walks the gallery tiles of its split; the query block is re-staged from L2 with every gallery tile (at E = 1024
-//    it would be 512 KB of LDS).  The staging of the next tile's first K slab is issued before the epilogue of the current one;
-//  * edges: a staged row past the end of an operand is the operand's last row again, a staged 16-byte piece past E (E % 32 == 16, last slab) is a
-//    piece of the same slab below E and is never read from LDS: nothing outside the n x E elements is read; scores of such rows / columns are masked;
-//  * rank: a first launch of the same tile code over the ground-truth rows GATHERED by index (tile p, column c = ground truth p of query row c) leaves the
-//    threshold scores on the tiles' diagonals, with the bits the sweep computes for those columns; the sweep keeps one counter per owned row in registers
-//    and ends with one reduction and one integer atomicAdd per (row, workgroup);
-//  * top-k: every wave keeps a sorted list per row of its 64x64 quadrant's columns in LDS; scores are compared in registers with the row's current k-th
-//    and only survivors are inserted (the four lanes that share a row take turns).  Per-(split, wave column) lists go to the workspace, a merge
-//    kernel writes idx / val.
-#include "common.h"
-#include <math.h>
+// This file: the f32 instantiations of the tile code (search_tile.h, where the design is described), the merge kernel and the workspace function,
+// which do not depend on the operand type.  The 2-byte instantiations and the typed entry points are search16.hip's.
+#include "search_tile.h"
 
 namespace {
-
-constexpr int BM = 128, BN = 128, BK = 32;
-constexpr int ROW_BYTES = 128;
-constexpr int TILE_BYTES = BM * ROW_BYTES;
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;
-constexpr int NTHREADS = 256;
-constexpr int KMAX = 16;
-constexpr int WG_TARGET = 512;      // workgroups wanted per launch: two per CU of an MI355X
-constexpr int MODE_TOPK = 0, MODE_RANK = 1, MODE_THRESH = 2;
-
-struct SearchArgs {
-    int nq, ng, E;
-    const float* Q;
-    int ldq;
-    const float* G;
-    int ldg;
-    int k, tiles, splits;
-    const int32_t* gt;
-    int gpr;
-    float* thr;          // [nq] threshold score of the best ground-truth column (+inf: none)
-    int32_t* gstar;      // [nq] its index (-1: none)
-    int32_t* rank;
-    float* part_val;     // [2 * splits][nq][k]
-    int32_t* part_idx;
-};
-
-// (s, j) before (v, i) in the order value descending, then index descending
-__device__ __forceinline__ bool beats(float s, int j, float v, int i) { return s > v || (s == v && j > i); }
-
-// one lane inserts into a sorted list of k
-typedef __attribute__((address_space(3))) volatile float lds_f32;
-typedef __attribute__((address_space(3))) volatile int lds_i32;
-__device__ __forceinline__ void list_insert(lds_f32* lv, lds_i32* li, int k, float s, int j) {
-    if (!beats(s, j, lv[k - 1], li[k - 1])) return;
-    int p = k - 1;
-    while (p > 0) {
-        const float pv = lv[p - 1];
-        const int pi = li[p - 1];
-        if (!beats(s, j, pv, pi)) break;
-        lv[p] = pv;
-        li[p] = pi;
-        --p;
-    }
-    lv[p] = s;
-    li[p] = j;
-}
-
-template <int MODE>
-__global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int m0 = blockIdx.x * BM;
-    int t_begin = 0, t_end = a.gpr;      // MODE_THRESH: tile p = the p-th ground-truth row of each query row
-    if constexpr (MODE != MODE_THRESH) {
-        t_begin = (int)((long)blockIdx.y * a.tiles / a.splits);
-        t_end = (int)((long)(blockIdx.y + 1) * a.tiles / a.splits);
-    }
-    const int nk = (a.E + BK - 1) / BK;
-    const int ks_last = (a.E & 31) ? 1 : 2;      // 16-wide k steps of the last slab
-
-    // ---- staging (gemm.hip): thread t, instruction i writes LDS byte i*4096 + t*16 of a tile; row = i*32 + t/8, logical chunk = (t%8) ^ ((row>>1)&7)
-    const int srow = tid >> 3;
-    const int schunk = (tid & 7) ^ (((wave & 1) << 2) | (lane >> 4));
-    const float* qp[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qp[i] = a.Q + (size_t)min(m0 + srow + 32 * i, a.nq - 1) * a.ldq;
-
-    auto stage = [&](int tile, int kt, int buf) {
-        char* base = smem + buf * STAGE_BYTES + wave * 1024;
-        int koff = kt * BK + schunk * 4;
-        if (koff >= a.E) koff -= 16;      // the dead half of the last slab: staged from below E, never read
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qp[i] + koff),
-                                             (__attribute__((address_space(3))) void*)(base + i * 4096), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int gr;
-            if constexpr (MODE == MODE_THRESH) {
-                const int q = m0 + srow + 32 * i;
-                gr = q < a.nq ? a.gt[(size_t)q * a.gpr + tile] : -1;
-                if ((unsigned)gr >= (unsigned)a.ng) gr = 0;
-            } else {
-                gr = min(tile * BN + srow + 32 * i, a.ng - 1);
-            }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.G + (size_t)gr * a.ldg + koff),
-                                             (__attribute__((address_space(3))) void*)(base + TILE_BYTES + i * 4096), 16, 0, 0);
-        }
-    };
-
-    // ---- fragment read offsets: lane reads row (l&15) of a 16-row sub tile, logical chunk 4*ks + (l>>4)
-    const int fsw = r16 >> 1;
-    int foff[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) foff[ks] = r16 * ROW_BYTES + (((ks << 2) | g) ^ fsw) * 16;
-    const int a_frag_base = (wm * 64) * ROW_BYTES;               // query rows
-    const int b_frag_base = TILE_BYTES + (wn * 64) * ROW_BYTES;  // gallery rows
-
-    // ---- per-mode state.  A lane owns rows m0 + wm*64 + mi*16 + r16 (mi = 0..3) and, of each, columns wn*64 + ni*16 + 4g + 0..3 of the tile
-    lds_f32* Lv = nullptr;      // MODE_TOPK: this wave's lists, [64 rows][k]
-    lds_i32* Li = nullptr;
-    int cnt[4] = {0, 0, 0, 0};         // MODE_RANK
-    float tv[4];                       // MODE_RANK: thresholds; MODE_THRESH: best ground-truth score so far
-    int ti[4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) { tv[mi] = -INFINITY; ti[mi] = -1; }
-    if constexpr (MODE == MODE_TOPK) {
-        auto lists = (__attribute__((address_space(3))) char*)smem + 2 * STAGE_BYTES + wave * (64 * a.k * 8);
-        Lv = (lds_f32*)lists;
-        Li = (lds_i32*)(lists + 64 * a.k * 4);
-        for (int e = lane; e < 64 * a.k; e += 64) { Lv[e] = -INFINITY; Li[e] = -1; }
-    }
-    if constexpr (MODE == MODE_RANK) {
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            const int row = m0 + wm * 64 + mi * 16 + r16;
-            tv[mi] = row < a.nq ? a.thr[row] : INFINITY;
-            ti[mi] = row < a.nq ? a.gstar[row] : -1;
-        }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) asm volatile("" :: "v"(tv[mi]), "v"(ti[mi]));      // the loads are waited for here, not under the LDS-DMA
-    }
-
-    f32x4 acc[4][4];  // [n sub tile][m sub tile]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    int it = 0;
-    if (t_begin < t_end) stage(t_begin, 0, 0);
-    for (int tile = t_begin; tile < t_end; ++tile) {
-        for (int kt = 0; kt < nk; ++kt, ++it) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA of slab `it` has landed
-            __syncthreads();                                  // ... and everyone's; buffer (it+1)&1 is free again
-            if (kt + 1 < nk) stage(tile, kt + 1, (it + 1) & 1);
-            else if (tile + 1 < t_end) stage(tile + 1, 0, (it + 1) & 1);
-            const char* buf = smem + (it & 1) * STAGE_BYTES;
-            const int nks = kt == nk - 1 ? ks_last : 2;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                if (ks < nks) {
-                    Chunk fa[4], fb[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        fa[i].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
-                        fb[i].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
-                    }
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                        for (int mi = 0; mi < 4; ++mi) mma_chunk<float>(acc[ni][mi], fb[ni], fa[mi]);
-                }
-            }
-        }
-
-        // ---- the tile's scores are in acc: lane holds s[row = .. + mi*16 + r16][col = col0 + ni*16 + 0..3]
-        const int col0 = tile * BN + wn * 64 + 4 * g;
-        if constexpr (MODE == MODE_TOPK) {
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                lds_f32* lv = Lv + (mi * 16 + r16) * a.k;
-                lds_i32* li = Li + (mi * 16 + r16) * a.k;
-                const float kv = lv[a.k - 1];
-                const int ki = li[a.k - 1];
-                unsigned mask = 0;
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int col = col0 + ni * 16 + e;
-                        if (col < a.ng && beats(acc[ni][mi][e], col, kv, ki)) mask |= 1u << (ni * 4 + e);
-                    }
-                if (__ballot(mask != 0) == 0) continue;
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const bool want = mask & (1u << (ni * 4 + e));
-                        if (__ballot(want) == 0) continue;
-                        // the four lanes of a row (g = 0..3) take turns; lanes of one turn own different rows
-#pragma unroll 1
-                        for (int gp = 0; gp < 4; ++gp) {
-                            if (want && g == gp) list_insert(lv, li, a.k, acc[ni][mi][e], col0 + ni * 16 + e);
-                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                            __builtin_amdgcn_wave_barrier();
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        }
-                    }
-            }
-        } else if constexpr (MODE == MODE_RANK) {
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int col = col0 + ni * 16 + e;
-                        cnt[mi] += (col < a.ng && col != ti[mi] && beats(acc[ni][mi][e], col, tv[mi], ti[mi])) ? 1 : 0;
-                    }
-        } else {
-            // the diagonal of the tile: row == column  <=>  wm == wn, mi == ni, r16 == 4g + e
-            if (wm == wn && g == (r16 >> 2)) {
-                const int e = lane & 3;
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) {
-                    const f32x4 v = acc[mi][mi];
-                    const float s = e == 0 ? v[0] : e == 1 ? v[1] : e == 2 ? v[2] : v[3];
-                    const int row = m0 + wm * 64 + mi * 16 + r16;
-                    const int gi = row < a.nq ? a.gt[(size_t)row * a.gpr + tile] : -1;
-                    if ((unsigned)gi < (unsigned)a.ng && beats(s, gi, tv[mi], ti[mi])) { tv[mi] = s; ti[mi] = gi; }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    if constexpr (MODE == MODE_TOPK) {
-        // this wave's lists -> part [blockIdx.y * 2 + wn][row][k]
-        const size_t pbase = (size_t)(blockIdx.y * 2 + wn) * a.nq;
-        for (int e = lane; e < 64 * a.k; e += 64) {
-            const int row = m0 + wm * 64 + e / a.k;
-            if (row < a.nq) {
-                const size_t o = (pbase + row) * a.k + e % a.k;
-                a.part_val[o] = Lv[e];
-                a.part_idx[o] = Li[e];
-            }
-        }
-    } else if constexpr (MODE == MODE_RANK) {
-        int* wg = reinterpret_cast<int*>(smem);
-        __syncthreads();      // every wave is done with the staging buffers
-        if (tid < BM) wg[tid] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            int c = cnt[mi];
-            c += __shfl_xor(c, 16, 64);
-            c += __shfl_xor(c, 32, 64);
-            if (g == 0) atomicAdd(&wg[wm * 64 + mi * 16 + r16], c);      // the two waves of a row
-        }
-        __syncthreads();
-        if (tid < BM && m0 + tid < a.nq && wg[tid]) atomicAdd(a.rank + m0 + tid, wg[tid]);
-    } else {
-        if (wm == wn && g == (r16 >> 2)) {
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                const int row = m0 + wm * 64 + mi * 16 + r16;
-                if (row < a.nq) {
-                    a.thr[row] = ti[mi] >= 0 ? tv[mi] : INFINITY;
-                    a.gstar[row] = ti[mi];
-                    a.rank[row] = ti[mi] >= 0 ? 0 : 0x7fffffff;      // lpi_retrieval_rank's value for a row without ground truth
-                }
-            }
-        }
-    }
-}
 
 // one thread per query row: the partial lists (and, with accumulate, the list idx / val already hold) -> idx / val
 __global__ __launch_bounds__(64) void search_merge_kernel(int nq, int k, int nparts, const float* __restrict__ part_val,
@@ -324,23 +46,15 @@ __global__ __launch_bounds__(64) void search_merge_kernel(int nq, int k, int npa
     }
 }
 
-int search_splits(int nq, int ng)
-{
-    const int rb = (nq + BM - 1) / BM, tiles = (ng + BN - 1) / BN;
-    const int want = (WG_TARGET + rb - 1) / rb;
-    return tiles < want ? tiles : want;
-}
+}  // namespace
 
-// the envelope both calls share
-int search_check(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg)
+int lpi_search_merge(int nq, int k, int nparts, const float* part_val, const int32_t* part_idx, int col_base, int accumulate, int32_t* idx, float* val,
+                     hipStream_t s)
 {
-    if (nq <= 0 || ng <= 0 || E <= 0 || (E & 15) || E > 1024) return LPI_EINVAL;
-    if (ldq < E || ldg < E || (ldq & 3) || (ldg & 3)) return LPI_EINVAL;
-    if (!Q || !G || (((uintptr_t)Q | (uintptr_t)G) & 15)) return LPI_EINVAL;
+    LPI_LAUNCH(search_merge_kernel, dim3((nq + 63) / 64), dim3(64), 0, s, nq, k, nparts, part_val, part_idx, col_base, accumulate, idx, val);
+    LPI_CHECK_LAST();
     return 0;
 }
-
-}  // namespace
 
 // An upper bound of what the launches use that never shrinks when an argument grows (the split count itself falls as the row blocks rise).
 extern "C" long lpi_search_workspace(int nq, int ng, int k)
@@ -355,49 +69,11 @@ extern "C" long lpi_search_workspace(int nq, int ng, int k)
 extern "C" int lpi_search_topk(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, int k, int col_base, int accumulate,
                                int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
 {
-    if (int e = search_check(nq, ng, E, Q, ldq, G, ldg)) return e;
-    if (k < 1 || k > KMAX || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
-    if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, k)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    SearchArgs a{};
-    a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
-    a.tiles = (ng + BN - 1) / BN;
-    a.splits = search_splits(nq, ng);
-    const size_t nlist = (size_t)2 * a.splits * nq * k;
-    a.part_val = (float*)ws;
-    a.part_idx = (int32_t*)ws + nlist;
-    auto kern = search_kernel<MODE_TOPK>;
-    static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES + 4 * 64 * KMAX * 8)) return e;
-    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE_BYTES + 4 * 64 * k * 8, s, a);
-    LPI_CHECK_LAST();
-    LPI_LAUNCH(search_merge_kernel, dim3((nq + 63) / 64), dim3(64), 0, s, nq, k, 2 * a.splits, a.part_val, a.part_idx, col_base, accumulate, idx, val);
-    LPI_CHECK_LAST();
-    return 0;
+    return search_topk<float>(nq, ng, E, Q, ldq, G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
 }
 
 extern "C" int lpi_search_rank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* gt, int gt_per_row,
                                int32_t* rank, void* ws, long ws_bytes, void* stream)
 {
-    if (int e = search_check(nq, ng, E, Q, ldq, G, ldg)) return e;
-    if (!gt || gt_per_row <= 0 || !rank || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, 0)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    SearchArgs a{};
-    a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg;
-    a.tiles = (ng + BN - 1) / BN;
-    a.splits = search_splits(nq, ng);
-    a.gt = gt; a.gpr = gt_per_row;
-    a.thr = (float*)ws;
-    a.gstar = (int32_t*)ws + nq;
-    a.rank = rank;
-    auto kt = search_kernel<MODE_THRESH>;
-    auto kr = search_kernel<MODE_RANK>;
-    static LdsOnce once_t, once_r;
-    if (int e = lpi_ensure_lds(once_t, (const void*)kt, 2 * STAGE_BYTES)) return e;
-    if (int e = lpi_ensure_lds(once_r, (const void*)kr, 2 * STAGE_BYTES)) return e;
-    LPI_LAUNCH(kt, dim3((nq + BM - 1) / BM, 1), dim3(NTHREADS), 2 * STAGE_BYTES, s, a);
-    LPI_CHECK_LAST();
-    LPI_LAUNCH(kr, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE_BYTES, s, a);
-    LPI_CHECK_LAST();
-    return 0;
+    return search_rank<float>(nq, ng, E, Q, ldq, G, ldg, gt, gt_per_row, rank, ws, ws_bytes, stream);
 }

@@ -102,12 +102,26 @@ def _eval_scores(args):
     return mode
 
 
+def _eval_search_operands(args):
+    """eval_search_operands = 'f32' (default: the evaluation is unchanged bit for bit) | 'bf16' | 'f16': the operand type of the streamed search
+    (lpi_amd.search.gt_rank(..., operands=...)): the features are rounded to it once and searched at the 2-byte matrix rate.  It belongs to
+    eval_scores = 'streamed': with 'matrix' a non-f32 value is a ValueError."""
+    ops = args.get('eval_search_operands', 'f32')
+    if not isinstance(ops, str) or ops not in ('f32', 'bf16', 'f16'):
+        raise ValueError(f"unknown eval_search_operands {ops!r} (f32 | bf16 | f16)")
+    if ops != 'f32' and _eval_scores(args) != 'streamed':
+        raise ValueError(f"eval_search_operands={ops!r} is the operand type of eval_scores='streamed': it cannot go with "
+                         f"eval_scores={_eval_scores(args)!r}")
+    return ops
+
+
 class SPrompts(BaseLearner):
     def __init__(self, args):
         super().__init__(args)
         _check_jpeg_progressive(args)           # a conflicting key fails here, beside the preprocessing keys, not at the first task
         _check_jpeg_layouts(args)
         _eval_scores(args)
+        _eval_search_operands(args)
         if args["net_type"] == "slip":
             self._network = SliNet(args)
         else:
@@ -447,8 +461,10 @@ class SPrompts(BaseLearner):
         if _eval_scores(self.args) == 'streamed':
             from lpi_amd.search import gt_rank
             gt_i, gt_t = self._gt_lists(ds.txt2img, ds.img2txt, image_feats.shape[0], num_text)
-            ranks_i = gt_rank(image_feats, text_feats, gt_i).cpu().numpy()
-            ranks_t = gt_rank(text_feats, image_feats, gt_t).cpu().numpy()
+            ops = _eval_search_operands(self.args)
+            kw = {} if ops == 'f32' else {'operands': ops}      # f32: the call as it was
+            ranks_i = gt_rank(image_feats, text_feats, gt_i, **kw).cpu().numpy()
+            ranks_t = gt_rank(text_feats, image_feats, gt_t, **kw).cpu().numpy()
             return None, None, self._recall_per_task(ranks_i, ranks_t, category_i, texts_cat)
         from lpi_amd.engine import score_matrix
         score_i2t, score_t2i = score_matrix(image_feats, text_feats)      # sprompt.py:509: (I @ T^T) and its transpose, f32 MFMA GEMM

@@ -2,8 +2,9 @@
 
 ``topk`` and ``gt_rank`` compute the scores ``queries @ gallery.T`` tile by tile on the matrix cores in the f32 mode's arithmetic and consume them from the
 accumulators: memory is O(nq * k) instead of O(nq * ng).  A score's bits depend on its two rows only, so a gallery searched chunk by chunk
-(``col_base`` / ``into``) gives the result of one call bit for bit.  There is no fall-back: a shape outside the envelope (E a multiple of 16, <= 1024;
-1 <= k <= 16) raises."""
+(``col_base`` / ``into``) gives the result of one call bit for bit.  ``operands="bf16"`` / ``"f16"`` searches 2-byte operands (csrc/search16.hip): a
+tensor of that dtype is read in place, a score is the f32 sum in one fixed order of the exact products of the 2-byte values, and every property above
+holds.  There is no fall-back: a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, <= 1024; 1 <= k <= 16) raises."""
 from __future__ import annotations
 
 import torch
@@ -22,6 +23,28 @@ def _f32_rows(t):
     return t
 
 
+_OPERANDS = {"bf16": (_lib.BF16, torch.bfloat16), "f16": (_lib.F16, torch.float16)}
+
+
+def _operands(operands):
+    """None | 'f32' -> None (the f32 entry points); 'bf16' | 'f16' -> (LPI code, torch dtype)."""
+    if operands is None or operands == "f32":
+        return None
+    if not isinstance(operands, str) or operands not in _OPERANDS:
+        raise ValueError(f"unknown operands {operands!r} (f32 | bf16 | f16)")
+    return _OPERANDS[operands]
+
+
+def _rows16(t, dtype):
+    """`dtype` (2 bytes) with unit inner stride, a 16-byte row stride and a 16-byte aligned base: such a tensor is used in place, anything else is cast
+    or made contiguous once."""
+    if t.dim() != 2:
+        raise ValueError("expected a [rows, E] tensor")
+    if t.dtype != dtype or t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        t = t.to(dtype).contiguous()
+    return t
+
+
 def _workspace(dev, nq, ng, k):
     need = int(_lib.load().lpi_search_workspace(nq, ng, k))
     if need <= 0:
@@ -33,11 +56,12 @@ def _workspace(dev, nq, ng, k):
     return ws
 
 
-def topk(queries, gallery, k, *, col_base=0, into=None):
+def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
     """-> (idx int32 [nq, k], val f32 [nq, k]): per query row the k largest scores in the order (value descending, then index descending),
     lpi_topk's.  ``col_base`` is added to the indices.  ``into`` = the (idx, val) of earlier calls over other gallery chunks: the lists are merged in
-    place and returned."""
-    q, g = _f32_rows(queries), _f32_rows(gallery)
+    place and returned.  ``operands``: None | "f32" (anything not f32 is cast to f32) | "bf16" | "f16" (both operands end in that type; val stays f32)."""
+    typed = _operands(operands)
+    q, g = (_f32_rows(queries), _f32_rows(gallery)) if typed is None else (_rows16(queries, typed[1]), _rows16(gallery, typed[1]))
     nq, E = q.shape
     ng = g.shape[0]
     if g.shape[1] != E:
@@ -52,15 +76,17 @@ def topk(queries, gallery, k, *, col_base=0, into=None):
                 or not idx.is_contiguous() or not val.is_contiguous()):
             raise ValueError("into = (idx int32 [nq, k], val f32 [nq, k]), contiguous")
     ws = _workspace(dev, nq, ng, k)
-    _lib.call("lpi_search_topk", nq, ng, E, q, q.stride(0), g, g.stride(0), int(k), int(col_base), 0 if into is None else 1, idx, val, ws,
+    name, dt = ("lpi_search_topk", ()) if typed is None else ("lpi_search_topk_t", (typed[0],))
+    _lib.call(name, *dt, nq, ng, E, q, q.stride(0), g, g.stride(0), int(k), int(col_base), 0 if into is None else 1, idx, val, ws,
               ws.numel(), torch.cuda.current_stream().cuda_stream)
     return idx, val
 
 
-def gt_rank(queries, gallery, gt):
+def gt_rank(queries, gallery, gt, *, operands=None):
     """-> rank int32 [nq]: lpi_retrieval_rank of the score matrix the two feature sets would give, over the ground-truth list ``gt`` int32 [nq] or
-    [nq, gt_per_row] (entries < 0 are padding)."""
-    q, g = _f32_rows(queries), _f32_rows(gallery)
+    [nq, gt_per_row] (entries < 0 are padding).  ``operands`` as in ``topk``."""
+    typed = _operands(operands)
+    q, g = (_f32_rows(queries), _f32_rows(gallery)) if typed is None else (_rows16(queries, typed[1]), _rows16(gallery, typed[1]))
     nq, E = q.shape
     ng = g.shape[0]
     if g.shape[1] != E:
@@ -69,6 +95,7 @@ def gt_rank(queries, gallery, gt):
     gt = torch.as_tensor(gt).to(device=dev, dtype=torch.int32).reshape(nq, -1).contiguous()
     rank = torch.empty(nq, dtype=torch.int32, device=dev)
     ws = _workspace(dev, nq, ng, 0)
-    _lib.call("lpi_search_rank", nq, ng, E, q, q.stride(0), g, g.stride(0), gt, gt.shape[1], rank, ws, ws.numel(),
+    name, dt = ("lpi_search_rank", ()) if typed is None else ("lpi_search_rank_t", (typed[0],))
+    _lib.call(name, *dt, nq, ng, E, q, q.stride(0), g, g.stride(0), gt, gt.shape[1], rank, ws, ws.numel(),
               torch.cuda.current_stream().cuda_stream)
     return rank

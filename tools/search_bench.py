@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The streamed search (lpi_amd.search: lpi_search_rank / lpi_search_topk) against the matrix path (engine.score_matrix + lpi_retrieval_rank / lpi_topk),
+"""The streamed search (lpi_amd.search: lpi_search_rank / lpi_search_topk, and their bf16 / f16 forms lpi_search_rank_t / lpi_search_topk_t) against the
+matrix path (engine.score_matrix + lpi_retrieval_rank / lpi_topk),
 ONE process on one GPU, arms interleaved: time (HIP events, median of `--rounds` rounds' medians of `--steps` calls) and the growth of
 torch.cuda.max_memory_allocated over one call of each arm, at
 
@@ -11,11 +12,14 @@ torch.cuda.max_memory_allocated over one call of each arm, at
 
 The matrix arm of i2t / t2i is what the path does for one direction: score_matrix (the padded GEMM output, its copy and its transpose) + one
 lpi_retrieval_rank.  Rows unit-normalised Gaussian; ranks of the two arms are compared (they may differ where two scores lie within rounding: the GEMM
-kernels sum K in another order) and the count is recorded.
+kernels sum K in another order) and the count is recorded.  The bf16 / f16 arms (`operands=`) search copies of the operands cast ONCE, outside the
+timed region and before the peak is taken, as a gallery held in that type is; their ranks are compared with the f32 streamed arm's, which is the
+baseline their time is read against in the same run (rounding the rows moves scores by up to 2u + u^2, so ranks differ: the count is a description).
 
     python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large]
 
-writes profiles/search_stream.json.  An error ends the process: nothing further is started.  Run it under a time limit."""
+writes profiles/search_stream_2byte.json (profiles/search_stream.json is the record of the f32 arms alone, before the 2-byte arms existed).  An error
+ends the process: nothing further is started.  Run it under a time limit."""
 import argparse
 import json
 import os
@@ -73,13 +77,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--no-large", action="store_true")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "search_stream.json"))
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "search_stream_2byte.json"))
     a = ap.parse_args()
     import torch
     from lpi_amd import _lib, search
     from lpi_amd.engine import score_matrix
     gen = torch.Generator(device=DEV).manual_seed(0)
     E = 512
+    TWO_BYTE = (("bf16", torch.bfloat16), ("f16", torch.float16))
     img, txt = _unit(5000, E, gen), _unit(25000, E, gen)
     gt_i = (torch.arange(5000, device=DEV, dtype=torch.int32)[:, None] * 5 + torch.arange(5, device=DEV, dtype=torch.int32)[None, :]).contiguous()
     gt_t = (torch.arange(25000, device=DEV, dtype=torch.int32) // 5).view(-1, 1).contiguous()
@@ -105,6 +110,10 @@ def main():
             "matrix_top10": lambda q=q, g=g: matrix_topk(score_matrix(q, g)[0], 10),
             "streamed_top10": lambda q=q, g=g: search.topk(q, g, 10),
         }
+        for ops, tdt in TWO_BYTE:
+            q2, g2 = q.to(tdt), g.to(tdt)      # cast once, outside the timed region
+            arms["streamed_rank_" + ops] = lambda q2=q2, g2=g2, gt=gt, ops=ops: search.gt_rank(q2, g2, gt, operands=ops)
+            arms["streamed_top10_" + ops] = lambda q2=q2, g2=g2, ops=ops: search.topk(q2, g2, 10, operands=ops)
         out = _median_rounds(arms, a.rounds, a.steps)
         for k, fn in arms.items():
             out[k]["peak_bytes"] = _peak(fn)
@@ -113,6 +122,9 @@ def main():
         is_, _ = arms["streamed_top10"]()
         out["rank_rows_differing"] = int((rm != rs).sum())
         out["top10_rows_differing"] = int((im != is_).any(1).sum())
+        for ops, _ in TWO_BYTE:
+            out["rank_rows_differing_%s_vs_streamed_f32" % ops] = int((arms["streamed_rank_" + ops]() != rs).sum())
+            out["top10_rows_differing_%s_vs_streamed_f32" % ops] = int((arms["streamed_top10_" + ops]()[0] != is_).any(1).sum())
         out["rows"] = int(q.shape[0])
         out["workspace_bytes"] = {"rank": int(_lib.load().lpi_search_workspace(q.shape[0], g.shape[0], 0)),
                                   "top10": int(_lib.load().lpi_search_workspace(q.shape[0], g.shape[0], 10))}
@@ -140,7 +152,12 @@ def main():
         q, g = _unit(nq, E, gen), _unit(ng, E, gen)
         gt = (torch.arange(nq, device=DEV, dtype=torch.int32)[:, None] * 5 + torch.arange(5, device=DEV, dtype=torch.int32)[None, :]).contiguous()
         out = {"matrix": {"exists": False, "bytes_needed_for_three_f32_matrices": 3 * nq * ng * 4}}
-        for k, fn in (("streamed_rank", lambda: search.gt_rank(q, g, gt)), ("streamed_top10", lambda: search.topk(q, g, 10))):
+        large = [("streamed_rank", lambda: search.gt_rank(q, g, gt)), ("streamed_top10", lambda: search.topk(q, g, 10))]
+        for ops, tdt in TWO_BYTE:
+            q2, g2 = q.to(tdt), g.to(tdt)
+            large += [("streamed_rank_" + ops, lambda q2=q2, g2=g2, ops=ops: search.gt_rank(q2, g2, gt, operands=ops)),
+                      ("streamed_top10_" + ops, lambda q2=q2, g2=g2, ops=ops: search.topk(q2, g2, 10, operands=ops))]
+        for k, fn in large:
             search._WS.clear()
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
