@@ -613,6 +613,22 @@ int lpi_search_topk_t(int dt, int nq, int ng, int E, const void* Q, int ldq, con
                       int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
 int lpi_search_rank_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, const int32_t* gt, int gt_per_row,
                       int32_t* rank, void* ws, long ws_bytes, void* stream);
+/* The same two calls on MX-FP8 operands read in place (search_mx8.hip, since 616): Q / G are e4m3 bytes [n, ld] and q_scales / g_scales their E8M0
+ * scale bytes [n, lds], one per 32 consecutive elements of a row: the project's MX format, THE FORMAT below (what lpi_mx8_quantize writes).  1.03 bytes
+ * per gallery element.  s[i,j] is the f32 result of the chain of E / 128 block-scaled instructions (v_mfma_scale_f32_16x16x128_f8f6f4) over the two
+ * rows, in one fixed order: its bits depend on its two rows (elements and scales) only, so a chunked search equals one call bit for bit, duplicate rows
+ * (elements and scales alike) tie exactly and fall by index, and the rank threshold carries the sweep's bits.  val holds the scores of the QUANTISED
+ * rows.  The instruction aligns the 128 scaled products of a step before it adds them: a score is within 8.6e-5 |q| . |g| of the exact product of the
+ * dequantised rows (tests/test_search_mx8_gpu.py has the measured figure), and exact on data whose partial sums are exact.
+ * Envelope: nq, ng > 0; E a multiple of 128 and <= 1024 (one instruction covers 128 k-values: there is no tail); ldq / ldg >= E and multiples of 16,
+ * Q and G 16-byte aligned; ldqs / ldgs >= E / 32 and multiples of 4, the scale bases 4-byte aligned; no NULL operand or scale pointer; k, col_base,
+ * accumulate, gt, idx, val, rank, ws and lpi_search_workspace (which does not depend on the type) as for the f32 calls.  Anything else is LPI_EINVAL
+ * before any launch.  Nothing outside the n x E element bytes and the n x E / 32 scale bytes is read.  NaN element bytes (0x7F, 0xFF) and the scale
+ * byte 0xFF are out of contract, like non-finite inputs above.  lpi_search_topk_t / lpi_search_rank_t keep refusing dt = LPI_MX8. */
+int lpi_search_topk_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg, const void* g_scales,
+                        int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
+int lpi_search_rank_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg, const void* g_scales,
+                        int ldgs, const int32_t* gt, int gt_per_row, int32_t* rank, void* ws, long ws_bytes, void* stream);
 
 /* ---- a6 (host side): CLIP byte-level BPE      replaces: models/clip/simple_tokenizer.py:62-132, clip.py:185-221 ------
  * HOST functions (no GPU work, no stream).  create: `merges_utf8` is the decompressed text of bpe_simple_vocab_16e6.txt(.gz) —

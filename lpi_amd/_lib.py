@@ -141,6 +141,9 @@ SIGNATURES = {
     "lpi_search_rank": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P],
     "lpi_search_topk_t": [_I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],      # dt first: LPI_F32 | LPI_BF16 | LPI_F16 (search16.hip)
     "lpi_search_rank_t": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P],
+    # MX-FP8 operands: e4m3 bytes + E8M0 scales per operand (search_mx8.hip)
+    "lpi_search_topk_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "lpi_search_rank_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P],
     # host side: batch assembly of the input pipeline (pipeline.py), BPE tokenizer (a6)
     "lpi_host_gather": [_P, _P, _I, _L, _I],
     "lpi_host_gather_v": [_P, _P, _P, _I, _I],
@@ -170,7 +173,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 615
+EXPECTED_ABI = 616
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

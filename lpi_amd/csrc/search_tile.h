@@ -1,4 +1,5 @@
-// The tile code of the streamed search and the host logic of its two calls, for an operand type T: float (search.hip) or bf16_t / f16_t (search16.hip).
+// The tile code of the streamed search and the host logic of its two calls, for an operand type T: float (search.hip), bf16_t / f16_t (search16.hip) or
+// mx8_t (search_mx8.hip: e4m3 bytes + one E8M0 scale per 32 elements, mx8.h).
 //
 // Design:
 //  * the main loop is gemm.hip's: 128x128 tile, 4 waves as 2x2, K-contiguous operands staged one 128-byte row piece (BK = 32 f32 / 64 2-byte k-values) at
@@ -12,11 +13,19 @@
 //  * rank: a first launch of the same tile code over the ground-truth rows GATHERED by index (tile p, column c = ground truth p of query row c) leaves the
 //    threshold scores on the tiles' diagonals, with the bits the sweep computes for those columns; the sweep keeps one counter per owned row in registers
 //    and ends with one reduction and one integer atomicAdd per (row, workgroup);
+//  * MX-FP8 (T = mx8_t, everything under `if constexpr (kIsMx8<T>)`): a staged 128-byte row piece is 128 elements = ONE v_mfma_scale_f32_16x16x128_f8f6f4's
+//    K, so a slab is one k step and E is a multiple of 128: the two ds_read_b128 of a lane per sub tile (chunks g and 4 + g) are the instruction's eight
+//    operand registers.  The scale bytes of a slab, 4 per tile row, are staged behind the element tiles of the stage (2 x 512 B) by one
+//    global_load_lds of a dword per lane (waves 0, 1 the query rows, waves 2, 3 the gallery rows: clamped or gathered by the same row index as the
+//    elements) and read back with ds_read_u8 at row * 4 + (l >> 4): the register a lane hands the instruction holds the scale of row l & 15, K block
+//    l >> 4 (gemm_mx8.hip has the measured operand map).  Gallery = the instruction's first operand, queries its second, as mma_chunk's: the lane ends
+//    with the same acc[n][m], and the epilogues below are the same lines for every type;
 //  * top-k: every wave keeps a sorted list per row of its 64x64 quadrant's columns in LDS; scores are compared in registers with the row's current k-th
 //    and only survivors are inserted (the four lanes that share a row take turns).  Per-(split, wave column) lists go to the workspace, the merge
 //    kernel (search.hip, one for every operand type: it sees f32 scores only) writes idx / val.
 #pragma once
 #include "common.h"
+#include "mx8.h"
 #include <math.h>
 
 // search.hip: the launch of search_merge_kernel, the partial lists (and, with accumulate, the list idx / val already hold) -> idx / val
@@ -29,6 +38,8 @@ constexpr int BM = 128, BN = 128;
 constexpr int ROW_BYTES = 128;
 constexpr int TILE_BYTES = BM * ROW_BYTES;
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;
+constexpr int SCALE_BYTES = BM * 4;      // MX-FP8: the scale bytes of one operand's tile rows for one slab
+template <typename T> inline constexpr int kStageBytes = STAGE_BYTES + (kIsMx8<T> ? 2 * SCALE_BYTES : 0);
 constexpr int NTHREADS = 256;
 constexpr int KMAX = 16;
 constexpr int WG_TARGET = 512;      // workgroups wanted per launch: two per CU of an MI355X
@@ -49,6 +60,32 @@ struct SearchArgs {
     int32_t* rank;
     float* part_val;     // [2 * splits][nq][k]
     int32_t* part_idx;
+};
+
+// MX-FP8 operands carry their scale arrays ([rows, E/32] bytes with a leading dimension) beside the element pointers
+template <>
+struct SearchArgs<mx8_t> {
+    int nq, ng, E;
+    const mx8_t* Q;
+    int ldq;
+    const mx8_t* G;
+    int ldg;
+    int k, tiles, splits;
+    const int32_t* gt;
+    int gpr;
+    float* thr;
+    int32_t* gstar;
+    int32_t* rank;
+    float* part_val;
+    int32_t* part_idx;
+    const uint8_t* Qs;
+    int ldqs;
+    const uint8_t* Gs;
+    int ldgs;
+};
+struct SearchScales {      // what the host calls take for them; unused by the other types
+    const uint8_t* q; int ldq;
+    const uint8_t* g; int ldg;
 };
 
 // (s, j) before (v, i) in the order value descending, then index descending
@@ -76,7 +113,8 @@ template <typename T, int MODE>
 __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
 {
     constexpr int EPC = Elem<T>::EPC;                      // elements per 16-byte piece
-    constexpr int BK = ROW_BYTES / (int)sizeof(T);         // k-values per slab: two k steps of 4 pieces each
+    constexpr int BK = ROW_BYTES / (int)sizeof(T);         // k-values per slab: two k steps of 4 pieces each (MX-FP8: one step of 8)
+    constexpr int STAGE = kStageBytes<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -100,7 +138,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
     for (int i = 0; i < 4; ++i) qp[i] = a.Q + (size_t)min(m0 + srow + 32 * i, a.nq - 1) * a.ldq;
 
     auto stage = [&](int tile, int kt, int buf) {
-        char* base = smem + buf * STAGE_BYTES + wave * 1024;
+        char* base = smem + buf * STAGE + wave * 1024;
         int koff = kt * BK + schunk * EPC;
         if (koff >= a.E) koff -= BK / 2;      // the dead half of the last slab: staged from below E, never read
 #pragma unroll
@@ -121,6 +159,25 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.G + (size_t)gr * a.ldg + koff),
                                              (__attribute__((address_space(3))) void*)(base + TILE_BYTES + i * 4096), 16, 0, 0);
         }
+        if constexpr (kIsMx8<T>) {      // the slab's scales: lane = tile row (wave & 1) * 64 + lane of the queries (waves 0, 1) / the gallery (waves 2, 3)
+            const int r = (wave & 1) * 64 + lane;
+            const uint8_t* sp;
+            if (wave < 2) {
+                sp = a.Qs + (size_t)min(m0 + r, a.nq - 1) * a.ldqs;
+            } else {
+                int gr;
+                if constexpr (MODE == MODE_THRESH) {
+                    const int q = m0 + r;
+                    gr = q < a.nq ? a.gt[(size_t)q * a.gpr + tile] : -1;
+                    if ((unsigned)gr >= (unsigned)a.ng) gr = 0;
+                } else {
+                    gr = min(tile * BN + r, a.ng - 1);
+                }
+                sp = a.Gs + (size_t)gr * a.ldgs;
+            }
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp + kt * 4),
+                                             (__attribute__((address_space(3))) void*)(smem + buf * STAGE + 2 * TILE_BYTES + (wave >> 1) * SCALE_BYTES + (wave & 1) * 256), 4, 0, 0);
+        }
     };
 
     // ---- fragment read offsets: lane reads row (l&15) of a 16-row sub tile, logical chunk 4*ks + (l>>4)
@@ -130,6 +187,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
     for (int ks = 0; ks < 2; ++ks) foff[ks] = r16 * ROW_BYTES + (((ks << 2) | g) ^ fsw) * 16;
     const int a_frag_base = (wm * 64) * ROW_BYTES;               // query rows
     const int b_frag_base = TILE_BYTES + (wn * 64) * ROW_BYTES;  // gallery rows
+    const int a_sc_base = 2 * TILE_BYTES + (wm * 64 + r16) * 4 + g;                // MX-FP8: the lane's scale byte of its first query / gallery row
+    const int b_sc_base = 2 * TILE_BYTES + SCALE_BYTES + (wn * 64 + r16) * 4 + g;
 
     // ---- per-mode state.  A lane owns rows m0 + wm*64 + mi*16 + r16 (mi = 0..3) and, of each, columns wn*64 + ni*16 + 4g + 0..3 of the tile
     lds_f32* Lv = nullptr;      // MODE_TOPK: this wave's lists, [64 rows][k]
@@ -140,7 +199,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) { tv[mi] = -INFINITY; ti[mi] = -1; }
     if constexpr (MODE == MODE_TOPK) {
-        auto lists = (__attribute__((address_space(3))) char*)smem + 2 * STAGE_BYTES + wave * (64 * a.k * 8);
+        auto lists = (__attribute__((address_space(3))) char*)smem + 2 * STAGE + wave * (64 * a.k * 8);
         Lv = (lds_f32*)lists;
         Li = (lds_i32*)(lists + 64 * a.k * 4);
         for (int e = lane; e < 64 * a.k; e += 64) { Lv[e] = -INFINITY; Li[e] = -1; }
@@ -170,21 +229,44 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
             __syncthreads();                                  // ... and everyone's; buffer (it+1)&1 is free again
             if (kt + 1 < nk) stage(tile, kt + 1, (it + 1) & 1);
             else if (tile + 1 < t_end) stage(tile + 1, 0, (it + 1) & 1);
-            const char* buf = smem + (it & 1) * STAGE_BYTES;
-            const int nks = kt == nk - 1 ? ks_last : 2;
+            const char* buf = smem + (it & 1) * STAGE;
+            if constexpr (kIsMx8<T>) {
+                Chunk fa[4][2], fb[4][2];
+                int sa[4], sb[4];
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                if (ks < nks) {
-                    Chunk fa[4], fb[4];
+                for (int i = 0; i < 4; ++i) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        fa[i].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
-                        fb[i].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                    for (int ks = 0; ks < 2; ++ks) {
+                        fa[i][ks].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                        fb[i][ks].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
                     }
+                    sa[i] = *reinterpret_cast<const uint8_t*>(buf + a_sc_base + i * 64);      // rows 16 apart are 64 bytes apart
+                    sb[i] = *reinterpret_cast<const uint8_t*>(buf + b_sc_base + i * 64);
+                }
 #pragma unroll
-                    for (int ni = 0; ni < 4; ++ni)
+                for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-                        for (int mi = 0; mi < 4; ++mi) mma_chunk<T>(acc[ni][mi], fb[ni], fa[mi]);
+                    for (int mi = 0; mi < 4; ++mi)
+                        mx8_mma(acc[ni][mi], mx8_operand(fb[ni][0], fb[ni][1]), mx8_operand(fa[mi][0], fa[mi][1]), 0, sb[ni], 0, sa[mi]);
+                // hipcc sinks block-scaled instructions past barriers (gemm256_tile.h): an empty statement that "uses" the accumulators keeps them in their slab
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) asm volatile("" : "+v"(acc[ni][0]), "+v"(acc[ni][1]), "+v"(acc[ni][2]), "+v"(acc[ni][3]));
+            } else {
+                const int nks = kt == nk - 1 ? ks_last : 2;
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    if (ks < nks) {
+                        Chunk fa[4], fb[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            fa[i].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                            fb[i].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                        }
+#pragma unroll
+                        for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                            for (int mi = 0; mi < 4; ++mi) mma_chunk<T>(acc[ni][mi], fb[ni], fa[mi]);
+                    }
                 }
             }
         }
@@ -300,27 +382,33 @@ inline int search_splits(int nq, int ng)
     return tiles < want ? tiles : want;
 }
 
-// the envelope both calls share: E a multiple of half a slab (f32: 16, 2-byte: 32), rows of whole 16-byte pieces
+// the envelope both calls share: E a multiple of half a slab (f32: 16, 2-byte: 32; MX-FP8: of a whole one, 128), rows of whole 16-byte pieces; MX-FP8:
+// scale rows of whole dwords
 template <typename T>
-int search_check(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg)
+int search_check(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const SearchScales& sc)
 {
-    constexpr int EPC = Elem<T>::EPC, HALF = ROW_BYTES / (int)sizeof(T) / 2;
+    constexpr int EPC = Elem<T>::EPC, HALF = kIsMx8<T> ? ROW_BYTES : ROW_BYTES / (int)sizeof(T) / 2;
     if (nq <= 0 || ng <= 0 || E <= 0 || (E & (HALF - 1)) || E > 1024) return LPI_EINVAL;
     if (ldq < E || ldg < E || (ldq & (EPC - 1)) || (ldg & (EPC - 1))) return LPI_EINVAL;
     if (!Q || !G || (((uintptr_t)Q | (uintptr_t)G) & 15)) return LPI_EINVAL;
+    if constexpr (kIsMx8<T>) {
+        if (!sc.q || !sc.g || (((uintptr_t)sc.q | (uintptr_t)sc.g) & 3)) return LPI_EINVAL;
+        if (sc.ldq < E / 32 || sc.ldg < E / 32 || (sc.ldq & 3) || (sc.ldg & 3)) return LPI_EINVAL;
+    }
     return 0;
 }
 
 template <typename T>
 int search_topk(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, int k, int col_base, int accumulate, int32_t* idx, float* val,
-                void* ws, long ws_bytes, void* stream)
+                void* ws, long ws_bytes, void* stream, SearchScales sc = SearchScales{})
 {
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg)) return e;
+    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
     if (k < 1 || k > KMAX || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
     if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, k)) return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     SearchArgs<T> a{};
     a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
+    if constexpr (kIsMx8<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
     a.tiles = (ng + BN - 1) / BN;
     a.splits = search_splits(nq, ng);
     const size_t nlist = (size_t)2 * a.splits * nq * k;
@@ -328,21 +416,23 @@ int search_topk(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg,
     a.part_idx = (int32_t*)ws + nlist;
     auto kern = search_kernel<T, MODE_TOPK>;
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES + 4 * 64 * KMAX * 8)) return e;
-    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE_BYTES + 4 * 64 * k * 8, s, a);
+    constexpr int STAGE = kStageBytes<T>;
+    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE + 4 * 64 * KMAX * 8)) return e;
+    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE + 4 * 64 * k * 8, s, a);
     LPI_CHECK_LAST();
     return lpi_search_merge(nq, k, 2 * a.splits, a.part_val, a.part_idx, col_base, accumulate, idx, val, s);
 }
 
 template <typename T>
 int search_rank(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const int32_t* gt, int gt_per_row, int32_t* rank, void* ws,
-                long ws_bytes, void* stream)
+                long ws_bytes, void* stream, SearchScales sc = SearchScales{})
 {
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg)) return e;
+    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
     if (!gt || gt_per_row <= 0 || !rank || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, 0)) return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     SearchArgs<T> a{};
     a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg;
+    if constexpr (kIsMx8<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
     a.tiles = (ng + BN - 1) / BN;
     a.splits = search_splits(nq, ng);
     a.gt = gt; a.gpr = gt_per_row;
@@ -352,11 +442,12 @@ int search_rank(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg,
     auto kt = search_kernel<T, MODE_THRESH>;
     auto kr = search_kernel<T, MODE_RANK>;
     static LdsOnce once_t, once_r;
-    if (int e = lpi_ensure_lds(once_t, (const void*)kt, 2 * STAGE_BYTES)) return e;
-    if (int e = lpi_ensure_lds(once_r, (const void*)kr, 2 * STAGE_BYTES)) return e;
-    LPI_LAUNCH(kt, dim3((nq + BM - 1) / BM, 1), dim3(NTHREADS), 2 * STAGE_BYTES, s, a);
+    constexpr int STAGE = kStageBytes<T>;
+    if (int e = lpi_ensure_lds(once_t, (const void*)kt, 2 * STAGE)) return e;
+    if (int e = lpi_ensure_lds(once_r, (const void*)kr, 2 * STAGE)) return e;
+    LPI_LAUNCH(kt, dim3((nq + BM - 1) / BM, 1), dim3(NTHREADS), 2 * STAGE, s, a);
     LPI_CHECK_LAST();
-    LPI_LAUNCH(kr, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE_BYTES, s, a);
+    LPI_LAUNCH(kr, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE, s, a);
     LPI_CHECK_LAST();
     return 0;
 }

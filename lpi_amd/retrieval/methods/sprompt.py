@@ -103,12 +103,13 @@ def _eval_scores(args):
 
 
 def _eval_search_operands(args):
-    """eval_search_operands = 'f32' (default: the evaluation is unchanged bit for bit) | 'bf16' | 'f16': the operand type of the streamed search
-    (lpi_amd.search.gt_rank(..., operands=...)): the features are rounded to it once and searched at the 2-byte matrix rate.  It belongs to
+    """eval_search_operands = 'f32' (default: the evaluation is unchanged bit for bit) | 'bf16' | 'f16' | 'mx8': the operand type of the streamed
+    search (lpi_amd.search.gt_rank(..., operands=...)): the features are rounded to it once and searched at the 2-byte matrix rate, or ('mx8')
+    quantised once to MX-FP8 (e4m3 bytes + one scale per 32 elements) and searched on the block-scaled instruction.  It belongs to
     eval_scores = 'streamed': with 'matrix' a non-f32 value is a ValueError."""
     ops = args.get('eval_search_operands', 'f32')
-    if not isinstance(ops, str) or ops not in ('f32', 'bf16', 'f16'):
-        raise ValueError(f"unknown eval_search_operands {ops!r} (f32 | bf16 | f16)")
+    if not isinstance(ops, str) or ops not in ('f32', 'bf16', 'f16', 'mx8'):
+        raise ValueError(f"unknown eval_search_operands {ops!r} (f32 | bf16 | f16 | mx8)")
     if ops != 'f32' and _eval_scores(args) != 'streamed':
         raise ValueError(f"eval_search_operands={ops!r} is the operand type of eval_scores='streamed': it cannot go with "
                          f"eval_scores={_eval_scores(args)!r}")
@@ -463,6 +464,9 @@ class SPrompts(BaseLearner):
             gt_i, gt_t = self._gt_lists(ds.txt2img, ds.img2txt, image_feats.shape[0], num_text)
             ops = _eval_search_operands(self.args)
             kw = {} if ops == 'f32' else {'operands': ops}      # f32: the call as it was
+            if ops == 'mx8':      # quantised once each, searched in both directions
+                from lpi_amd import search
+                image_feats, text_feats = search.quantize_mx8(image_feats), search.quantize_mx8(text_feats)
             ranks_i = gt_rank(image_feats, text_feats, gt_i, **kw).cpu().numpy()
             ranks_t = gt_rank(text_feats, image_feats, gt_t, **kw).cpu().numpy()
             return None, None, self._recall_per_task(ranks_i, ranks_t, category_i, texts_cat)

@@ -4,7 +4,10 @@
 accumulators: memory is O(nq * k) instead of O(nq * ng).  A score's bits depend on its two rows only, so a gallery searched chunk by chunk
 (``col_base`` / ``into``) gives the result of one call bit for bit.  ``operands="bf16"`` / ``"f16"`` searches 2-byte operands (csrc/search16.hip): a
 tensor of that dtype is read in place, a score is the f32 sum in one fixed order of the exact products of the 2-byte values, and every property above
-holds.  There is no fall-back: a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, <= 1024; 1 <= k <= 16) raises."""
+holds.  ``operands="mx8"`` searches MX-FP8 operands (csrc/search_mx8.hip): e4m3 bytes with one E8M0 scale byte per 32 elements, an ``Mx8Rows`` (what
+``quantize_mx8`` returns), one byte per element plus the scales; an ``Mx8Rows`` is read in place, a float tensor is quantised once; a score is the f32
+result of the block-scaled instruction chain over E in one fixed order, of the QUANTISED rows, and the properties above hold.  There is no fall-back:
+a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, of 128 for MX-FP8, <= 1024; 1 <= k <= 16) raises."""
 from __future__ import annotations
 
 import torch
@@ -27,12 +30,106 @@ _OPERANDS = {"bf16": (_lib.BF16, torch.bfloat16), "f16": (_lib.F16, torch.float1
 
 
 def _operands(operands):
-    """None | 'f32' -> None (the f32 entry points); 'bf16' | 'f16' -> (LPI code, torch dtype)."""
+    """None | 'f32' -> None (the f32 entry points); 'bf16' | 'f16' -> (LPI code, torch dtype); 'mx8' -> 'mx8'."""
     if operands is None or operands == "f32":
         return None
+    if operands == "mx8":
+        return "mx8"
     if not isinstance(operands, str) or operands not in _OPERANDS:
-        raise ValueError(f"unknown operands {operands!r} (f32 | bf16 | f16)")
+        raise ValueError(f"unknown operands {operands!r} (f32 | bf16 | f16 | mx8)")
     return _OPERANDS[operands]
+
+
+class Mx8Rows:
+    """Rows in the project's MX-FP8 format (include/lpi_hip.h): ``codes`` uint8 [n, E] (e4m3fn bytes) and ``scales`` uint8 [n, E/32] (E8M0, one per 32
+    consecutive elements), as the search reads them in place: unit inner strides, a 16-byte row stride and base for the codes, a 4-byte row stride and
+    base for the scales.  Immutable; ``rows[a:b]`` is a view of rows a..b-1 (a gallery searched in chunks with ``col_base`` / ``into``)."""
+    __slots__ = ("codes", "scales")
+
+    def __init__(self, codes, scales):
+        for name, t in (("codes", codes), ("scales", scales)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2:
+                raise ValueError(f"Mx8Rows: {name} must be a uint8 tensor [rows, ...]")
+        n, E = codes.shape
+        if E == 0 or E % 32 or tuple(scales.shape) != (n, E // 32):
+            raise ValueError(f"Mx8Rows: codes [n, E] with E a multiple of 32 and scales [n, E / 32], got {tuple(codes.shape)} and {tuple(scales.shape)}")
+        if codes.device != scales.device:
+            raise ValueError("Mx8Rows: codes and scales on different devices")
+        for name, t, align in (("codes", codes, 16), ("scales", scales, 4)):
+            if t.stride(1) != 1 or t.stride(0) % align or t.stride(0) < t.shape[1] or t.data_ptr() % align:
+                raise ValueError(f"Mx8Rows: {name} needs a unit inner stride and a row stride and base that are multiples of {align} bytes")
+        object.__setattr__(self, "codes", codes)
+        object.__setattr__(self, "scales", scales)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Mx8Rows is immutable")
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    @property
+    def nbytes(self):
+        """The bytes of the elements and scales themselves (gaps of a strided view are not counted)."""
+        n, E = self.codes.shape
+        return n * E + n * (E // 32)
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    def __getitem__(self, rows):
+        if not isinstance(rows, slice) or rows.step not in (None, 1):
+            raise TypeError("Mx8Rows[a:b]: a slice of rows with step 1")
+        return Mx8Rows(self.codes[rows], self.scales[rows])
+
+
+_QUANT_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+
+
+def quantize_mx8(x):
+    """f32 / bf16 / f16 [n, E] on the device (E a multiple of 32) -> Mx8Rows: one lpi_mx8_quantize launch (bit for bit tests/mx8_emulate.quantize)."""
+    if x.dim() != 2:
+        raise ValueError("expected a [rows, E] tensor")
+    if x.dtype not in _QUANT_DT:
+        x = x.float()
+    n, E = x.shape
+    if n == 0 or E == 0 or E % 32:
+        raise ValueError(f"quantize_mx8: [n, E] with n > 0 and E a positive multiple of 32, got {tuple(x.shape)}")
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < E or x.data_ptr() % (4 * x.element_size()):
+        x = x.contiguous()
+    codes = torch.empty(n, E, dtype=torch.uint8, device=x.device)
+    lds = (E // 32 + 3) // 4 * 4      # scale rows of whole dwords
+    scales = torch.empty(n, lds, dtype=torch.uint8, device=x.device)[:, :E // 32]
+    _lib.call("lpi_mx8_quantize", _QUANT_DT[x.dtype], n, E, x, x.stride(0), codes, E, scales, lds, torch.cuda.current_stream().cuda_stream)
+    return Mx8Rows(codes, scales)
+
+
+def _prepare(queries, gallery, typed, form):
+    """The operands as `typed` (_operands) wants them -> (nq, ng, E, device, entry point of `form` = 'topk' | 'rank', its arguments up to the gallery's)."""
+    if typed != "mx8" and (isinstance(queries, Mx8Rows) or isinstance(gallery, Mx8Rows)):
+        raise ValueError('an Mx8Rows operand is searched with operands="mx8"')
+    if typed is None:
+        q, g = _f32_rows(queries), _f32_rows(gallery)
+    elif typed == "mx8":
+        q, g = (t if isinstance(t, Mx8Rows) else quantize_mx8(t) for t in (queries, gallery))
+    else:
+        q, g = _rows16(queries, typed[1]), _rows16(gallery, typed[1])
+    nq, E = q.shape
+    ng = g.shape[0]
+    if g.shape[1] != E:
+        raise ValueError(f"queries have {E} features, the gallery {g.shape[1]}")
+    if typed == "mx8":
+        if E % 128:
+            raise ValueError(f"MX-FP8 operands are searched with E a multiple of 128, not {E}")
+        return nq, ng, E, q.device, f"lpi_search_{form}_mx8", (nq, ng, E, q.codes, q.codes.stride(0), q.scales, q.scales.stride(0),
+                                                                g.codes, g.codes.stride(0), g.scales, g.scales.stride(0))
+    if typed is None:
+        return nq, ng, E, q.device, f"lpi_search_{form}", (nq, ng, E, q, q.stride(0), g, g.stride(0))
+    return nq, ng, E, q.device, f"lpi_search_{form}_t", (typed[0], nq, ng, E, q, q.stride(0), g, g.stride(0))
 
 
 def _rows16(t, dtype):
@@ -59,14 +156,10 @@ def _workspace(dev, nq, ng, k):
 def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
     """-> (idx int32 [nq, k], val f32 [nq, k]): per query row the k largest scores in the order (value descending, then index descending),
     lpi_topk's.  ``col_base`` is added to the indices.  ``into`` = the (idx, val) of earlier calls over other gallery chunks: the lists are merged in
-    place and returned.  ``operands``: None | "f32" (anything not f32 is cast to f32) | "bf16" | "f16" (both operands end in that type; val stays f32)."""
+    place and returned.  ``operands``: None | "f32" (anything not f32 is cast to f32) | "bf16" | "f16" (both operands end in that type; val stays f32)
+    | "mx8" (an Mx8Rows is read in place, a float tensor is quantised once; val = the scores of the quantised rows)."""
     typed = _operands(operands)
-    q, g = (_f32_rows(queries), _f32_rows(gallery)) if typed is None else (_rows16(queries, typed[1]), _rows16(gallery, typed[1]))
-    nq, E = q.shape
-    ng = g.shape[0]
-    if g.shape[1] != E:
-        raise ValueError(f"queries have {E} features, the gallery {g.shape[1]}")
-    dev = q.device
+    nq, ng, E, dev, name, lead = _prepare(queries, gallery, typed, "topk")
     if into is None:
         idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
         val = torch.empty(nq, k, dtype=torch.float32, device=dev)
@@ -76,9 +169,7 @@ def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
                 or not idx.is_contiguous() or not val.is_contiguous()):
             raise ValueError("into = (idx int32 [nq, k], val f32 [nq, k]), contiguous")
     ws = _workspace(dev, nq, ng, k)
-    name, dt = ("lpi_search_topk", ()) if typed is None else ("lpi_search_topk_t", (typed[0],))
-    _lib.call(name, *dt, nq, ng, E, q, q.stride(0), g, g.stride(0), int(k), int(col_base), 0 if into is None else 1, idx, val, ws,
-              ws.numel(), torch.cuda.current_stream().cuda_stream)
+    _lib.call(name, *lead, int(k), int(col_base), 0 if into is None else 1, idx, val, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
     return idx, val
 
 
@@ -86,16 +177,9 @@ def gt_rank(queries, gallery, gt, *, operands=None):
     """-> rank int32 [nq]: lpi_retrieval_rank of the score matrix the two feature sets would give, over the ground-truth list ``gt`` int32 [nq] or
     [nq, gt_per_row] (entries < 0 are padding).  ``operands`` as in ``topk``."""
     typed = _operands(operands)
-    q, g = (_f32_rows(queries), _f32_rows(gallery)) if typed is None else (_rows16(queries, typed[1]), _rows16(gallery, typed[1]))
-    nq, E = q.shape
-    ng = g.shape[0]
-    if g.shape[1] != E:
-        raise ValueError(f"queries have {E} features, the gallery {g.shape[1]}")
-    dev = q.device
+    nq, ng, E, dev, name, lead = _prepare(queries, gallery, typed, "rank")
     gt = torch.as_tensor(gt).to(device=dev, dtype=torch.int32).reshape(nq, -1).contiguous()
     rank = torch.empty(nq, dtype=torch.int32, device=dev)
     ws = _workspace(dev, nq, ng, 0)
-    name, dt = ("lpi_search_rank", ()) if typed is None else ("lpi_search_rank_t", (typed[0],))
-    _lib.call(name, *dt, nq, ng, E, q, q.stride(0), g, g.stride(0), gt, gt.shape[1], rank, ws, ws.numel(),
-              torch.cuda.current_stream().cuda_stream)
+    _lib.call(name, *lead, gt, gt.shape[1], rank, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
     return rank

@@ -16,10 +16,16 @@ kernels sum K in another order) and the count is recorded.  The bf16 / f16 arms 
 timed region and before the peak is taken, as a gallery held in that type is; their ranks are compared with the f32 streamed arm's, which is the
 baseline their time is read against in the same run (rounding the rows moves scores by up to 2u + u^2, so ranks differ: the count is a description).
 
-    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large]
+    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8]
 
-writes profiles/search_stream_2byte.json (profiles/search_stream.json is the record of the f32 arms alone, before the 2-byte arms existed).  An error
-ends the process: nothing further is started.  Run it under a time limit."""
+writes profiles/search_stream_2byte.json (profiles/search_stream.json is the record of the f32 arms alone, before the 2-byte arms existed).
+
+--mx8: the MX-FP8 arm (`operands="mx8"` on Mx8Rows quantised ONCE, outside the timed region and before the peak is taken, as a gallery held in that
+format is) beside the f32 and bf16 streamed arms of the same run, and nothing else: rank and top-10 at i2t / t2i and, unless --no-large, at train.
+Against the f32 streamed arm it records the rows whose rank differs and the mean overlap of the top-10 index sets (descriptions: MX rounding moves
+scores).  It writes profiles/search_stream_mx8.json and leaves the other two records alone.
+
+An error ends the process: nothing further is started.  Run it under a time limit."""
 import argparse
 import json
 import os
@@ -72,13 +78,94 @@ def _peak(fn):
     return int(peak)
 
 
+def _overlap10(i_a, i_b):
+    """Mean over the rows of |top-10 set a & top-10 set b| / 10."""
+    return float((i_a[:, :, None] == i_b[:, None, :]).any(2).float().mean())
+
+
+def _timed_once(fn):
+    import torch
+    from lpi_amd import search
+    search._WS.clear()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    r = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return r, e0.elapsed_time(e1), int(torch.cuda.max_memory_allocated() - base)
+
+
+def _mx8_arms(a, res, img, txt, gt_i, gt_t, gen):
+    """--mx8: streamed f32 / bf16 / mx8, rank and top-10, interleaved in this process."""
+    import torch
+    from lpi_amd import search
+    E = img.shape[1]
+    for name, q, g, gt in (("i2t_5000x25000", img, txt, gt_i), ("t2i_25000x5000", txt, img, gt_t)):
+        q2, g2 = q.bfloat16(), g.bfloat16()                          # cast / quantised once, outside the timed region
+        q8, g8 = search.quantize_mx8(q), search.quantize_mx8(g)
+        arms = {
+            "streamed_rank": lambda q=q, g=g, gt=gt: search.gt_rank(q, g, gt),
+            "streamed_rank_bf16": lambda q2=q2, g2=g2, gt=gt: search.gt_rank(q2, g2, gt, operands="bf16"),
+            "streamed_rank_mx8": lambda q8=q8, g8=g8, gt=gt: search.gt_rank(q8, g8, gt, operands="mx8"),
+            "streamed_top10": lambda q=q, g=g: search.topk(q, g, 10),
+            "streamed_top10_bf16": lambda q2=q2, g2=g2: search.topk(q2, g2, 10, operands="bf16"),
+            "streamed_top10_mx8": lambda q8=q8, g8=g8: search.topk(q8, g8, 10, operands="mx8"),
+        }
+        out = _median_rounds(arms, a.rounds, a.steps)
+        for k, fn in arms.items():
+            out[k]["peak_bytes"] = _peak(fn)
+            out[k]["tflops"] = round(2.0 * q.shape[0] * g.shape[0] * E / (out[k]["ms"] * 1e-3) / 1e12, 2)
+        rs, is_ = arms["streamed_rank"](), arms["streamed_top10"]()[0]
+        for ops in ("bf16", "mx8"):
+            out["rank_rows_differing_%s_vs_streamed_f32" % ops] = int((arms["streamed_rank_" + ops]() != rs).sum())
+            out["top10_overlap_%s_vs_streamed_f32" % ops] = round(_overlap10(arms["streamed_top10_" + ops]()[0], is_), 4)
+        out["rows"] = int(q.shape[0])
+        out["gallery_bytes"] = {"f32": g.shape[0] * E * 4, "bf16": g.shape[0] * E * 2, "mx8": g8.nbytes}
+        res["shapes"][name] = out
+        print(name, json.dumps(out), flush=True)
+    if a.no_large:
+        return
+    nq, ng = 123287, 616767
+    del q, g, q2, g2, q8, g8, arms
+    torch.cuda.empty_cache()
+    q, g = _unit(nq, E, gen), _unit(ng, E, gen)
+    gt = (torch.arange(nq, device=DEV, dtype=torch.int32)[:, None] * 5 + torch.arange(5, device=DEV, dtype=torch.int32)[None, :]).contiguous()
+    q2, g2 = q.bfloat16(), g.bfloat16()
+    q8, g8 = search.quantize_mx8(q), search.quantize_mx8(g)
+    out, kept = {}, {}
+    for k, fn in (("streamed_rank", lambda: search.gt_rank(q, g, gt)),
+                  ("streamed_rank_bf16", lambda: search.gt_rank(q2, g2, gt, operands="bf16")),
+                  ("streamed_rank_mx8", lambda: search.gt_rank(q8, g8, gt, operands="mx8")),
+                  ("streamed_top10", lambda: search.topk(q, g, 10)),
+                  ("streamed_top10_bf16", lambda: search.topk(q2, g2, 10, operands="bf16")),
+                  ("streamed_top10_mx8", lambda: search.topk(q8, g8, 10, operands="mx8"))):
+        r, ms, peak = _timed_once(fn)
+        kept[k] = r if "rank" in k else r[0][:4096].clone()      # the quality figures of the top-10 form on the first 4 096 rows
+        out[k] = {"ms": round(ms, 2), "calls_timed": 1, "peak_bytes": peak, "tflops": round(2.0 * nq * ng * E / (ms * 1e-3) / 1e12, 2)}
+        del r
+        print(k, json.dumps(out[k]), flush=True)
+    for ops in ("bf16", "mx8"):
+        out["rank_rows_differing_%s_vs_streamed_f32" % ops] = int((kept["streamed_rank_" + ops] != kept["streamed_rank"]).sum())
+        out["top10_overlap_%s_vs_streamed_f32_first_4096_rows" % ops] = round(_overlap10(kept["streamed_top10_" + ops], kept["streamed_top10"]), 4)
+    out["rows"] = nq
+    out["gallery_bytes"] = {"f32": ng * E * 4, "bf16": ng * E * 2, "mx8": g8.nbytes}
+    res["shapes"]["train_123287x616767"] = out
+    print("train", json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--no-large", action="store_true")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "search_stream_2byte.json"))
+    ap.add_argument("--mx8", action="store_true", help="the f32, bf16 and MX-FP8 streamed arms only -> profiles/search_stream_mx8.json")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "search_stream_mx8.json" if a.mx8 else "search_stream_2byte.json")
     import torch
     from lpi_amd import _lib, search
     from lpi_amd.engine import score_matrix
@@ -103,6 +190,13 @@ def main():
         return idx, val
 
     res = {"device": torch.cuda.get_device_name(0), "abi": int(_lib.load().lpi_version()), "rounds": a.rounds, "steps": a.steps, "E": E, "shapes": {}}
+    if a.mx8:
+        _mx8_arms(a, res, img, txt, gt_i, gt_t, gen)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print("wrote", a.out)
+        return
     for name, q, g, gt in (("i2t_5000x25000", img, txt, gt_i), ("t2i_25000x5000", txt, img, gt_t)):
         arms = {
             "matrix_rank": lambda q=q, g=g, gt=gt: matrix_rank(score_matrix(q, g)[0], gt),
