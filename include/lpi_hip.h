@@ -234,7 +234,27 @@ int lpi_gather_batch_rows(int dtype, int B, int L, int row0, int P, int cols, co
  * dqkv: [B*L, 3*d] `dtype`.  L <= 288: one workgroup per (sample, head) keeps the head's K and V in LDS (attention.hip, attention4.hip).  Round 6: NON-CAUSAL
  * UNIFORM sequences of 288 < L <= 1024 tokens (ViT-L/14@336px: 577 + prompts) run tiled over the keys with an online softmax (attn_long.hip: forward one
  * launch, backward two — dQ + delta, then dK / dV; the backward computes every row, `rows_needed` of the _prefix form is ignored there); causal or ragged
- * sequences of that length are refused with LPI_EINVAL. */
+ * sequences of that length are refused with LPI_EINVAL.
+ *
+ * Alignment of the attention operands (every entry point of this section and of the _varlen / _prefix / _layout / _shared / pooled / spool forms below; anything
+ * else is LPI_EINVAL before any launch; each leading dimension is its own argument and may differ from every other — tests/test_attn_strides_gpu.py).  The rule
+ * is the widest access the kernels make to the operand: 16-byte row loads and stores for matrices, one element for what a lane stores alone.
+ *   lpi_attn_fwd / _varlen / _shared / _pair (interleaved): ldqkv >= 3 H 64 and a whole number of 16-byte units; ldctx >= H 64 and a multiple of 8 ELEMENTS for
+ *     every dtype (f32 too: stricter than its 16-byte stores need); qkv, ctx 16-byte aligned.
+ *   lpi_attn_bwd / _varlen / _prefix / _shared: ldqkv, lddqkv >= 3 H 64, ldctx, lddctx >= H 64, each a whole number of 16-byte units; qkv, ctx, dctx, dqkv (and
+ *     shared_dkv) 16-byte aligned.  A ctx that goes through both directions therefore takes ldctx in multiples of 8 elements.
+ *   layout forms (lpi_attn_fwd_one / _pair with layout strides, lpi_attn_bwd_layout; 2-byte types): every leading dimension and layout stride >= 64 and a multiple
+ *     of 8 elements; the same pointers 16-byte aligned.
+ *   lpi_shared_kv_reduce: lddqkv >= 3 H 64 and a multiple of 4 elements; partial 16-byte aligned, dqkv 8-byte (2-byte types) / 16-byte (f32) aligned.
+ *   lpi_attn_pooled_* (all forms): ldqkv >= 3 H 64, ldq, lddctx >= H 64, whole 16-byte units, q, qkv, dctx 16-byte aligned (read four elements at a time); ctx, dq
+ *     and dqkv are stored one element at a time: ldctx, lddq >= H 64 and lddqkv >= 3 H 64 in ANY step, no pointer alignment beyond the element's.  With
+ *     shared_rows > 0 (lpi_attn_pooled_bwd_desc / _bwd_pair) dqkv and shared_dkv go through lpi_shared_kv_reduce behind the pooled kernel, so that function's
+ *     rule holds for them and is refused BEFORE that kernel: lddqkv a multiple of 4 elements, dqkv 8-byte (f32: 16-byte) aligned, shared_dkv 16-byte aligned
+ *     (since 617; up to 616 such a call returned LPI_EINVAL from the reduce, after the pooled kernel had run).
+ *   lpi_spool_attn_fwd / _bwd: ldx, ldw, ldq, lddctx >= d, ldwt >= 3 d, multiples of 8 elements, x, Wqkv, WqkvT, q, dctx 16-byte aligned; lddh >= d and a multiple
+ *     of 4 elements, dh 8-byte aligned (8-byte stores); ctx and dq are stored one element at a time: ldctx, lddq >= d in any step.  scratch, gamma and beta are
+ *     moved four floats at a time: 16-byte aligned (since 617; not checked up to 616).  bqkv, mean, rstd, lse: one float at a time.
+ *   lse / delta: f32, written one element at a time, inside [B, H, L] ((B + 1) H L on a shared prefix) — never for the rows between L and the 32-row tile. */
 int lpi_attn_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx,
                  float* lse, int causal, void* stream);
 int lpi_attn_bwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx,

@@ -316,6 +316,8 @@ extern "C" int lpi_attn_pooled_bwd_pair(int dtype, const lpi_attn_pooled_desc* d
         const int Lp = (q.L + 63) / 64 * 64;
         lds = std::max(lds, (size_t)(3 * Lp + WPB * DH) * sizeof(float));
         if (q.shared_rows < 0 || (q.shared_rows > 0 && (!q.causal || !q.row_start || !q.idx || q.shared_rows >= q.L || !q.shared_dkv))) return LPI_EINVAL;
+        // shared prefix: dqkv and shared_dkv go through lpi_shared_kv_reduce after the launch (four elements per lane): its conditions are refused here, before it
+        if (q.shared_rows > 0 && ((q.lddqkv & 3) || ((uintptr_t)q.shared_dkv & 15) || ((uintptr_t)q.dqkv & (dtype == LPI_F32 ? 15 : 7)))) return LPI_EINVAL;
         p[i] = PoolBwdP{q.B, q.L, q.H, Lp, q.ldq, q.ldqkv, q.lddctx, q.lddq, q.lddqkv, q.causal, q.row_start, q.q, q.qkv, q.idx, q.dctx, q.lse, q.dq, q.dqkv, q.shared_rows,
                         q.shared_dkv};
     }
@@ -377,6 +379,8 @@ extern "C" int lpi_attn_pooled_bwd_desc(int dtype, const lpi_attn_pooled_desc* d
     const int esz = dtype == LPI_F32 ? 4 : 2;
     if ((d->ldqkv * esz) % 16 || (d->ldq * esz) % 16 || (d->lddctx * esz) % 16) return LPI_EINVAL;
     if (((uintptr_t)d->q | (uintptr_t)d->qkv | (uintptr_t)d->dctx) & 15) return LPI_EINVAL;
+    // dqkv and shared_dkv go through lpi_shared_kv_reduce after the launch (four elements per lane): its conditions are refused here, before any launch
+    if ((d->lddqkv & 3) || ((uintptr_t)d->shared_dkv & 15) || ((uintptr_t)d->dqkv & (dtype == LPI_F32 ? 15 : 7))) return LPI_EINVAL;
     const int Lp = (d->L + 63) / 64 * 64;
     const size_t lds = (size_t)(3 * Lp + WPB * DH) * sizeof(float);
     if (lds > 64 * 1024) return LPI_EINVAL;

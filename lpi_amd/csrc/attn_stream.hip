@@ -535,7 +535,8 @@ extern "C" int lpi_spool_attn_fwd(int w_dtype, int B, int L, int H, const void* 
     const int d = HD * H;
     if (!q || !Wqkv || !WqkvT || !bqkv || !x || !mean || !rstd || !gamma || !beta || !scratch || !lse || !ctx || B <= 0) return LPI_EINVAL;
     if ((w_dtype != LPI_BF16 && w_dtype != LPI_F16) || !spool_ok(L, H, d) || ldq < d || ldw < d || ldwt < 3 * d || ldx < d || ldctx < d || ((ldx | ldw | ldwt | ldq) & 7) ||
-        (((uintptr_t)x | (uintptr_t)Wqkv | (uintptr_t)WqkvT | (uintptr_t)q) & 15))
+        (((uintptr_t)x | (uintptr_t)Wqkv | (uintptr_t)WqkvT | (uintptr_t)q) & 15) ||
+        (((uintptr_t)scratch | (uintptr_t)gamma | (uintptr_t)beta) & 15))      // qt / hbar, gamma and beta are moved as f32x4
         return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     float* qt = scratch;
@@ -557,7 +558,8 @@ extern "C" int lpi_spool_attn_bwd(int B, int L, int H, const void* Wqkv, int ldw
     const int d = HD * H;
     if (!Wqkv || !WqkvT || !x || !mean || !rstd || !gamma || !scratch || !lse || !dctx || !dq || !dh || B <= 0) return LPI_EINVAL;
     if (!spool_ok(L, H, d) || ldw < d || ldwt < 3 * d || ldx < d || lddctx < d || lddq < d || lddh < d || ((ldx | ldw | ldwt | lddctx) & 7) || (lddh & 3) ||
-        (((uintptr_t)x | (uintptr_t)Wqkv | (uintptr_t)WqkvT | (uintptr_t)dctx) & 15) || ((uintptr_t)dh & 7))
+        (((uintptr_t)x | (uintptr_t)Wqkv | (uintptr_t)WqkvT | (uintptr_t)dctx) & 15) || ((uintptr_t)dh & 7) ||
+        (((uintptr_t)scratch | (uintptr_t)gamma) & 15))      // qt / dhbar / dqt and gamma are moved as f32x4
         return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * H * d;

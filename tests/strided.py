@@ -9,7 +9,9 @@ or a 16-byte store that runs over a row's end from one that does not.  Here ever
     * every arena element OUTSIDE the view's footprint {col0 + r * ld + c} holds PAD, a NaN (set by bit pattern): read into a result it
       shows as NaN, written it shows in `check_pads`, which compares the arena's bits with those of before the call;
     * an INPUT (fill = a [rows, cols] tensor) holds its live values in the footprint;
-    * an OUTPUT (fill = None) holds UNWRITTEN there, a second NaN with other bits: `check_written` finds what the kernel left out.
+    * an OUTPUT (fill = None) holds UNWRITTEN there, a second NaN with other bits: `check_written` finds what the kernel left out.  Where a
+      call MAY leave a part of its output untouched (the rows behind `rows_needed` of an attention backward, a scratch block whose contents
+      are unspecified), `must_write` narrows what `check_written` asks for: the rest of the footprint is neither a pad nor a must.
 
 THE SAFETY RULE (arena sizing).  Within one test case EVERY arena has the same size in bytes, `arena_bytes(...)`, worked out from the
 LARGEST row count, the LARGEST leading dimension and the LARGEST element size of ANY operand of that case, plus the base offset col0:
@@ -42,6 +44,7 @@ class Record:
 
     def __init__(self, t, arena, inside, output):
         self.t, self.arena, self.inside, self.output = t, arena, inside, output
+        self.must = inside      # the part of an output's footprint the call MUST write (narrowed by `must_write`)
         self.before = bits(arena).clone()
 
 
@@ -84,6 +87,28 @@ def operand(rows, cols, ld, dtype, col0, arena_elems, fill=None, device="cpu"):
     return Record(view, arena, inside, fill is None)
 
 
+def must_write(rec, rows=None, none=False, index=None):
+    """Narrow what `check_written` asks of the output `rec`.  Give one of:
+        rows   an `operand` view: a count (the first rows) or a list of row indices;
+        index  a `region`: the arena elements;
+        none   True: nothing must be written (contents unspecified).
+    The rest of the footprint may be written or left: neither `check_pads` nor `check_written` looks at it."""
+    assert rec.output
+    must = torch.zeros_like(rec.inside)
+    if index is not None:
+        must[torch.as_tensor(index, dtype=torch.int64, device=must.device)] = True
+        assert not bool((must & ~rec.inside).any())
+    elif not none:
+        assert rec.t.dim() == 2
+        r = torch.arange(rows) if isinstance(rows, int) else torch.as_tensor(rows, dtype=torch.int64)
+        assert r.numel() > 0 and int(r.min()) >= 0 and int(r.max()) < rec.t.shape[0]
+        col0 = (rec.t.data_ptr() - rec.arena.data_ptr()) // rec.arena.element_size()
+        idx = col0 + r[:, None] * rec.t.stride(0) + torch.arange(rec.t.shape[1])[None, :]
+        must[idx.reshape(-1).to(must.device)] = True
+    rec.must = must
+    return rec
+
+
 def check_pads(name, rec):
     """Every arena element outside the footprint still has the bits it had before the call (integer compare: NaN payloads count)."""
     now = bits(rec.arena)
@@ -95,8 +120,8 @@ def check_pads(name, rec):
 
 
 def check_written(name, rec):
-    """No footprint element of an output still holds UNWRITTEN."""
+    """No must-be-written footprint element of an output still holds UNWRITTEN."""
     assert rec.output, name
-    left = (bits(rec.arena) == UNWRITTEN[rec.arena.dtype]) & rec.inside
+    left = (bits(rec.arena) == UNWRITTEN[rec.arena.dtype]) & rec.must
     n = int(left.sum())
-    assert n == 0, f"{name}: {n} of {int(rec.inside.sum())} output elements were never written (first at arena element {int(left.nonzero()[0]) if n else -1})"
+    assert n == 0, f"{name}: {n} of {int(rec.must.sum())} output elements were never written (first at arena element {int(left.nonzero()[0]) if n else -1})"
