@@ -186,7 +186,25 @@ int lpi_gemm_nt_rows(int dtype, int c_dtype, int epilogue, float alpha, int coun
  * bwd: dx[r,:] (f32, in/out: residual-stream gradient) += LN'(dy[r,:]); optionally also writes a `cast_dtype`
  *      copy dx_cast (the next dgrad GEMM's operand).  dx == NULL: dx_cast itself is the in/out gradient stream (bf16 mode keeps
  *      no f32 copy).  dy is `dy_dtype`.  accumulate == 0: the gradient stream is WRITTEN (= LN'(dy)) instead of added to — the first
- *      backward kernel of a tower then needs no zero-fill of the [rows, d] stream. */
+ *      backward kernel of a tower then needs no zero-fill of the [rows, d] stream.
+ *
+ * Leading dimensions and alignment of the row operations (this section, the pooled heads, the vision front end, lpi_row_jobs and the MX-FP8 rows below;
+ * anything else is LPI_EINVAL before any launch — for a pair or a job list before the FIRST launch; each leading dimension is its own argument and may differ
+ * from every other — tests/test_rowop_strides_gpu.py).  The rule is the widest access the kernels make to the operand (since 618; up to 617 the row kernels
+ * only asked for leading dimensions in multiples of four elements):
+ *   a [rows, d] operand with a row stride (x / ldx, y / ldy, dy / lddy, dx / lddx, dx_cast / ldcast, patch_emb / ldpe, cols / ldcols) is moved FOUR ELEMENTS at a
+ *     time: d a multiple of 4 (<= 2048), ld >= d and a multiple of 4 elements, the pointer aligned to 4 elements (16 bytes f32, 8 bytes bf16 / f16).  dx == NULL /
+ *     dx_cast == NULL: lddx / ldcast still a multiple of 4 (their size is not looked at).  Streams without a row stride of their own ([B L, d]: x, dx, dx_cast of
+ *     lpi_pool_ln_*, x0, dx0, the x of lpi_prompt_add) take the same pointer rule;
+ *   gamma, beta, cls, pos, prompt0 / prompt_l / ctx rows, dprompt, the f32 copy `out2` of POOL_LN_FWD: read or written as four floats, 16-byte aligned;
+ *     mean, rstd, inv_norm, the statistics outputs: one float, no rule;
+ *   the fp16-stream LayerNorms move 16 bytes per lane (a half wave per row) when d and every leading dimension of the call are multiples of 8 and x, y (dy, x,
+ *     dx_cast with dx == NULL) are 16-byte aligned, and the four-element kernels otherwise: the leading dimension picks the kernel, the results are the same.  The
+ *     statistics-only form (y == NULL), the fused pair launch and LN_BWD_ROWS_H16 have the 16-byte kernel only: those conditions are required;
+ *   lpi_gather_batch_rows(_varlen): whole 16-byte units (cols, ld_src >= cols, ld_dst >= cols, both pointers); lpi_scatter_add_rows / SCATTER_ADD: the four-element rule
+ *     above for src / ld_src and dst / ld_dst (up to 617 f32 rows were held to 8 bytes); lpi_transpose(2), lpi_copy_rows, lpi_ln_stats_finalize(_pair): one element per lane — lds >= cols, ldd >= rows (ld >= rows), any step;
+ *   lpi_mx8_quantize / lpi_layernorm_mx8_fwd: ldx >= K (d) in multiples of 4, x aligned to 4 elements, ldq >= K in multiples of 4 with q 4-byte aligned, lds >=
+ *     K / 32 in any step (one scale byte per store), gamma / beta 16-byte aligned — unchanged, each exactly as wide as its access. */
 int lpi_layernorm_fwd(int dtype, int x_dtype, int rows, int d, const void* x, int ldx, const float* gamma, const float* beta,
                       void* y, int ldy, float* mean, float* rstd, void* stream);
 int lpi_layernorm_bwd(int dy_dtype, int cast_dtype, int x_dtype, int rows, int d, const void* dy, int lddy,

@@ -418,7 +418,8 @@ extern "C" int lpi_scatter_add_rows(int dtype, int B, int L, int d, const void* 
 {
     if (!src || !dst || B <= 0 || L < 0 || (L == 0 && !idx) || d <= 0 || (d & 3) || ld_src < d || ld_dst < d) return LPI_EINVAL;      // L == 0: idx holds absolute rows
     const int esz = dtype == LPI_F32 ? 4 : 2;
-    if ((ld_src * esz) % 8 || (ld_dst * esz) % 8 || (((uintptr_t)src | (uintptr_t)dst) & 7)) return LPI_EINVAL;
+    // rows are moved four elements at a time (Elem<T>::ld4 / st4): 16 bytes of f32, 8 bytes of bf16 (up to 617 f32 rows were held to 8 bytes only)
+    if ((ld_src & 3) || (ld_dst & 3) || (((uintptr_t)src | (uintptr_t)dst) & (uintptr_t)(4 * esz - 1))) return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LPI_F32)
         LPI_LAUNCH((scatter_add_rows_kernel<float>), dim3(B), dim3(256), 0, s, B, L, d, (const float*)src, ld_src, idx, (float*)dst, ld_dst);

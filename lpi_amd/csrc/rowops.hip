@@ -914,17 +914,36 @@ static int nc_of(int d) { const int n = (d + 255) / 256; return n <= 4 ? n : 0; 
 static bool ln_h16_ok(int d, int ld0, int ld1, const void* p0, const void* p1) {
     return !(d & 7) && !(ld0 & 7) && !(ld1 & 7) && !(((uintptr_t)p0 | (uintptr_t)p1) & 15) && nc_of(d) != 0;
 }
+// The argument rules of this family (include/lpi_hip.h, "Leading dimensions and alignment of the row operations"): what the kernels above do to a row.
+// row4_ok: a [rows, d] operand moved FOUR ELEMENTS at a time (Elem<T>::ld4 / st4: one 16-byte access of f32, one 8-byte access of a 2-byte type) at
+// p + row * ld + 4 c: the row stride covers the width (rows of an output must not overlap) and is a multiple of four elements, the pointer is aligned to
+// the access.  al16: a vector read or written as f32x4 (gamma, beta, cls, pos, prompt rows, every f32 row).
+static int esz_of(int dt) { return dt == LPI_F32 ? 4 : 2; }
+static bool al16(const void* p) { return !((uintptr_t)p & 15); }
+static bool row4_ok(const void* p, long ld, int d, int dt) { return ld >= d && !(ld & 3) && !((uintptr_t)p & (uintptr_t)(4 * esz_of(dt) - 1)); }
+static bool ln_fwd_args_ok(int dtype, int x_dtype, int rows, int d, const void* x, int ldx, const float* gamma, const float* beta, const void* y, int ldy,
+                           const float* mean, const float* rstd) {
+    if (!y)      // statistics only: the half-wave kernel alone (16-byte loads of x; gamma / beta unused)
+        return x && mean && rstd && rows > 0 && !bad_row_dim(d) && x_dtype == LPI_F16 && ldx >= d && ln_h16_ok(d, ldx, 0, x, nullptr);
+    return x && gamma && beta && mean && rstd && rows > 0 && !bad_row_dim(d) && row4_ok(x, ldx, d, x_dtype) && row4_ok(y, ldy, d, dtype) && al16(gamma) && al16(beta);
+}
+static bool ln_bwd_args_ok(int dy_dtype, int cast_dtype, int x_dtype, int rows, int d, const void* dy, int lddy, const void* x, int ldx, const float* gamma,
+                           const float* mean, const float* rstd, const float* dx, int lddx, const void* dx_cast, int ldcast) {
+    if (!dy || !x || !gamma || !mean || !rstd || (!dx && !dx_cast) || rows <= 0 || bad_row_dim(d) || (lddx & 3) || (ldcast & 3)) return false;
+    return row4_ok(dy, lddy, d, dy_dtype) && row4_ok(x, ldx, d, x_dtype) && al16(gamma) && (!dx || row4_ok(dx, lddx, d, LPI_F32)) &&
+           (!dx_cast || row4_ok(dx_cast, ldcast, d, cast_dtype));
+}
 extern "C" int lpi_layernorm_fwd(int dtype, int x_dtype, int rows, int d, const void* x, int ldx, const float* gamma, const float* beta,
                                  void* y, int ldy, float* mean, float* rstd, void* stream) {
     if (!y) {      // statistics only (fp16 stream): mean / rstd of every row, nothing else written
-        if (!x || !mean || !rstd || rows <= 0 || bad_row_dim(d) || x_dtype != LPI_F16 || !ln_h16_ok(d, ldx, 0, x, nullptr)) return LPI_EINVAL;
+        if (!ln_fwd_args_ok(dtype, x_dtype, rows, d, x, ldx, gamma, beta, y, ldy, mean, rstd)) return LPI_EINVAL;
 #define LNS(NC) LPI_LAUNCH((ln_fwd_h16_kernel<NC, void>), dim3((rows + 7) / 8), dim3(256), 0, S(stream), rows, d, (const f16_t*)x, ldx, gamma, beta, (void*)nullptr, 0, mean, rstd)
         LN_NC_SWITCH(d, LNS);
 #undef LNS
         LPI_CHECK_LAST();
         return 0;
     }
-    if (!x || !gamma || !beta || !y || !mean || !rstd || rows <= 0 || bad_row_dim(d) || (ldx & 3) || (ldy & 3)) return LPI_EINVAL;
+    if (!ln_fwd_args_ok(dtype, x_dtype, rows, d, x, ldx, gamma, beta, y, ldy, mean, rstd)) return LPI_EINVAL;
     dim3 g(rows_grid(rows)), b(256);
 #define LNF(TX, TY, NC) LPI_LAUNCH((ln_fwd_kernel<TX, TY, NC>), g, b, 0, S(stream), rows, d, (const TX*)x, ldx, gamma, beta, (TY*)y, ldy, mean, rstd)
 #define LNF_FF(NC) LNF(float, float, NC)
@@ -959,8 +978,7 @@ extern "C" int lpi_layernorm_fwd(int dtype, int x_dtype, int rows, int d, const 
 static int ln_bwd_impl(int dy_dtype, int cast_dtype, int x_dtype, int rows, int d, const void* dy, int lddy, const void* x, int ldx,
                        const float* gamma, const float* mean, const float* rstd, float* dx, int lddx, void* dx_cast,
                        int ldcast, int accumulate, int mapP, int mapL, int map0, const int* map_rs, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || (!dx && !dx_cast) || rows <= 0 || bad_row_dim(d) || (lddy & 3) || (ldx & 3) || (lddx & 3) || (ldcast & 3))
-        return LPI_EINVAL;
+    if (!ln_bwd_args_ok(dy_dtype, cast_dtype, x_dtype, rows, d, dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, dx_cast, ldcast)) return LPI_EINVAL;
     dim3 g(rows_grid(rows)), b(256);
 #define LNB(TX, TDY, TC, NC) LPI_LAUNCH((ln_bwd_kernel<TX, TDY, TC, NC>), g, b, 0, S(stream), rows, d, (const TDY*)dy, lddy, (const TX*)x, ldx, gamma, mean, rstd, dx, lddx, (TC*)dx_cast, ldcast, accumulate, mapP, mapL, map0, map_rs)
 #define LNB_HBB(NC) LNB(f16_t, bf16_t, bf16_t, NC)
@@ -1040,8 +1058,7 @@ extern "C" int lpi_layernorm_fwd_pair(int dtype, int x_dtype, const lpi_ln_fwd_d
     if (!d) return LPI_EINVAL;
     if (!d[0].y && !d[1].y) {      // statistics only, both problems (y = NULL): see lpi_layernorm_fwd
         for (int i = 0; i < 2; ++i)
-            if (!d[i].x || !d[i].mean || !d[i].rstd || d[i].rows <= 0 || bad_row_dim(d[i].d) || x_dtype != LPI_F16 || !ln_h16_ok(d[i].d, d[i].ldx, 0, d[i].x, nullptr))
-                return LPI_EINVAL;
+            if (!ln_fwd_args_ok(dtype, x_dtype, d[i].rows, d[i].d, d[i].x, d[i].ldx, d[i].gamma, d[i].beta, nullptr, 0, d[i].mean, d[i].rstd)) return LPI_EINVAL;
         const int o = nc_of(d[0].d) >= nc_of(d[1].d) ? 0 : 1;
         LnFwdP p[2];
         for (int i = 0; i < 2; ++i) {
@@ -1055,7 +1072,8 @@ extern "C" int lpi_layernorm_fwd_pair(int dtype, int x_dtype, const lpi_ln_fwd_d
         return 0;
     }
     for (int i = 0; i < 2; ++i)
-        if (!d[i].x || !d[i].gamma || !d[i].beta || !d[i].y || !d[i].mean || !d[i].rstd || d[i].rows <= 0 || bad_row_dim(d[i].d)) return LPI_EINVAL;
+        if (!d[i].y || !ln_fwd_args_ok(dtype, x_dtype, d[i].rows, d[i].d, d[i].x, d[i].ldx, d[i].gamma, d[i].beta, d[i].y, d[i].ldy, d[i].mean, d[i].rstd))
+            return LPI_EINVAL;      // both problems are checked before the first launch (a pair off the fused path is two launches)
     const bool fast = x_dtype == LPI_F16 && (dtype == LPI_BF16 || dtype == LPI_F16) && ln_h16_ok(d[0].d, d[0].ldx, d[0].ldy, d[0].x, d[0].y) &&
                       ln_h16_ok(d[1].d, d[1].ldx, d[1].ldy, d[1].x, d[1].y);
     if (fast) {
@@ -1095,8 +1113,9 @@ static int ln_bwd_pair_launch(const LnBwdP& a, const LnBwdP& b, hipStream_t s) {
 extern "C" int lpi_layernorm_bwd_pair(int dy_dtype, int cast_dtype, int x_dtype, const lpi_ln_bwd_desc* d, void* stream) {
     if (!d) return LPI_EINVAL;
     for (int i = 0; i < 2; ++i)
-        if (!d[i].dy || !d[i].x || !d[i].gamma || !d[i].mean || !d[i].rstd || (!d[i].dx && !d[i].dx_cast) || d[i].rows <= 0 || bad_row_dim(d[i].d))
-            return LPI_EINVAL;
+        if (!ln_bwd_args_ok(dy_dtype, cast_dtype, x_dtype, d[i].rows, d[i].d, d[i].dy, d[i].lddy, d[i].x, d[i].ldx, d[i].gamma, d[i].mean, d[i].rstd, d[i].dx,
+                            d[i].lddx, d[i].dx_cast, d[i].ldcast))
+            return LPI_EINVAL;      // both problems are checked before the first launch
     bool fast = x_dtype == LPI_F16 && dy_dtype == LPI_BF16 && cast_dtype == LPI_BF16;
     for (int i = 0; i < 2 && fast; ++i)
         fast = !d[i].dx && d[i].dx_cast && ln_h16_ok(d[i].d, d[i].lddy, d[i].ldx, d[i].dy, d[i].x) && !(d[i].ldcast & 7) && !(((uintptr_t)d[i].dx_cast) & 15);
@@ -1123,7 +1142,8 @@ extern "C" int lpi_patchify(int dtype, int B, int R, int ps, const float* image,
     const int esz = dtype == LPI_F32 ? 4 : 2;
     const int bk = 128 / esz;
     const int Kp = (K + bk - 1) / bk * bk;
-    if (ldcols < Kp || (ldcols & 3)) return LPI_EINVAL;
+    if (dtype != LPI_F32 && dtype != LPI_BF16 && dtype != LPI_F16) return LPI_EINVAL;
+    if (!row4_ok(cols, ldcols, Kp, dtype)) return LPI_EINVAL;
     const long total = (long)B * G * G * (Kp >> 2);
     dim3 g((unsigned)((total + 255) / 256)), b(256);
     const bool vec4 = (ps & 3) == 0 && (R & 3) == 0 && ((uintptr_t)image & 15) == 0;
@@ -1144,7 +1164,8 @@ extern "C" int lpi_patchify_u8(int dtype, int B, int R, int ps, const uint8_t* i
     const int esz = dtype == LPI_F32 ? 4 : 2;
     const int bk = 128 / esz;
     const int Kp = (K + bk - 1) / bk * bk;
-    if (ldcols < Kp || (ldcols & 3)) return LPI_EINVAL;
+    if (dtype != LPI_F32 && dtype != LPI_BF16 && dtype != LPI_F16) return LPI_EINVAL;
+    if (!row4_ok(cols, ldcols, Kp, dtype)) return LPI_EINVAL;
     const long total = (long)B * G * G * (Kp >> 2);
     dim3 g((unsigned)((total + 255) / 256)), b(256);
     if (dtype == LPI_F32) LPI_LAUNCH(patchify_u8_kernel<float>, g, b, 0, S(stream), B, R, ps, G, Kp, image, lut, (float*)cols, ldcols);
@@ -1161,7 +1182,9 @@ extern "C" int lpi_vis_assemble_fwd(int x_dtype, int B, int G2, int P, int d, co
     if ((out_mean != nullptr) != (out_rstd != nullptr)) return LPI_EINVAL;
     if (!patch_emb || !cls || !pos || !gamma || !beta || !x0 || !mean || !rstd || B <= 0 || G2 <= 0 || P < 0 || bad_row_dim(d) || (ldpe & 3))
         return LPI_EINVAL;
-    if (P > 0 && (!prompt0 || (prompt_bstride & 3))) return LPI_EINVAL;
+    if (P > 0 && (!prompt0 || (prompt_bstride & 3) || !al16(prompt0))) return LPI_EINVAL;
+    if (x_dtype != LPI_F32 && x_dtype != LPI_F16) return LPI_EINVAL;
+    if (!row4_ok(patch_emb, ldpe, d, LPI_F32) || !al16(cls) || !al16(pos) || !al16(gamma) || !al16(beta) || !row4_ok(x0, d, d, x_dtype)) return LPI_EINVAL;
     const long rows = (long)B * (1 + P + G2);
     if (x_dtype == LPI_F32)
         LPI_LAUNCH(vis_assemble_fwd_kernel<float>, dim3(rows_grid(rows)), dim3(256), 0, S(stream), B, G2, P, d, patch_emb, ldpe, cls, pos,
@@ -1208,6 +1231,7 @@ extern "C" int lpi_rows_sum_over_batch(int dtype, int B, int L, int row0, int P,
 extern "C" int lpi_vis_assemble_bwd(int dtype, int B, int G2, int P, int d, void* dx0, const float* prompt0, long prompt_bstride,
                                     const float* gamma, const float* mean, const float* rstd, float* dprompt, void* stream) {
     if (!dx0 || !prompt0 || !gamma || !mean || !rstd || !dprompt || B <= 0 || P <= 0 || bad_row_dim(d) || (prompt_bstride & 3)) return LPI_EINVAL;
+    if ((dtype != LPI_F32 && dtype != LPI_BF16) || !row4_ok(dx0, d, d, dtype) || !al16(prompt0) || !al16(gamma) || !al16(dprompt)) return LPI_EINVAL;
     const int L = 1 + P + G2;
     dim3 g(rows_grid((long)B * P)), bl(256);
     if (dtype == LPI_F32) LPI_LAUNCH(vis_prompt_rows_bwd_kernel<float>, g, bl, 0, S(stream), B, L, P, d, (float*)dx0, prompt0, prompt_bstride, gamma, mean, rstd);
@@ -1251,6 +1275,7 @@ extern "C" int lpi_prompt_add_varlen(int x_dtype, int B, int L, const int32_t* r
                                      float* out_mean, float* out_rstd, void* stream) {
     if ((out_mean != nullptr) != (out_rstd != nullptr)) return LPI_EINVAL;
     if (!x || !prompt_l || B <= 0 || P <= 0 || P + 1 > L || bad_row_dim(d) || (prompt_bstride & 3)) return LPI_EINVAL;
+    if ((x_dtype != LPI_F32 && x_dtype != LPI_F16) || !row4_ok(x, d, d, x_dtype) || !al16(prompt_l)) return LPI_EINVAL;
     if (x_dtype == LPI_F32)
         LPI_LAUNCH(prompt_add_kernel<float>, dim3(rows_grid((long)B * P)), dim3(256), 0, S(stream), B, L, row_start, P, d, (float*)x, prompt_l, prompt_bstride, out_mean, out_rstd, t_rowstat_guard);
     else if (x_dtype == LPI_F16)
@@ -1268,6 +1293,7 @@ extern "C" int lpi_prompt_add(int x_dtype, int B, int L, int P, int d, void* x, 
 extern "C" int lpi_pool_ln_fwd(int dtype, int x_dtype, int B, int L, int d, const void* x, const int32_t* idx, const float* gamma, const float* beta,
                                void* y, int ldy, float* mean, float* rstd, void* stream) {
     if (!x || !gamma || !beta || !y || !mean || !rstd || B <= 0 || L < 0 || (L == 0 && !idx) || bad_row_dim(d) || (ldy & 3)) return LPI_EINVAL;      // L == 0: idx holds absolute rows
+    if (!row4_ok(x, d, d, x_dtype) || !row4_ok(y, ldy, d, dtype) || !al16(gamma) || !al16(beta)) return LPI_EINVAL;
     dim3 g(rows_grid(B)), b(256);
     if (dtype == LPI_F32 && x_dtype == LPI_F32)
         LPI_LAUNCH((pool_ln_fwd_kernel<float, float>), g, b, 0, S(stream), B, L, d, (const float*)x, idx, gamma, beta, (float*)y, ldy, mean, rstd);
@@ -1287,6 +1313,7 @@ extern "C" int lpi_pool_ln_fwd(int dtype, int x_dtype, int B, int L, int d, cons
 extern "C" int lpi_pool_ln_bwd(int cast_dtype, int B, int L, int d, const float* dy, int lddy, const float* x, const int32_t* idx,
                                const float* gamma, const float* mean, const float* rstd, float* dx, void* dx_cast, void* stream) {
     if (!dy || !x || !gamma || !mean || !rstd || !dx || B <= 0 || bad_row_dim(d) || (lddy & 3)) return LPI_EINVAL;
+    if (!row4_ok(dy, lddy, d, LPI_F32) || !al16(x) || !al16(gamma) || !al16(dx) || (dx_cast && !row4_ok(dx_cast, d, d, cast_dtype))) return LPI_EINVAL;
     dim3 g(rows_grid(B)), b(256);
     if (cast_dtype == LPI_F32) LPI_LAUNCH(pool_ln_bwd_kernel<float>, g, b, 0, S(stream), B, L, d, dy, lddy, x, idx, gamma, mean, rstd, dx, (float*)dx_cast);
     else if (cast_dtype == LPI_BF16) LPI_LAUNCH(pool_ln_bwd_kernel<bf16_t>, g, b, 0, S(stream), B, L, d, dy, lddy, x, idx, gamma, mean, rstd, dx, (bf16_t*)dx_cast);
@@ -1316,7 +1343,7 @@ extern "C" int lpi_scatter_rows(int cast_dtype, int B, int L, int d, const float
 }
 
 extern "C" int lpi_l2norm_fwd(int B, int E, const float* x, int ldx, float* y, int ldy, float* inv_norm, void* stream) {
-    if (!x || !y || !inv_norm || B <= 0 || bad_row_dim(E) || (ldx & 3) || (ldy & 3)) return LPI_EINVAL;
+    if (!x || !y || !inv_norm || B <= 0 || bad_row_dim(E) || !row4_ok(x, ldx, E, LPI_F32) || !row4_ok(y, ldy, E, LPI_F32)) return LPI_EINVAL;
     LPI_LAUNCH(l2norm_fwd_kernel, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, E, x, ldx, y, ldy, inv_norm);
     LPI_CHECK_LAST();
     return 0;
@@ -1324,7 +1351,8 @@ extern "C" int lpi_l2norm_fwd(int B, int E, const float* x, int ldx, float* y, i
 
 extern "C" int lpi_l2norm_bwd(int B, int E, const float* y, int ldy, const float* dy, int lddy, const float* inv_norm, float* dx, int lddx,
                               void* stream) {
-    if (!y || !dy || !inv_norm || !dx || B <= 0 || bad_row_dim(E) || (ldy & 3) || (lddy & 3) || (lddx & 3)) return LPI_EINVAL;
+    if (!y || !dy || !inv_norm || !dx || B <= 0 || bad_row_dim(E) || !row4_ok(y, ldy, E, LPI_F32) || !row4_ok(dy, lddy, E, LPI_F32) || !row4_ok(dx, lddx, E, LPI_F32))
+        return LPI_EINVAL;
     LPI_LAUNCH(l2norm_bwd_kernel, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, E, y, ldy, dy, lddy, inv_norm, dx, lddx);
     LPI_CHECK_LAST();
     return 0;
@@ -1370,30 +1398,32 @@ extern "C" int lpi_ln_stats_finalize(int rows, int d, const float* part, int ld,
 
 // ---- lpi_row_jobs (see row_jobs_kernel): validation per op = the single-op entry point's
 static int row_job_blocks(const lpi_row_job& q) {
-    auto al16 = [](const void* p) { return !((uintptr_t)p & 15); };
     if (q.B <= 0) return -1;
     switch (q.op) {
     case LPI_ROWOP_POOL_LN_FWD:
         if (!q.a || !q.gamma || !q.beta || !q.out || !q.mean || !q.rstd || q.L < 0 || (q.L == 0 && !q.idx) || bad_row_dim(q.d) || (q.ld_c & 3)) return -1;
         if (!((q.dt_a == LPI_F32 && (q.dt_b == LPI_F32 || q.dt_b == LPI_BF16 || q.dt_b == LPI_F16)) || (q.dt_a == LPI_F16 && (q.dt_b == LPI_BF16 || q.dt_b == LPI_F16)))) return -1;
+        if (!row4_ok(q.a, q.d, q.d, q.dt_a) || !row4_ok(q.out, q.ld_c, q.d, q.dt_b) || !al16(q.gamma) || !al16(q.beta) || !al16(q.out2)) return -1;      // out2: f32 rows
         return rows_grid(q.B);
     case LPI_ROWOP_L2NORM_FWD:
-        if (!q.a || !q.out || !q.mean || bad_row_dim(q.d) || (q.ld_a & 3) || (q.ld_c & 3)) return -1;
+        if (!q.a || !q.out || !q.mean || bad_row_dim(q.d) || !row4_ok(q.a, q.ld_a, q.d, LPI_F32) || !row4_ok(q.out, q.ld_c, q.d, LPI_F32)) return -1;
         return rows_grid(q.B);
     case LPI_ROWOP_L2NORM_BWD:
         if (!q.a || !q.b || !q.mean_in || !q.out || bad_row_dim(q.d) || (q.ld_a & 3) || (q.ld_b & 3) || (q.ld_c & 3) || (q.out2 && q.dt_b != LPI_BF16)) return -1;
+        if (!row4_ok(q.a, q.ld_a, q.d, LPI_F32) || !row4_ok(q.b, q.ld_b, q.d, LPI_F32) || !row4_ok(q.out, q.ld_c, q.d, LPI_F32) || !row4_ok(q.out2, q.ld_c, q.d, LPI_BF16)) return -1;
         return rows_grid(q.B);
     case LPI_ROWOP_POOL_LN_BWD:
         if (!q.a || !q.b || !q.gamma || !q.mean_in || !q.rstd_in || !q.out || bad_row_dim(q.d) || (q.ld_a & 3) || (q.dt_b != LPI_BF16 && q.dt_b != LPI_F32)) return -1;
+        if (!row4_ok(q.a, q.ld_a, q.d, LPI_F32) || !al16(q.b) || !al16(q.gamma) || !al16(q.out) || !row4_ok(q.out2, q.d, q.d, q.dt_b)) return -1;
         return rows_grid(q.B);
     case LPI_ROWOP_LN_BWD:
         if (!q.a || !q.b || !q.gamma || !q.mean_in || !q.rstd_in || (!q.out && !q.out2) || bad_row_dim(q.d) || (q.ld_a & 3) || (q.ld_b & 3) || (q.ld_c & 3)) return -1;
         if (!((q.dt_a == LPI_BF16 && q.dt_b == LPI_BF16) || (q.dt_a == LPI_F32 && q.dt_b == LPI_F32))) return -1;
+        if (!ln_bwd_args_ok(q.dt_a, q.dt_b, LPI_F32, q.B, q.d, q.a, q.ld_a, q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, (const float*)q.out, q.ld_c, q.out2, q.ld_c)) return -1;
         return rows_grid(q.B);
     case LPI_ROWOP_SCATTER_ADD: {
         if (!q.a || !q.out || q.L < 0 || (q.L == 0 && !q.idx) || q.d <= 0 || (q.d & 3) || q.ld_a < q.d || q.ld_c < q.d || (q.dt_a != LPI_BF16 && q.dt_a != LPI_F32)) return -1;
-        const int esz = q.dt_a == LPI_F32 ? 4 : 2;
-        if ((q.ld_a * esz) % 8 || (q.ld_c * esz) % 8 || (((uintptr_t)q.a | (uintptr_t)q.out) & 7)) return -1;
+        if (!row4_ok(q.a, q.ld_a, q.d, q.dt_a) || !row4_ok(q.out, q.ld_c, q.d, q.dt_a)) return -1;
         return q.B;
     }
     case LPI_ROWOP_GATHER_BATCH_ROWS:
@@ -1401,13 +1431,15 @@ static int row_job_blocks(const lpi_row_job& q) {
         return (int)(((long)q.B * q.P * q.d + 255) / 256);
     case LPI_ROWOP_PROMPT_ADD:
         if (!q.out || !q.a || q.P <= 0 || q.P + 1 > q.L || bad_row_dim(q.d) || (q.bstride & 3) || ((q.mean != nullptr) != (q.rstd != nullptr)) || (q.dt_a != LPI_F16 && q.dt_a != LPI_F32)) return -1;
+        if (!row4_ok(q.out, q.d, q.d, q.dt_a) || !al16(q.a)) return -1;
         return rows_grid((long)q.B * q.P);
     case LPI_ROWOP_LN_BWD_ROWS_H16:
         if (!q.a || !q.b || !q.gamma || !q.mean_in || !q.rstd_in || !q.out2 || q.P <= 0 || q.row0 < 0 || q.row0 + q.P > q.L || bad_row_dim(q.d)) return -1;
-        if (!ln_h16_ok(q.d, q.ld_a, q.ld_b, q.a, q.b) || (q.ld_c & 7) || !al16(q.out2)) return -1;
+        if (!ln_h16_ok(q.d, q.ld_a, q.ld_b, q.a, q.b) || (q.ld_c & 7) || !al16(q.out2) || q.ld_a < q.d || q.ld_b < q.d || q.ld_c < q.d || !al16(q.gamma)) return -1;
         return (q.B * q.P + 7) / 8;
     case LPI_ROWOP_VIS_PROMPT_ROWS_BWD:
         if (!q.out || !q.a || !q.gamma || !q.mean_in || !q.rstd_in || q.P <= 0 || bad_row_dim(q.d) || (q.bstride & 3) || (q.dt_a != LPI_BF16 && q.dt_a != LPI_F32)) return -1;
+        if (!row4_ok(q.out, q.d, q.d, q.dt_a) || !al16(q.a) || !al16(q.gamma)) return -1;
         return rows_grid((long)q.B * q.P);
     }
     return -1;

@@ -9,9 +9,11 @@ or a 16-byte store that runs over a row's end from one that does not.  Here ever
     * every arena element OUTSIDE the view's footprint {col0 + r * ld + c} holds PAD, a NaN (set by bit pattern): read into a result it
       shows as NaN, written it shows in `check_pads`, which compares the arena's bits with those of before the call;
     * an INPUT (fill = a [rows, cols] tensor) holds its live values in the footprint;
-    * an OUTPUT (fill = None) holds UNWRITTEN there, a second NaN with other bits: `check_written` finds what the kernel left out.  Where a
+    * an OUTPUT (fill = None) holds UNWRITTEN there, a second NaN with other bits: `check_written` finds what the kernel left out (1-byte operands,
+      torch.uint8 = MX-FP8 element and scale bytes: PAD 0x7F, UNWRITTEN 0xFF; compared as bytes).  `in_out` turns a filled operand into an output.  Where a
       call MAY leave a part of its output untouched (the rows behind `rows_needed` of an attention backward, a scratch block whose contents
-      are unspecified), `must_write` narrows what `check_written` asks for: the rest of the footprint is neither a pad nor a must.
+      are unspecified), `must_write` narrows what `check_written` asks for: the rest of the footprint is neither a pad nor a must — unless the
+      call must leave it alone (the rows of a stream it does not own): `check_kept` holds it to its earlier bits.
 
 THE SAFETY RULE (arena sizing).  Within one test case EVERY arena has the same size in bytes, `arena_bytes(...)`, worked out from the
 LARGEST row count, the LARGEST leading dimension and the LARGEST element size of ANY operand of that case, plus the base offset col0:
@@ -27,9 +29,11 @@ import torch
 
 from poison import bits
 
-PAD = {torch.float32: 0x7FC00BAD, torch.bfloat16: 0x7FC5, torch.float16: 0x7E05}            # NaNs, told apart by their payloads
-UNWRITTEN = {torch.float32: 0x7FC0F00D, torch.bfloat16: 0x7FCA, torch.float16: 0x7E0A}
-_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16}
+# NaNs, told apart by their payloads.  torch.uint8 carries the MX-FP8 operands (e4m3 element bytes, E8M0 scale bytes): PAD 0x7F is e4m3's NaN, UNWRITTEN 0xFF is
+# the NaN of both formats, which neither an element code nor a scale byte of finite data can be — so `check_written` still tells "left out" from "written"
+PAD = {torch.float32: 0x7FC00BAD, torch.bfloat16: 0x7FC5, torch.float16: 0x7E05, torch.uint8: 0x7F}
+UNWRITTEN = {torch.float32: 0x7FC0F00D, torch.bfloat16: 0x7FCA, torch.float16: 0x7E0A, torch.uint8: 0xFF}
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.uint8: torch.uint8}
 SLACK = 64      # bytes behind the last row: a 16-byte access that starts inside the last row ends inside the arena
 
 
@@ -87,6 +91,13 @@ def operand(rows, cols, ld, dtype, col0, arena_elems, fill=None, device="cpu"):
     return Record(view, arena, inside, fill is None)
 
 
+def in_out(rec):
+    """An operand the call reads AND writes (a gradient stream it adds to): built with its live values as `fill`, then held as an output — its pads are
+    checked, its footprint may change, `must_write` / `check_kept` say which part of it."""
+    rec.output = True
+    return rec
+
+
 def must_write(rec, rows=None, none=False, index=None):
     """Narrow what `check_written` asks of the output `rec`.  Give one of:
         rows   an `operand` view: a count (the first rows) or a list of row indices;
@@ -125,3 +136,12 @@ def check_written(name, rec):
     left = (bits(rec.arena) == UNWRITTEN[rec.arena.dtype]) & rec.must
     n = int(left.sum())
     assert n == 0, f"{name}: {n} of {int(rec.must.sum())} output elements were never written (first at arena element {int(left.nonzero()[0]) if n else -1})"
+
+
+def check_kept(name, rec):
+    """The footprint elements of an output that are NOT must-be-written still have the bits they had before the call: for a call that owns some rows of a
+    larger matrix (the mapped rows of a stream) and must leave the others alone.  Not for outputs whose remaining part MAY be written (attn_arms)."""
+    assert rec.output, name
+    changed = (bits(rec.arena) != rec.before) & rec.inside & ~rec.must
+    n = int(changed.sum())
+    assert n == 0, f"{name}: {n} footprint elements the call does not own were written (first at arena element {int(changed.nonzero()[0]) if n else -1})"

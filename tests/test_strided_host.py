@@ -1,5 +1,5 @@
 """tests/strided.py can fail: a plain numpy "GEMM with explicit leading dimensions" with four deliberate addressing mistakes, each of which the
-helper's checks (or a NaN in the result) catch, and the correct call, which passes them.  No GPU."""
+helper's checks (or a NaN in the result) catch, and the correct call, which passes them; 1-byte operands (MX-FP8 bytes); rows a call must leave alone.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -84,3 +84,32 @@ def test_each_wrong_gemm_is_caught(bug, how):
     ops, ref = run(bug)
     msg = caught(ops, ref)
     assert msg is not None and how in msg, (bug, msg)
+
+
+def test_one_byte_operands_and_kept_rows():
+    """strided.py on torch.uint8 (the MX-FP8 element and scale bytes): PAD 0x7F, UNWRITTEN 0xFF, compared as bytes; in_out + check_kept on the rows a call does not own."""
+    n = S.arena_bytes(13, 168, 4, 4)
+    q = S.operand(13, 160, 168, torch.uint8, 4, n)
+    assert q.t.dtype == torch.uint8 and q.t.stride() == (168, 1) and q.t.data_ptr() == q.arena.data_ptr() + 4
+    assert bool((q.arena[q.inside] == 0xFF).all()) and bool((q.arena[~q.inside] == 0x7F).all())
+    with pytest.raises(AssertionError, match="never written"):
+        S.check_written("q", q)
+    q.t[:] = 0x38
+    q.t[3, 5] = 0x7F      # an element byte that equals PAD is a written value like any other
+    S.check_written("q", q), S.check_pads("q", q)
+    q.arena[4 + 160] = 0
+    with pytest.raises(AssertionError, match="outside the operand's footprint"):
+        S.check_pads("q", q)
+    sc = S.operand(13, 5, 8, torch.uint8, 3, n, torch.full((13, 5), 127, dtype=torch.uint8))
+    assert not sc.output and bool((sc.t == 127).all())
+    sc.t[0, 0] = 126
+    with pytest.raises(AssertionError, match="an input operand was written"):
+        S.check_pads("scales", sc)
+    vals = torch.arange(13 * 8, dtype=torch.float32).reshape(13, 8)
+    s = S.must_write(S.in_out(S.operand(13, 8, 12, torch.float32, 4, n // 4, vals)), rows=[2, 5])
+    s.t[2] += 1
+    s.t[5] += 1
+    S.check_pads("stream", s), S.check_written("stream", s), S.check_kept("stream", s)
+    s.t[6, 0] = -1.0
+    with pytest.raises(AssertionError, match="does not own"):
+        S.check_kept("stream", s)
