@@ -536,6 +536,25 @@ typedef struct lpi_rows_sum_desc {
 } lpi_rows_sum_desc;
 int lpi_rows_sum_over_batch_pair(int dtype, const lpi_rows_sum_desc* d /* [2] */, void* stream);
 
+/* Leading dimensions and argument checks of the loss / prompt / k-means / ranking / interaction family (loss.hip, interact.hip: the sections a8, a9, a10, a11, a1,
+ * "misc" ranking and f4 of this header; tests/test_loss_strides_gpu.py runs every entry point on offset, strided views with poisoned pads).  Every kernel of the
+ * family moves ONE f32 (or int32) per lane: no pointer or leading dimension has an alignment rule beyond the element's own 4 bytes, odd leading dimensions are
+ * legal.  All checks are made on the host BEFORE the first launch (since 619; up to 618 lpi_clip_loss_fwd_bwd looked at lddl after three launches): a refused call
+ * (LPI_EINVAL) has launched nothing and written nothing.
+ *   every leading dimension >= the width it strides: ld, lddl, ldg >= n (lddl only with dlogits, ldg only with g / gt); ldf, ldx >= E; the scores' ld >= n_cols;
+ *     ldv, ldov, ldgv, lddv >= Dv and ldt, ldot, ldgt, lddt >= Dt (ten independent values: no two need be equal);
+ *   every count > 0; r0 >= 0, nloc > 0, r0 + nloc <= n (with g / gt); label0 >= 0, label0 + rows <= n; row < T <= 32; 1 <= k <= n_cols (lpi_topk: ANY such k, a pass
+ *     over the row per pick; the callers use k <= 16); r <= 16 (prompt CP) and Lyr P r, D r, 2 Lyr P within int (the CP kernels index with int; since 619);
+ *     a one-thread-per-element grid (the CP forwards: Lyr P D, both widths summed for _fwd2; lpi_sgd_step: n; lpi_copy_rows: rows cols) within 2^31 - 1 workgroups of 256 (since 619);
+ *     R <= 8, Dv, Dt <= 1024, 0 <= layer < Lyr (interaction; since 619 lpi_interact_workspace_floats refuses exactly what lpi_interact_fwd refuses);
+ *     temp > 0; the alignment loss's LDS: 4 Lyr P + 2 Lyr^2 + 2 Lyr floats (lpi_align_loss_fwd_bwd; 2 Lyr P + ... for _fwd_bwd2) <= 64 KB;
+ *   required pointers non-NULL.  Optional (NULL = not wanted): dlogits, g / gt (both or neither), lpi_sum_scaled's b, dist, mindist, center, val, dvis / dtxt (both
+ *     or neither: since 619 lpi_align_loss_fwd_bwd refuses one without the other, as _fwd_bwd2 always did), dx_row (NULL, or row < 0: forward only — both spellings
+ *     are accepted, a row >= 0 with dx_row = NULL computes the loss alone);
+ *   lpi_ce_rows_fwd_bwd's dlogits may BE logits (the gradient overwrites the block, row by row by the wave that read it): then lddl must equal ld (since 619).
+ * What the host CANNOT check, because the arrays are device memory — the caller's contract: gt[i, t] < n_cols (or < 0 = padding), cand[c] in [0, n),
+ * labels[i] in [0, k) for lpi_kmeans_update (lpi_kmeans_assign accepts any stored value: it only compares), target entries 0 / 1 with at least one of each per row
+ * (else the loss is NaN, as the reference's is); scratch / workspace sizes as stated at each call; dxv / dxt, g / gt, the output rows must not overlap their inputs. */
 /* ---- a8: symmetric contrastive loss   replaces: loss/loss.py:75-87 (ClipLoss.forward), slinet.py:139-141
  * logits f32 [n_rows, n_cols] (ld), rows r0..r0+n_local-1 are this rank's pairs; square global matrix
  * (n_rows == n_cols == W*B).  loss[0] = (CE(logits,arange)+CE(logits^T,arange))/2 over ALL rows/cols;
@@ -554,7 +573,7 @@ int lpi_clip_loss_local(int n, const float* logits, int ld, float upstream, int 
                         float* g, float* gt, int ldg, void* stream);
 /* `local_loss=True` form of the same loss (sprompt.py:278-283 with loss/loss.py:62-73): row-wise cross-entropy of a [rows, n] block of
  * logits (this rank's images against ALL texts, or its texts against all images) whose row i has label label0 + i (= rank * B + i).
- * loss_rows[i] = logsumexp(logits[i, :]) - logits[i, label0 + i]; dlogits (optional, may alias nothing) = upstream * (softmax - onehot).
+ * loss_rows[i] = logsumexp(logits[i, :]) - logits[i, label0 + i]; dlogits (optional; may be `logits` itself with lddl == ld: in place) = upstream * (softmax - onehot).
  * lpi_sum_scaled: out[0] = scale * sum(a[i] + b[i]) (b may be NULL), fixed order — the mean of the two row-loss vectors. */
 int lpi_ce_rows_fwd_bwd(int rows, int n, const float* logits, int ld, int label0, float upstream, float* loss_rows, float* dlogits,
                         int lddl, void* stream);
@@ -615,6 +634,8 @@ int lpi_transpose2(int dtype, int rows0, int cols0, const void* src0, int lds0, 
  * (np.argsort(score)[::-1] places later indices first among ties.) */
 int lpi_retrieval_rank(int n_rows, int n_cols, const float* scores, int ld, const int32_t* gt, int gt_per_row,
                        int32_t* rank, void* stream);
+/* idx [n_rows, k] (val [n_rows, k], NULL = not wanted): the k best columns of every row in that order (value descending, later index first among equal values,
+ * -inf included); any 1 <= k <= n_cols. */
 int lpi_topk(int n_rows, int n_cols, int k, const float* scores, int ld, int32_t* idx, float* val, void* stream);
 
 /* ---- streamed search (search.hip, since 614): the two calls above without the score matrix.  s[i,j] = Q[i,:] . G[j,:] is computed tile by tile on the

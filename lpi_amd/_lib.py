@@ -173,7 +173,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 618
+EXPECTED_ABI = 619
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

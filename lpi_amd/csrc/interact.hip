@@ -285,7 +285,7 @@ inline int rows_per_wg(int N) { return (N + 255) / 256 < 1 ? 1 : (N + 255) / 256
 }  // namespace
 
 extern "C" int lpi_interact_workspace_floats(int N, int Dv, int Dt, int R) {
-    if (N <= 0 || Dv <= 0 || Dt <= 0 || R <= 0) return LPI_EINVAL;
+    if (N <= 0 || Dv <= 0 || Dt <= 0 || Dv > MAXC * TPB || Dt > MAXC * TPB || R <= 0 || R > MAXR) return LPI_EINVAL;      // what lpi_interact_fwd / _bwd take, no more
     const int rp = rows_per_wg(N), G = (N + rp - 1) / rp;
     return G * (part_len(Dv, Dt, R) + part_len(Dt, Dv, R));
 }

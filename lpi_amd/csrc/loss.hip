@@ -188,6 +188,14 @@ __global__ __launch_bounds__(256) void sgd_step_kernel(long n, float* __restrict
 
 // ---------------------------------------------------------------------------------------------- CP prompt
 constexpr int MAXR = 16;
+// one thread per element in 256-thread workgroups: the workgroup count must fit the grid's x dimension (2^31 - 1), not be cut by the cast to unsigned
+inline bool grid_too_large(long elems) { return (elems + 255) / 256 > 0x7fffffffL; }
+// the CP kernels index d1 / d2 / d3 / t / g3 with int arithmetic: rows * r and D * r must fit, and the forwards launch one thread per output element (D: the
+// width; lpi_prompt_cp_fwd2 checks the sum of both widths as well; Lyr P < 2^31 by the first term, so the product cannot overflow a long).  Host check of every
+// lpi_prompt_cp_* entry point.
+inline bool cp_too_large(int Lyr, int P, int D, int r) {
+    return (long)Lyr * P * r > 0x7fffffffL || (long)D * r > 0x7fffffffL || 2L * Lyr * P > 0x7fffffffL || grid_too_large((long)Lyr * P * D);
+}
 
 __global__ __launch_bounds__(256) void cp_fwd_kernel(int Lyr, int P, int D, int r, const float* __restrict__ d1, const float* __restrict__ d2,
                                                     const float* __restrict__ d3, float sc, float* __restrict__ out) {
@@ -293,8 +301,10 @@ __device__ __forceinline__ void cp_bwd_g12_body(int Lyr, int P, int r, const flo
         const int l = i / r, k = i % r;
         float s = 0.f;
         for (int p = 0; p < P; ++p) s += t[(l * P + p) * r + k] * d2[p * r + k];
-        s *= sc;
-        g1[i] = accumulate_g1 ? g1[i] + s : s;
+        // the accumulation is ONE fused multiply-add, spelled out: written as s *= sc; g1[i] + s the compiler contracted it where accumulate_g1 is a compile-time 1
+        // (cp_bwd_g2_kernel's second call) and not where it is a kernel argument, and the two-launch form differed from the per-stack launches in the last bit
+        // whenever sc is no power of two (r = 3).  cp_bwd_g2_kernel computes what it always did.
+        g1[i] = accumulate_g1 ? fmaf(s, sc, g1[i]) : s * sc;
     }
     for (int i = threadIdx.x; i < P * r; i += blockDim.x) {
         const int p = i / r, k = i % r;
@@ -353,10 +363,17 @@ __global__ __launch_bounds__(1024) void align_loss_kernel(int Lyr, int P, int Dv
             const int rr = isv ? row : row - nr;
             const int D = isv ? Dv : Dt;
             const float* src = (isv ? vis : txt) + (size_t)rr * D;
-            float s = 0.f;
-            for (int d = lane; d < D; d += 64) s += src[d];
-            s = wave_sum(s);
-            if (lane == 0) (isv ? v : t)[rr] = s / (float)D / temp;
+            // align_means_kernel's summation order (256 threads per row: thread 64 w + lane adds every 256th column, four wave sums, (p0 + p1) + (p2 + p3)) on one
+            // wave, so that the value does not depend on whether gradients were asked for and equals lpi_align_loss_fwd_bwd2's bit for bit (a plain 64-lane walk
+            // differed in the last bit at D > 64)
+            float p4[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                float s = 0.f;
+                for (int d = lane + 64 * w; d < D; d += 256) s += src[d];
+                p4[w] = wave_sum(s);
+            }
+            if (lane == 0) (isv ? v : t)[rr] = ((p4[0] + p4[1]) + (p4[2] + p4[3])) / (float)D / temp;
         }
     }
     __syncthreads();
@@ -688,7 +705,7 @@ __global__ __launch_bounds__(256) void retrieval_rank_kernel(int n_rows, int n_c
     if (lane == 0) rank[row] = best;
 }
 
-// top-k per row by k rounds of (value desc, index desc) arg-max; k is small (<= 16)
+// top-k per row by k rounds of (value desc, index desc) arg-max: any 1 <= k <= n_cols (a round costs one pass over the row; the callers ask for k <= 16)
 __global__ __launch_bounds__(256) void topk_kernel(int n_rows, int n_cols, int k, const float* __restrict__ s, int ld,
                                                   int32_t* __restrict__ idx, float* __restrict__ val) {
     const int lane = threadIdx.x & 63;
@@ -724,15 +741,13 @@ __global__ __launch_bounds__(256) void topk_kernel(int n_rows, int n_cols, int k
 
 extern "C" int lpi_clip_loss_fwd_bwd(int n, const float* logits, int ld, float upstream, float* loss, float* dlogits, int lddl,
                                      float* row_lse, float* col_lse, void* stream) {
-    if (!logits || !loss || !row_lse || !col_lse || n <= 0 || ld < n) return LPI_EINVAL;
+    if (!logits || !loss || !row_lse || !col_lse || n <= 0 || ld < n || (dlogits && lddl < n)) return LPI_EINVAL;      // every check before the first launch
     LPI_LAUNCH(row_lse_kernel, dim3((n + 3) / 4), dim3(256), 0, S(stream), n, logits, ld, row_lse);
     LPI_LAUNCH(col_lse_kernel, dim3((n + 63) / 64), dim3(1024), 0, S(stream), n, logits, ld, col_lse);
     LPI_LAUNCH(clip_loss_reduce_kernel, dim3(1), dim3(256), 0, S(stream), n, logits, ld, row_lse, col_lse, loss);
-    if (dlogits) {
-        if (lddl < n) return LPI_EINVAL;
+    if (dlogits)
         LPI_LAUNCH(clip_loss_grad_kernel, dim3((n + 255) / 256, n), dim3(256), 0, S(stream), n, logits, ld, row_lse, col_lse, upstream,
                            dlogits, lddl);
-    }
     LPI_CHECK_LAST();
     return 0;
 }
@@ -803,7 +818,9 @@ __global__ __launch_bounds__(256) void sum_scaled_kernel(int n, const float* __r
 
 extern "C" int lpi_ce_rows_fwd_bwd(int rows, int n, const float* logits, int ld, int label0, float upstream, float* loss_rows, float* dlogits,
                                    int lddl, void* stream) {
-    if (!logits || !loss_rows || rows <= 0 || n <= 0 || ld < n || label0 < 0 || label0 + rows > n || (dlogits && lddl < n)) return LPI_EINVAL;
+    if (!logits || !loss_rows || rows <= 0 || n <= 0 || ld < n || label0 < 0 || label0 + rows > n || (dlogits && lddl < n) ||
+        (dlogits == logits && lddl != ld))      // in place: the gradient rows ARE the logit rows
+        return LPI_EINVAL;
     LPI_LAUNCH(ce_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, S(stream), rows, n, logits, ld, label0, upstream, loss_rows, dlogits, lddl);
     LPI_CHECK_LAST();
     return 0;
@@ -816,7 +833,7 @@ extern "C" int lpi_sum_scaled(int n, const float* a, const float* b, float scale
 }
 
 extern "C" int lpi_copy_rows(int rows, int cols, const float* src, long lds, float* dst, long ldd, void* stream) {
-    if (!src || !dst || rows <= 0 || cols <= 0 || lds < cols || ldd < cols) return LPI_EINVAL;
+    if (!src || !dst || rows <= 0 || cols <= 0 || lds < cols || ldd < cols || grid_too_large((long)rows * cols)) return LPI_EINVAL;
     const long n = (long)rows * cols;
     LPI_LAUNCH(copy_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), rows, cols, src, lds, dst, ldd);
     LPI_CHECK_LAST();
@@ -833,7 +850,7 @@ extern "C" int lpi_l1_task_id(int n, int E, int T, int C, const float* feat, int
 
 extern "C" int lpi_sgd_step(long n, float* param, const float* grad, float* momentum_buf, float lr, float momentum, float weight_decay,
                             int first, void* stream) {
-    if (!param || !grad || !momentum_buf || n <= 0) return LPI_EINVAL;
+    if (!param || !grad || !momentum_buf || n <= 0 || grid_too_large(n)) return LPI_EINVAL;
     LPI_LAUNCH(sgd_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), n, param, grad, momentum_buf, lr, momentum, weight_decay, first);
     LPI_CHECK_LAST();
     return 0;
@@ -841,7 +858,7 @@ extern "C" int lpi_sgd_step(long n, float* param, const float* grad, float* mome
 
 extern "C" int lpi_prompt_cp_fwd(int Lyr, int P, int D, int r, const float* d1, const float* d2, const float* d3, float scale, float* out,
                                  void* stream) {
-    if (!d1 || !d2 || !d3 || !out || Lyr <= 0 || P <= 0 || D <= 0 || r <= 0 || r > MAXR) return LPI_EINVAL;
+    if (!d1 || !d2 || !d3 || !out || Lyr <= 0 || P <= 0 || D <= 0 || r <= 0 || r > MAXR || cp_too_large(Lyr, P, D, r)) return LPI_EINVAL;
     const long n = (long)Lyr * P * D;
     LPI_LAUNCH(cp_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), Lyr, P, D, r, d1, d2, d3, scale / (float)r, out);
     LPI_CHECK_LAST();
@@ -850,8 +867,10 @@ extern "C" int lpi_prompt_cp_fwd(int Lyr, int P, int D, int r, const float* d1, 
 
 extern "C" int lpi_prompt_cp_fwd2(int Lyr, int P, int Dv, int Dt, int r, const float* d1, const float* d2v, const float* d2t, const float* d3v,
                                   const float* d3t, float scale, float* outv, float* outt, void* stream) {
-    if (!d1 || !d2v || !d2t || !d3v || !d3t || !outv || !outt || Lyr <= 0 || P <= 0 || Dv <= 0 || Dt <= 0 || r <= 0 || r > MAXR) return LPI_EINVAL;
-    const long n = (long)Lyr * P * (Dv + Dt);
+    if (!d1 || !d2v || !d2t || !d3v || !d3t || !outv || !outt || Lyr <= 0 || P <= 0 || Dv <= 0 || Dt <= 0 || r <= 0 || r > MAXR || cp_too_large(Lyr, P, Dv, r) ||
+        cp_too_large(Lyr, P, Dt, r) || grid_too_large((long)Lyr * P * ((long)Dv + Dt)))
+        return LPI_EINVAL;
+    const long n = (long)Lyr * P * ((long)Dv + Dt);
     LPI_LAUNCH(cp_fwd2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), Lyr, P, Dv, Dt, r, d1, d2v, d2t, d3v, d3t, scale / (float)r, outv, outt);
     LPI_CHECK_LAST();
     return 0;
@@ -863,7 +882,7 @@ extern "C" int lpi_prompt_cp_bwd2(int Lyr, int P, int Dv, int Dt, int r, const f
                                   const float* d3t, float scale, const float* doutv, const float* doutt, float* g1, float* g2v, float* g2t, float* g3v,
                                   float* g3t, float* scratch, void* stream) {
     if (!d1 || !d2v || !d2t || !d3v || !d3t || !doutv || !doutt || !g1 || !g2v || !g2t || !g3v || !g3t || !scratch || Lyr <= 0 || P <= 0 || Dv <= 0 ||
-        Dt <= 0 || r <= 0 || r > MAXR)
+        Dt <= 0 || r <= 0 || r > MAXR || cp_too_large(Lyr, P, Dv, r) || cp_too_large(Lyr, P, Dt, r))
         return LPI_EINVAL;
     const float sc = scale / (float)r;
     const int rows = Lyr * P;
@@ -878,7 +897,7 @@ extern "C" int lpi_prompt_cp_bwd2(int Lyr, int P, int Dv, int Dt, int r, const f
 
 extern "C" int lpi_prompt_cp_bwd(int Lyr, int P, int D, int r, const float* d1, const float* d2, const float* d3, float scale,
                                  const float* dout, float* g1, float* g2, float* g3, int accumulate_g1, float* scratch, void* stream) {
-    if (!d1 || !d2 || !d3 || !dout || !g1 || !g2 || !g3 || !scratch || Lyr <= 0 || P <= 0 || D <= 0 || r <= 0 || r > MAXR) return LPI_EINVAL;
+    if (!d1 || !d2 || !d3 || !dout || !g1 || !g2 || !g3 || !scratch || Lyr <= 0 || P <= 0 || D <= 0 || r <= 0 || r > MAXR || cp_too_large(Lyr, P, D, r)) return LPI_EINVAL;
     const float sc = scale / (float)r;
     const int rows = Lyr * P;
     LPI_LAUNCH(cp_bwd_t_kernel, dim3((rows + 3) / 4), dim3(256), 0, S(stream), rows, D, r, d3, dout, scratch);
@@ -890,7 +909,7 @@ extern "C" int lpi_prompt_cp_bwd(int Lyr, int P, int D, int r, const float* d1, 
 
 extern "C" int lpi_align_loss_fwd_bwd(int Lyr, int P, int Dv, int Dt, const float* vis, const float* txt, float temp, float weight,
                                       float* loss, float* dvis, float* dtxt, void* stream) {
-    if (!vis || !txt || !loss || Lyr <= 0 || P <= 0 || Dv <= 0 || Dt <= 0 || temp <= 0.f) return LPI_EINVAL;
+    if (!vis || !txt || !loss || Lyr <= 0 || P <= 0 || Dv <= 0 || Dt <= 0 || temp <= 0.f || ((dvis != nullptr) != (dtxt != nullptr))) return LPI_EINVAL;
     const size_t lds = ((size_t)4 * Lyr * P + 2 * Lyr * Lyr + 2 * Lyr) * sizeof(float);
     if (lds > 64 * 1024) return LPI_EINVAL;
     const int grads = dvis && dtxt;      // with gradient buffers the row means and the final broadcast run grid-wide around the one-workgroup core

@@ -1,6 +1,6 @@
 """The two-arm assertions of the strided-view tests (a plain helper module next to strided.py: no fixtures, no pytest settings; works on the CPU and on the GPU).
-tests/test_attn_strides_gpu.py (through attn_arms) and tests/test_rowop_strides_gpu.py run HIP kernels through it; tests/test_attn_strides_host.py and
-tests/test_rowop_strides_host.py prove on CPU tensors that it catches what it is meant to catch.
+tests/test_attn_strides_gpu.py (through attn_arms), tests/test_rowop_strides_gpu.py and tests/test_loss_strides_gpu.py run HIP kernels through it;
+tests/test_attn_strides_host.py, tests/test_rowop_strides_host.py and tests/test_loss_strides_host.py prove on CPU tensors that it catches what it is meant to catch.
 
 A case builds its operands twice as {name: strided.Record} and runs the same calls on both.  Usually the arms are the STRIDED one (offset base pointers, every
 leading dimension different from the widths and from each other, NaN in every pad) and the TIGHT one (contiguous copies of the same values); `names` renames them

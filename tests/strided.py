@@ -10,7 +10,7 @@ or a 16-byte store that runs over a row's end from one that does not.  Here ever
       shows as NaN, written it shows in `check_pads`, which compares the arena's bits with those of before the call;
     * an INPUT (fill = a [rows, cols] tensor) holds its live values in the footprint;
     * an OUTPUT (fill = None) holds UNWRITTEN there, a second NaN with other bits: `check_written` finds what the kernel left out (1-byte operands,
-      torch.uint8 = MX-FP8 element and scale bytes: PAD 0x7F, UNWRITTEN 0xFF; compared as bytes).  `in_out` turns a filled operand into an output.  Where a
+      torch.uint8 = MX-FP8 element and scale bytes: PAD 0x7F, UNWRITTEN 0xFF; compared as bytes; torch.int32 = labels / ranks / indices: two negative sentinels).  `in_out` turns a filled operand into an output.  Where a
       call MAY leave a part of its output untouched (the rows behind `rows_needed` of an attention backward, a scratch block whose contents
       are unspecified), `must_write` narrows what `check_written` asks for: the rest of the footprint is neither a pad nor a must — unless the
       call must leave it alone (the rows of a stream it does not own): `check_kept` holds it to its earlier bits.
@@ -31,9 +31,11 @@ from poison import bits
 
 # NaNs, told apart by their payloads.  torch.uint8 carries the MX-FP8 operands (e4m3 element bytes, E8M0 scale bytes): PAD 0x7F is e4m3's NaN, UNWRITTEN 0xFF is
 # the NaN of both formats, which neither an element code nor a scale byte of finite data can be — so `check_written` still tells "left out" from "written"
-PAD = {torch.float32: 0x7FC00BAD, torch.bfloat16: 0x7FC5, torch.float16: 0x7E05, torch.uint8: 0x7F}
-UNWRITTEN = {torch.float32: 0x7FC0F00D, torch.bfloat16: 0x7FCA, torch.float16: 0x7E0A, torch.uint8: 0xFF}
-_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.uint8: torch.uint8}
+# torch.int32 carries labels, ranks, indices, counts and flags (the loss / k-means / ranking family): PAD and UNWRITTEN are two large NEGATIVE integers, which no label,
+# rank (0 .. n_cols, or 0x7fffffff for "no ground truth"), index or the -1 that pads a ground-truth list can equal; compared as integers
+PAD = {torch.float32: 0x7FC00BAD, torch.bfloat16: 0x7FC5, torch.float16: 0x7E05, torch.uint8: 0x7F, torch.int32: -0x5AD5AD00}
+UNWRITTEN = {torch.float32: 0x7FC0F00D, torch.bfloat16: 0x7FCA, torch.float16: 0x7E0A, torch.uint8: 0xFF, torch.int32: -0x0F00D000}
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.uint8: torch.uint8, torch.int32: torch.int32}
 SLACK = 64      # bytes behind the last row: a 16-byte access that starts inside the last row ends inside the arena
 
 
@@ -54,7 +56,7 @@ class Record:
 
 def _arena(arena_elems, dtype, device):
     assert dtype in _INT, dtype
-    return torch.full((arena_elems,), PAD[dtype], dtype=_INT[dtype], device=device).view(dtype)      # every pattern here is below 0x8000 / 2^31
+    return torch.full((arena_elems,), PAD[dtype], dtype=_INT[dtype], device=device).view(dtype)      # every pattern here fits its integer type
 
 
 def region(index, dtype, arena_elems, fill=None, device="cpu"):

@@ -113,3 +113,32 @@ def test_one_byte_operands_and_kept_rows():
     s.t[6, 0] = -1.0
     with pytest.raises(AssertionError, match="does not own"):
         S.check_kept("stream", s)
+
+
+def test_int32_operands_carry_sentinels_no_label_rank_or_index_can_equal():
+    """strided.py on torch.int32 (labels, ranks, top-k indices, the `changed` flag): PAD and UNWRITTEN are negative, differ from each other, from -1 (the padding of a
+    ground-truth list) and from 0x7fffffff (the rank of a row without ground truth); a written 0 counts as written; pads and inputs are compared as integers."""
+    pad, unw = S.PAD[torch.int32], S.UNWRITTEN[torch.int32]
+    assert pad < -1 and unw < -1 and pad != unw and -2 ** 31 <= min(pad, unw) and 0x7fffffff not in (pad, unw)
+    n = S.arena_bytes(7, 8, 4, 3) // 4
+    lab = S.operand(7, 1, 1, torch.int32, 3, n)
+    assert lab.t.dtype == torch.int32 and lab.t.data_ptr() == lab.arena.data_ptr() + 12
+    assert bool((lab.arena[lab.inside] == unw).all()) and bool((lab.arena[~lab.inside] == pad).all())
+    with pytest.raises(AssertionError, match="never written"):
+        S.check_written("labels", lab)
+    lab.t[:, 0] = torch.tensor([0, 1, 0, 4, 0x7fffffff, -1, 2], dtype=torch.int32)
+    S.check_written("labels", lab), S.check_pads("labels", lab)
+    lab.arena[3 + 7] = 0      # one label too many
+    with pytest.raises(AssertionError, match="outside the operand's footprint"):
+        S.check_pads("labels", lab)
+    gt = S.operand(7, 2, 5, torch.int32, 1, n, torch.tensor([[3, -1]] * 7, dtype=torch.int32))
+    assert not gt.output and bool((gt.t[:, 1] == -1).all()) and gt.arena[1 + 2] == pad
+    gt.t[2, 1] = 4
+    with pytest.raises(AssertionError, match="an input operand was written"):
+        S.check_pads("gt", gt)
+    flag = S.in_out(S.region(torch.tensor([3]), torch.int32, n, torch.tensor([0], dtype=torch.int32)))
+    S.check_written("changed", flag), S.check_pads("changed", flag), S.check_kept("changed", flag)      # a flag left at 0 is a value, not "unwritten"
+    S.must_write(flag, none=True)
+    flag.arena[3] = 1
+    with pytest.raises(AssertionError, match="does not own"):
+        S.check_kept("changed", flag)
