@@ -688,6 +688,27 @@ int lpi_search_topk_mx8(int nq, int ng, int E, const void* Q, int ldq, const voi
                         int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
 int lpi_search_rank_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg, const void* g_scales,
                         int ldgs, const int32_t* gt, int gt_per_row, int32_t* rank, void* ws, long ws_bytes, void* stream);
+/* Wide lists (search_wide.hip, since 620): lpi_search_topk / _t / _mx8 with 1 <= k <= LPI_SEARCH_KWIDE = 256, in ONE sweep of the gallery.  Argument
+ * lists, envelope per operand type (E and its multiple, leading dimensions, alignment, col_base, accumulate and its held list, k <= ng unless
+ * accumulate, finite values), order (value descending, then index descending; a short list ends with idx = -1, val = -inf) and refusals (LPI_EINVAL
+ * before any launch; lpi_search_topk_wide_t forwards dt = LPI_F32 and refuses LPI_MX8, LPI_F32X3 and anything else) are the narrow calls'.  The sweep
+ * is the narrow calls' tile code with another epilogue: every score has the narrow calls' bits, so for k <= 16 the lists are the narrow calls' bit for
+ * bit, a chunked search equals one call bit for bit, and duplicate rows tie exactly and fall by index.  Two launches per call, whatever k, nq and ng:
+ * the sweep, which appends the scores that beat a per-row threshold (the row's k-th best so far) to a candidate buffer and brings a buffer down to its
+ * k best when the next tile could overflow it, and the merge of the gallery splits' lists (with the held list when accumulating) into idx / val.
+ * ws: lpi_search_wide_workspace(nq, ng, k) bytes, a host function (LPI_EINVAL outside nq, ng > 0, 1 <= k <= 256) that never shrinks when an argument
+ * grows and is constant in ng from 65 536 on: per (gallery split, query row) one candidate buffer of 256 (k <= 128) or 512 (value, index) pairs, the
+ * values of all buffers first, then the indices; its contents need not survive between calls.  (2048, 1 048 576, 256): 264 MiB, the score matrix
+ * 8 GiB.  The narrow calls and lpi_search_workspace keep their range, k <= 16. */
+#define LPI_SEARCH_KWIDE 256
+long lpi_search_wide_workspace(int nq, int ng, int k);
+int lpi_search_topk_wide(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, int k, int col_base, int accumulate,
+                         int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
+int lpi_search_topk_wide_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, int k, int col_base, int accumulate,
+                           int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
+int lpi_search_topk_wide_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
+                             const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes,
+                             void* stream);
 
 /* ---- a6 (host side): CLIP byte-level BPE      replaces: models/clip/simple_tokenizer.py:62-132, clip.py:185-221 ------
  * HOST functions (no GPU work, no stream).  create: `merges_utf8` is the decompressed text of bpe_simple_vocab_16e6.txt(.gz) —

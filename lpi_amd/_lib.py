@@ -144,6 +144,11 @@ SIGNATURES = {
     # MX-FP8 operands: e4m3 bytes + E8M0 scales per operand (search_mx8.hip)
     "lpi_search_topk_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "lpi_search_rank_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P],
+    # wide lists, 1 <= k <= 256 in one sweep: the argument lists of the three top-k calls above (search_wide.hip)
+    "lpi_search_wide_workspace": [_I, _I, _I],
+    "lpi_search_topk_wide": [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "lpi_search_topk_wide_t": [_I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "lpi_search_topk_wide_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     # host side: batch assembly of the input pipeline (pipeline.py), BPE tokenizer (a6)
     "lpi_host_gather": [_P, _P, _I, _L, _I],
     "lpi_host_gather_v": [_P, _P, _P, _I, _I],
@@ -169,11 +174,11 @@ SIGNATURES = {
     "lpi_bpe_encode": [_P, _P, _P, _I],
     "lpi_bpe_tokenize": [_P, _P, _I, _I, _I, _P],
 }
-_RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_bpe_create": c_void_p, "lpi_bpe_destroy": None}
+_RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_search_wide_workspace": c_long, "lpi_bpe_create": c_void_p, "lpi_bpe_destroy": None}
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 619
+EXPECTED_ABI = 620
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -22,7 +22,9 @@
 //    with the same acc[n][m], and the epilogues below are the same lines for every type;
 //  * top-k: every wave keeps a sorted list per row of its 64x64 quadrant's columns in LDS; scores are compared in registers with the row's current k-th
 //    and only survivors are inserted (the four lanes that share a row take turns).  Per-(split, wave column) lists go to the workspace, the merge
-//    kernel (search.hip, one for every operand type: it sees f32 scores only) writes idx / val.
+//    kernel (search.hip, one for every operand type: it sees f32 scores only) writes idx / val;
+//  * wide top-k (MODE_WIDE, k <= 256, instantiated by search_wide.hip, where the design is described): the same main loop and masks; scores that beat a
+//    row's threshold are appended to a candidate buffer in the workspace and a wave selects the k best with a bitonic network in registers.
 #pragma once
 #include "common.h"
 #include "mx8.h"
@@ -43,7 +45,10 @@ template <typename T> inline constexpr int kStageBytes = STAGE_BYTES + (kIsMx8<T
 constexpr int NTHREADS = 256;
 constexpr int KMAX = 16;
 constexpr int WG_TARGET = 512;      // workgroups wanted per launch: two per CU of an MI355X
-constexpr int MODE_TOPK = 0, MODE_RANK = 1, MODE_THRESH = 2;
+constexpr int MODE_TOPK = 0, MODE_RANK = 1, MODE_THRESH = 2, MODE_WIDE = 3;
+constexpr int KWIDE = 256;          // MODE_WIDE (search_wide.hip): lists up to this k
+// MODE_WIDE: the capacity of a (split, row) candidate buffer: >= k + one tile's columns, 64 lanes x 4 or 8 registers of the selecting wave
+__host__ __device__ constexpr int wide_cap(int k) { return k <= 128 ? 256 : 512; }
 
 template <typename T>
 struct SearchArgs {
@@ -58,7 +63,7 @@ struct SearchArgs {
     float* thr;          // [nq] threshold score of the best ground-truth column (+inf: none)
     int32_t* gstar;      // [nq] its index (-1: none)
     int32_t* rank;
-    float* part_val;     // [2 * splits][nq][k]
+    float* part_val;     // [2 * splits][nq][k]; MODE_WIDE: the candidate buffers [splits][nq][wide_cap(k)], whose first k end as the split's sorted list
     int32_t* part_idx;
 };
 
@@ -107,6 +112,83 @@ __device__ __forceinline__ void list_insert(lds_f32* lv, lds_i32* li, int k, flo
     }
     lv[p] = s;
     li[p] = j;
+}
+
+// ---- MODE_WIDE: a wave sorts 64 R (value, index) pairs in registers with a bitonic network over `beats` (a total order: the result is unique; the empty
+// pairs (-inf, -1) are equal to each other only and come last).  Element i = lane * R + r: distances below R are exchanges between a lane's own registers
+// (static indices: no scratch), the others a lane exchange (ds_bpermute: no LDS memory)
+template <int R>
+__device__ __forceinline__ void wide_pass(float (&v)[R], int (&x)[R], int lane, int k2)      // one merge level: blocks of k2, distances k2 / 2 .. 1
+{
+    constexpr int LOGR = R == 8 ? 3 : 2;
+    static_assert(R == 4 || R == 8, "wide_pass: 4 or 8 elements per lane");
+#pragma unroll 1
+    for (int j = k2 >> 1; j >= R; j >>= 1) {
+        const int lj = j / R;
+        const bool lower = (lane & lj) == 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool desc = ((lane * R + r) & k2) == 0;      // a descending block: its lower element keeps the better pair
+            const float pv = __shfl_xor(v[r], lj, 64);
+            const int px = __shfl_xor(x[r], lj, 64);
+            const bool pb = beats(pv, px, v[r], x[r]);
+            const bool take = lower == desc ? pb : !pb;
+            v[r] = take ? pv : v[r];
+            x[r] = take ? px : x[r];
+        }
+    }
+#pragma unroll
+    for (int jb = LOGR - 1; jb >= 0; --jb) {
+        const int j = 1 << jb;
+        if (j < k2) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if ((r & j) == 0) {
+                    const int r2 = r | j;
+                    const bool desc = ((lane * R + r) & k2) == 0;
+                    const bool b = beats(v[r2], x[r2], v[r], x[r]);
+                    const bool sw = desc ? b : !b;
+                    const float fv = v[r];
+                    const int fx = x[r];
+                    v[r] = sw ? v[r2] : fv;
+                    x[r] = sw ? x[r2] : fx;
+                    v[r2] = sw ? fv : v[r2];
+                    x[r2] = sw ? fx : x[r2];
+                }
+            }
+        }
+    }
+}
+template <int R>
+__device__ __forceinline__ void wide_sort(float (&v)[R], int (&x)[R], int lane)      // descending in `beats`
+{
+#pragma unroll 1
+    for (int k2 = 2; k2 <= 64 * R; k2 <<= 1) wide_pass<R>(v, x, lane, k2);
+}
+
+// a wave brings the n candidates of a row down to its k best, sorted, in cv / ci [0, k) (a short list ends with (-inf, -1)) -> the k-th pair (tv, ti)
+template <int R>
+__device__ __forceinline__ void wide_select(float* cv, int32_t* ci, int n, int k, int lane, float& tv, int& ti)
+{
+    float v[R];
+    int x[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = lane * R + r;
+        v[r] = i < n ? cv[i] : -INFINITY;
+        x[r] = i < n ? ci[i] : -1;
+    }
+    wide_sort<R>(v, x, lane);
+    float kv = -INFINITY;
+    int ki = -1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = lane * R + r;
+        if (i < k) { cv[i] = v[r]; ci[i] = x[r]; }
+        if (i == k - 1) { kv = v[r]; ki = x[r]; }
+    }
+    tv = __shfl(kv, (k - 1) / R, 64);
+    ti = __shfl(ki, (k - 1) / R, 64);
 }
 
 template <typename T, int MODE>
@@ -203,6 +285,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
         Lv = (lds_f32*)lists;
         Li = (lds_i32*)(lists + 64 * a.k * 4);
         for (int e = lane; e < 64 * a.k; e += 64) { Lv[e] = -INFINITY; Li[e] = -1; }
+    }
+    float* Wv = nullptr;        // MODE_WIDE: per tile row the k-th best pair so far (the threshold) and the fill of its candidate buffer
+    int* Wi = nullptr;
+    int* Wn = nullptr;
+    if constexpr (MODE == MODE_WIDE) {
+        Wv = reinterpret_cast<float*>(smem + 2 * STAGE);
+        Wi = reinterpret_cast<int*>(smem + 2 * STAGE + BM * 4);
+        Wn = reinterpret_cast<int*>(smem + 2 * STAGE + BM * 8);
+        if (tid < BM) { Wv[tid] = -INFINITY; Wi[tid] = -1; Wn[tid] = 0; }      // seen by everyone after the first slab's barrier
     }
     if constexpr (MODE == MODE_RANK) {
 #pragma unroll
@@ -315,7 +406,55 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
                         const int col = col0 + ni * 16 + e;
                         cnt[mi] += (col < a.ng && col != ti[mi] && beats(acc[ni][mi][e], col, tv[mi], ti[mi])) ? 1 : 0;
                     }
-        } else {
+        } else if constexpr (MODE == MODE_WIDE) {
+            // a score that beats its row's threshold is appended to the row's candidate buffer of this split (slot from the LDS counter: the order in
+            // the buffer is arbitrary, the selection's result is not); the two waves of a row share the buffer
+            const int cap = wide_cap(a.k);
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const int rl = wm * 64 + mi * 16 + r16;
+                const bool rowok = m0 + rl < a.nq;
+                const float kv = Wv[rl];
+                const int ki = Wi[rl];
+                unsigned mask = 0;
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int col = col0 + ni * 16 + e;
+                        if (rowok && col < a.ng && beats(acc[ni][mi][e], col, kv, ki)) mask |= 1u << (ni * 4 + e);
+                    }
+                if (__ballot(mask != 0) == 0) continue;
+                const size_t cb = ((size_t)blockIdx.y * a.nq + (rowok ? m0 + rl : 0)) * cap;
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (mask & (1u << (ni * 4 + e))) {
+                            const int slot = atomicAdd(&Wn[rl], 1);      // < cap: the fill was <= cap - BN before this tile
+                            a.part_val[cb + slot] = acc[ni][mi][e];
+                            a.part_idx[cb + slot] = col0 + ni * 16 + e;
+                        }
+                    }
+            }
+            __syncthreads();      // the tile's appends are complete and visible to the workgroup
+            // wave w looks after tile rows 32 w ..: a buffer that the next tile could overflow, and every buffer after the last tile, is brought down to
+            // its k best (sorted: the final one is the part the merge kernel reads), which also raises the threshold
+            const bool last = tile + 1 == t_end;
+#pragma unroll 1
+            for (int rr = 0; rr < BM / 4; ++rr) {
+                const int rl = wave * (BM / 4) + rr;
+                if (m0 + rl >= a.nq) break;
+                const int n = __builtin_amdgcn_readfirstlane(Wn[rl]);
+                if (!last && n + BN <= cap) continue;
+                const size_t cb = ((size_t)blockIdx.y * a.nq + m0 + rl) * cap;
+                float sv;
+                int si;
+                if (cap == 256) wide_select<4>(a.part_val + cb, a.part_idx + cb, n, a.k, lane, sv, si);
+                else wide_select<8>(a.part_val + cb, a.part_idx + cb, n, a.k, lane, sv, si);
+                if (lane == 0) { Wv[rl] = sv; Wi[rl] = si; Wn[rl] = n < a.k ? n : a.k; }
+            }
+        } else if constexpr (MODE == MODE_THRESH) {
             // the diagonal of the tile: row == column  <=>  wm == wn, mi == ni, r16 == 4g + e
             if (wm == wn && g == (r16 >> 2)) {
                 const int e = lane & 3;
@@ -360,7 +499,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
         }
         __syncthreads();
         if (tid < BM && m0 + tid < a.nq && wg[tid]) atomicAdd(a.rank + m0 + tid, wg[tid]);
-    } else {
+    } else if constexpr (MODE == MODE_THRESH) {
         if (wm == wn && g == (r16 >> 2)) {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi) {

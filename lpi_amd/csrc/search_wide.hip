@@ -1,0 +1,131 @@
+// Streamed search, wide lists: the k best gallery rows of every query row for k up to 256 in ONE sweep of the gallery, for every operand type.
+//
+//   lpi_search_topk_wide / _wide_t / _wide_mx8: what lpi_search_topk / _t / _mx8 give, with 1 <= k <= 256
+//
+// The scores are the narrow kernels', bit for bit: the sweep is search_tile.h's kernel (same tile, staging, accumulator chain and masking) with another
+// epilogue, MODE_WIDE.  Keeping a sorted list of 256 per row in LDS is out of reach (64 rows x 256 x 8 bytes per wave), so the selection is lazy:
+//  * per tile row the workgroup keeps a threshold, the row's current k-th best (value, index), and a fill counter in LDS (1.5 KB beside the staging
+//    buffers: two workgroups per CU as before);
+//  * a score that `beats` the threshold is appended, unordered, to the (split, row) candidate buffer in the workspace: wide_cap(k) = 256 or 512 pairs,
+//    at least k + one tile's columns;
+//  * when the next tile could overflow a buffer, one wave sorts it in registers (a bitonic network over `beats`, 4 or 8 pairs per lane), keeps the k
+//    best and raises the threshold; after the first few tiles a row sees about k (1 + ln(columns / k)) appends in all, so this is rare;
+//  * after its last tile every buffer is selected once more: its first k pairs are the split's sorted list;
+//  * the merge kernel (one wave per query row) folds the lists of all splits, and the held list when accumulating, into idx / val: two sorted lists of
+//    256 are merged by taking the better of a[i] and b[255 - i], which are the 256 best as a bitonic sequence, and one merge level.
+// The order is total, so the lists are unique: they do not depend on the order of the appends, the split count or the chunking.  Two launches per call.
+#include "search_tile.h"
+
+namespace {
+
+constexpr int MERGE_ROWS = 4;      // waves (= query rows) per merge workgroup
+
+__global__ __launch_bounds__(64 * MERGE_ROWS) void search_wide_merge_kernel(int nq, int k, int nparts, int cap, const float* __restrict__ part_val,
+                                                                            const int32_t* __restrict__ part_idx, int col_base, int accumulate,
+                                                                            int32_t* idx, float* val)
+{
+    constexpr int R = KWIDE / 64;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * MERGE_ROWS + (threadIdx.x >> 6);
+    if (row >= nq) return;
+    float v[R];      // pair i = lane * R + r of the row's list so far, sorted
+    int x[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { v[r] = -INFINITY; x[r] = -1; }
+    if (accumulate) {      // the held list need not be sorted; its entries with idx < 0 are empty
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = lane * R + r;
+            const int j = i < k ? idx[(size_t)row * k + i] : -1;
+            if (j >= 0) { v[r] = val[(size_t)row * k + i]; x[r] = j; }
+        }
+        wide_sort<R>(v, x, lane);
+    }
+    for (int p = 0; p < nparts; ++p) {
+        const size_t o = ((size_t)p * nq + row) * cap;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = KWIDE - 1 - (lane * R + r);      // the part backwards
+            const int j = i < k ? part_idx[o + i] : -1;
+            if (j >= 0) {
+                const float s = part_val[o + i];
+                if (beats(s, j + col_base, v[r], x[r])) { v[r] = s; x[r] = j + col_base; }
+            }
+        }
+        wide_pass<R>(v, x, lane, KWIDE);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = lane * R + r;
+        if (i < k) { idx[(size_t)row * k + i] = x[r]; val[(size_t)row * k + i] = v[r]; }
+    }
+}
+
+template <typename T>
+int search_topk_wide(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, int k, int col_base, int accumulate, int32_t* idx, float* val,
+                     void* ws, long ws_bytes, void* stream, SearchScales sc = SearchScales{})
+{
+    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
+    if (k < 1 || k > KWIDE || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
+    if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_wide_workspace(nq, ng, k)) return LPI_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    SearchArgs<T> a{};
+    a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
+    if constexpr (kIsMx8<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
+    a.tiles = (ng + BN - 1) / BN;
+    a.splits = search_splits(nq, ng);
+    const int cap = wide_cap(k);
+    const size_t nlist = (size_t)a.splits * nq * cap;      // [splits][nq][cap] values, then as many indices
+    a.part_val = (float*)ws;
+    a.part_idx = (int32_t*)ws + nlist;
+    auto kern = search_kernel<T, MODE_WIDE>;
+    static LdsOnce once;
+    constexpr int LDS = 2 * kStageBytes<T> + BM * 12;
+    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS)) return e;
+    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), LDS, s, a);
+    LPI_CHECK_LAST();
+    LPI_LAUNCH(search_wide_merge_kernel, dim3((nq + MERGE_ROWS - 1) / MERGE_ROWS), dim3(64 * MERGE_ROWS), 0, s, nq, k, a.splits, cap, a.part_val,
+               a.part_idx, col_base, accumulate, idx, val);
+    LPI_CHECK_LAST();
+    return 0;
+}
+
+}  // namespace
+
+// An upper bound of what the launches use that never shrinks when an argument grows: lpi_search_workspace's block bound, one candidate buffer per block row.
+extern "C" long lpi_search_wide_workspace(int nq, int ng, int k)
+{
+    if (nq <= 0 || ng <= 0 || k < 1 || k > KWIDE) return LPI_EINVAL;
+    const long rb = (nq + BM - 1) / BM, tiles = (ng + BN - 1) / BN;
+    const long blocks = tiles * rb < WG_TARGET - 1 + rb ? tiles * rb : WG_TARGET - 1 + rb;      // >= splits * rb
+    return blocks * BM * wide_cap(k) * 8;
+}
+
+extern "C" int lpi_search_topk_wide(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, int k, int col_base, int accumulate,
+                                    int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
+{
+    return search_topk_wide<float>(nq, ng, E, Q, ldq, G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
+}
+
+extern "C" int lpi_search_topk_wide_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, int k, int col_base, int accumulate,
+                                      int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
+{
+    switch (dt) {
+    case LPI_F32:
+        return lpi_search_topk_wide(nq, ng, E, (const float*)Q, ldq, (const float*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
+    case LPI_BF16:
+        return search_topk_wide<bf16_t>(nq, ng, E, (const bf16_t*)Q, ldq, (const bf16_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes,
+                                        stream);
+    case LPI_F16:
+        return search_topk_wide<f16_t>(nq, ng, E, (const f16_t*)Q, ldq, (const f16_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
+    }
+    return LPI_EINVAL;
+}
+
+extern "C" int lpi_search_topk_wide_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
+                                        const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws,
+                                        long ws_bytes, void* stream)
+{
+    return search_topk_wide<mx8_t>(nq, ng, E, (const mx8_t*)Q, ldq, (const mx8_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream,
+                                   SearchScales{(const uint8_t*)q_scales, ldqs, (const uint8_t*)g_scales, ldgs});
+}

@@ -7,7 +7,12 @@ tensor of that dtype is read in place, a score is the f32 sum in one fixed order
 holds.  ``operands="mx8"`` searches MX-FP8 operands (csrc/search_mx8.hip): e4m3 bytes with one E8M0 scale byte per 32 elements, an ``Mx8Rows`` (what
 ``quantize_mx8`` returns), one byte per element plus the scales; an ``Mx8Rows`` is read in place, a float tensor is quantised once; a score is the f32
 result of the block-scaled instruction chain over E in one fixed order, of the QUANTISED rows, and the properties above hold.  There is no fall-back:
-a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, of 128 for MX-FP8, <= 1024; 1 <= k <= 16) raises."""
+a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, of 128 for MX-FP8, <= 1024; 1 <= k <= 256) raises.
+
+``topk`` with k <= 16 keeps a sorted list per row in LDS (the narrow entry points).  17 <= k <= 256 goes to the wide entry points (csrc/search_wide.hip):
+the same scores, bit for bit, in one sweep of the gallery; scores that beat a row's current k-th best are appended to a candidate buffer in the
+workspace and selected down to k when it fills.  The workspace is ``lpi_search_wide_workspace`` bytes (256 or 512 pairs per gallery split and query
+row: 264 MiB where the score matrix of 2048 x 1 048 576 would be 8 GiB), and every property above holds for every operand type."""
 from __future__ import annotations
 
 import torch
@@ -142,10 +147,14 @@ def _rows16(t, dtype):
     return t
 
 
+_KNARROW = 16      # the narrow entry points' k range; above it, up to 256, the wide ones (search_wide.hip)
+
+
 def _workspace(dev, nq, ng, k):
-    need = int(_lib.load().lpi_search_workspace(nq, ng, k))
+    fn = "lpi_search_wide_workspace" if k > _KNARROW else "lpi_search_workspace"
+    need = int(getattr(_lib.load(), fn)(nq, ng, k))
     if need <= 0:
-        raise _lib.LpiError(f"lpi_search_workspace({nq}, {ng}, {k}) refused the shape")
+        raise _lib.LpiError(f"{fn}({nq}, {ng}, {k}) refused the shape")
     ws = _WS.get(dev)
     if ws is None or ws.numel() < need:
         _WS[dev] = None      # drop the old one first: the peak is one workspace, not two
@@ -154,8 +163,8 @@ def _workspace(dev, nq, ng, k):
 
 
 def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
-    """-> (idx int32 [nq, k], val f32 [nq, k]): per query row the k largest scores in the order (value descending, then index descending),
-    lpi_topk's.  ``col_base`` is added to the indices.  ``into`` = the (idx, val) of earlier calls over other gallery chunks: the lists are merged in
+    """-> (idx int32 [nq, k], val f32 [nq, k]), 1 <= k <= 256: per query row the k largest scores in the order (value descending, then index
+    descending), lpi_topk's.  ``col_base`` is added to the indices.  ``into`` = the (idx, val) of earlier calls over other gallery chunks: the lists are merged in
     place and returned.  ``operands``: None | "f32" (anything not f32 is cast to f32) | "bf16" | "f16" (both operands end in that type; val stays f32)
     | "mx8" (an Mx8Rows is read in place, a float tensor is quantised once; val = the scores of the quantised rows)."""
     typed = _operands(operands)
@@ -169,6 +178,8 @@ def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
                 or not idx.is_contiguous() or not val.is_contiguous()):
             raise ValueError("into = (idx int32 [nq, k], val f32 [nq, k]), contiguous")
     ws = _workspace(dev, nq, ng, k)
+    if k > _KNARROW:
+        name = name.replace("lpi_search_topk", "lpi_search_topk_wide")
     _lib.call(name, *lead, int(k), int(col_base), 0 if into is None else 1, idx, val, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
     return idx, val
 

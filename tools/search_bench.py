@@ -16,7 +16,7 @@ kernels sum K in another order) and the count is recorded.  The bf16 / f16 arms 
 timed region and before the peak is taken, as a gallery held in that type is; their ranks are compared with the f32 streamed arm's, which is the
 baseline their time is read against in the same run (rounding the rows moves scores by up to 2u + u^2, so ranks differ: the count is a description).
 
-    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8]
+    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8 | --wide]
 
 writes profiles/search_stream_2byte.json (profiles/search_stream.json is the record of the f32 arms alone, before the 2-byte arms existed).
 
@@ -24,6 +24,10 @@ writes profiles/search_stream_2byte.json (profiles/search_stream.json is the rec
 format is) beside the f32 and bf16 streamed arms of the same run, and nothing else: rank and top-10 at i2t / t2i and, unless --no-large, at train.
 Against the f32 streamed arm it records the rows whose rank differs and the mean overlap of the top-10 index sets (descriptions: MX rounding moves
 scores).  It writes profiles/search_stream_mx8.json and leaves the other two records alone.
+
+--wide: the wide top-k path (csrc/search_wide.hip) at k = 17, 100, 256 on f32, bf16 and MX-FP8 operands, the matrix path (score_matrix + lpi_topk, which
+takes any k) at the same k and the narrow streamed top-16, interleaved, at i2t; each streamed arm once at train unless --no-large (the matrix does not
+exist there).  Per arm: time, time relative to top-16 and to the matrix path, peak bytes.  It writes profiles/search_stream_wide.json only.
 
 An error ends the process: nothing further is started.  Run it under a time limit."""
 import argparse
@@ -156,16 +160,76 @@ def _mx8_arms(a, res, img, txt, gt_i, gt_t, gen):
     print("train", json.dumps(out), flush=True)
 
 
+def _wide_arms(a, res, img, txt, gen, matrix_topk, score_matrix):
+    """--wide: streamed top-k on the wide path at k = 17, 100, 256 (f32 / bf16 / mx8 operands) against the matrix path (score_matrix + lpi_topk) and
+    the narrow streamed top-16, interleaved in this process."""
+    import torch
+    from lpi_amd import _lib, search
+    E = img.shape[1]
+    KS = (17, 100, 256)
+    q, g = img, txt
+    q2, g2 = q.bfloat16(), g.bfloat16()                              # cast / quantised once, outside the timed region
+    q8, g8 = search.quantize_mx8(q), search.quantize_mx8(g)
+    arms = {"streamed_top16": lambda: search.topk(q, g, 16)}
+    for k in KS:
+        arms["streamed_top%d" % k] = lambda k=k: search.topk(q, g, k)
+        arms["streamed_top%d_bf16" % k] = lambda k=k: search.topk(q2, g2, k, operands="bf16")
+        arms["streamed_top%d_mx8" % k] = lambda k=k: search.topk(q8, g8, k, operands="mx8")
+        arms["matrix_top%d" % k] = lambda k=k: matrix_topk(score_matrix(q, g)[0], k)
+    out = _median_rounds(arms, a.rounds, a.steps)
+    for name, fn in arms.items():
+        out[name]["peak_bytes"] = _peak(fn)
+    for k in KS:
+        out["top%d_rows_differing_matrix_vs_streamed" % k] = int((arms["matrix_top%d" % k]()[0] != arms["streamed_top%d" % k]()[0]).any(1).sum())
+        for ops in ("", "_bf16", "_mx8"):
+            name = "streamed_top%d%s" % (k, ops)
+            out[name]["vs_top16"] = round(out[name]["ms"] / out["streamed_top16"]["ms"], 3)
+            out[name]["vs_matrix"] = round(out[name]["ms"] / out["matrix_top%d" % k]["ms"], 3)
+    out["rows"] = int(q.shape[0])
+    out["workspace_bytes"] = dict({"top16": int(_lib.load().lpi_search_workspace(q.shape[0], g.shape[0], 16))},
+                                  **{"top%d" % k: int(_lib.load().lpi_search_wide_workspace(q.shape[0], g.shape[0], k)) for k in KS})
+    out["score_matrix_bytes"] = q.shape[0] * g.shape[0] * 4
+    res["shapes"]["i2t_5000x25000"] = out
+    print("i2t_5000x25000", json.dumps(out), flush=True)
+    if a.no_large:
+        res["shapes"]["train_123287x616767"] = "not measured (--no-large)"
+        return
+    nq, ng = 123287, 616767
+    del q, g, q2, g2, q8, g8, arms
+    torch.cuda.empty_cache()
+    q, g = _unit(nq, E, gen), _unit(ng, E, gen)
+    q2, g2 = q.bfloat16(), g.bfloat16()
+    q8, g8 = search.quantize_mx8(q), search.quantize_mx8(g)
+    out = {}
+    runs = [("streamed_top16", lambda: search.topk(q, g, 16))]
+    for k in KS:
+        runs += [("streamed_top%d" % k, lambda k=k: search.topk(q, g, k)),
+                 ("streamed_top%d_bf16" % k, lambda k=k: search.topk(q2, g2, k, operands="bf16")),
+                 ("streamed_top%d_mx8" % k, lambda k=k: search.topk(q8, g8, k, operands="mx8"))]
+    for name, fn in runs:
+        r, ms, peak = _timed_once(fn)
+        del r
+        out[name] = {"ms": round(ms, 2), "calls_timed": 1, "peak_bytes": peak, "tflops": round(2.0 * nq * ng * E / (ms * 1e-3) / 1e12, 2)}
+        out[name]["vs_top16"] = round(ms / out["streamed_top16"]["ms"], 3)
+        print(name, json.dumps(out[name]), flush=True)
+    out["rows"] = nq
+    out["matrix"] = "not measured: the score matrix would be %d bytes" % (nq * ng * 4)
+    out["score_matrix_bytes"] = nq * ng * 4
+    res["shapes"]["train_123287x616767"] = out
+    print("train", json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--no-large", action="store_true")
     ap.add_argument("--mx8", action="store_true", help="the f32, bf16 and MX-FP8 streamed arms only -> profiles/search_stream_mx8.json")
+    ap.add_argument("--wide", action="store_true", help="the wide top-k arms (k = 17, 100, 256) against the matrix path -> profiles/search_stream_wide.json")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "search_stream_mx8.json" if a.mx8 else "search_stream_2byte.json")
+        a.out = os.path.join(REPO, "profiles", "search_stream_wide.json" if a.wide else "search_stream_mx8.json" if a.mx8 else "search_stream_2byte.json")
     import torch
     from lpi_amd import _lib, search
     from lpi_amd.engine import score_matrix
@@ -190,8 +254,11 @@ def main():
         return idx, val
 
     res = {"device": torch.cuda.get_device_name(0), "abi": int(_lib.load().lpi_version()), "rounds": a.rounds, "steps": a.steps, "E": E, "shapes": {}}
-    if a.mx8:
+    if a.wide:
+        _wide_arms(a, res, img, txt, gen, matrix_topk, score_matrix)
+    elif a.mx8:
         _mx8_arms(a, res, img, txt, gt_i, gt_t, gen)
+    if a.wide or a.mx8:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
