@@ -709,6 +709,23 @@ int lpi_search_topk_wide_t(int dt, int nq, int ng, int E, const void* Q, int ldq
 int lpi_search_topk_wide_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
                              const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes,
                              void* stream);
+/* Second stage of a two-stage search (search_rerank.hip, since 621): exact scores of a short candidate list per query row.  For query row i the
+ * candidates are cand[i * ldc + 0 .. kc - 1], gallery row indices: what a coarse lpi_search_topk* call (2-byte or MX-FP8 operands, k a little above the
+ * k wanted) left in idx, or several such lists side by side.  An entry outside [0, ng), negative ones (the padding of a short list) included, is
+ * padding and never used as an address; an index that occurs several times in a row counts once.  The distinct valid candidates are scored against
+ * Q[i, :] and the k best go to idx / val [nq, k] (contiguous rows of k) in lpi_topk's order, value descending, then index descending; unfilled slots
+ * are (-1, -inf) and come last.  val has exactly the bits lpi_search_topk / lpi_search_topk_t of the same operand type returns for that (query row,
+ * gallery row): the same matrix instruction and the same accumulator chain over E, so a coarse list that contains the f32 top k, re-ranked on the f32
+ * rows, IS lpi_search_topk's f32 result, comparable with ==.  Envelope: the narrow call's for the operand type (nq, ng > 0; E <= 1024 and a multiple
+ * of 16 for f32, of 32 for 2-byte operands; leading dimensions >= E and multiples of 16 bytes, Q / G 16-byte aligned), 1 <= kc <= LPI_SEARCH_KWIDE,
+ * 1 <= k <= kc, ldc >= kc, no NULL pointer; cand is read only (it must not overlap idx / val), nothing of cand beyond kc entries per row and no
+ * gallery row that is not listed is read.  Anything else is LPI_EINVAL before any launch.  No workspace: memory is the two outputs.  One launch per
+ * call, whatever nq, kc and k.  lpi_search_rerank_t: dt = LPI_BF16 | LPI_F16 (2-byte Q / G of that one type, read in place); LPI_F32 forwards to
+ * lpi_search_rerank; LPI_MX8 (the second stage exists for the better operand), LPI_F32X3 and anything else is LPI_EINVAL. */
+int lpi_search_rerank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* cand, int ldc, int kc, int k,
+                      int32_t* idx, float* val, void* stream);
+int lpi_search_rerank_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, const int32_t* cand, int ldc, int kc, int k,
+                        int32_t* idx, float* val, void* stream);
 
 /* ---- a6 (host side): CLIP byte-level BPE      replaces: models/clip/simple_tokenizer.py:62-132, clip.py:185-221 ------
  * HOST functions (no GPU work, no stream).  create: `merges_utf8` is the decompressed text of bpe_simple_vocab_16e6.txt(.gz) —

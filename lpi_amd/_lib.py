@@ -149,6 +149,9 @@ SIGNATURES = {
     "lpi_search_topk_wide": [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "lpi_search_topk_wide_t": [_I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "lpi_search_topk_wide_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    # second stage: exact scores of a candidate list per query row, the k best of them (search_rerank.hip); the _t form takes dt first
+    "lpi_search_rerank": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "lpi_search_rerank_t": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     # host side: batch assembly of the input pipeline (pipeline.py), BPE tokenizer (a6)
     "lpi_host_gather": [_P, _P, _I, _L, _I],
     "lpi_host_gather_v": [_P, _P, _P, _I, _I],
@@ -178,7 +181,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 620
+EXPECTED_ABI = 621
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

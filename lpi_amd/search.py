@@ -12,7 +12,11 @@ a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, of 
 ``topk`` with k <= 16 keeps a sorted list per row in LDS (the narrow entry points).  17 <= k <= 256 goes to the wide entry points (csrc/search_wide.hip):
 the same scores, bit for bit, in one sweep of the gallery; scores that beat a row's current k-th best are appended to a candidate buffer in the
 workspace and selected down to k when it fills.  The workspace is ``lpi_search_wide_workspace`` bytes (256 or 512 pairs per gallery split and query
-row: 264 MiB where the score matrix of 2048 x 1 048 576 would be 8 GiB), and every property above holds for every operand type."""
+row: 264 MiB where the score matrix of 2048 x 1 048 576 would be 8 GiB), and every property above holds for every operand type.
+
+``rerank`` is the second stage of a two-stage search (csrc/search_rerank.hip): the exact scores of a short candidate list per query row, with the bits
+``topk`` of the same operand type gives those pairs, and the k best of them.  ``topk_reranked`` runs a coarse ``topk`` ("mx8" / "bf16") that
+over-fetches a little and re-ranks its lists on the better operand: where the coarse list holds the f32 top k, the result IS ``topk``'s f32 result."""
 from __future__ import annotations
 
 import torch
@@ -194,3 +198,78 @@ def gt_rank(queries, gallery, gt, *, operands=None):
     ws = _workspace(dev, nq, ng, 0)
     _lib.call(name, *lead, gt, gt.shape[1], rank, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
     return rank
+
+
+_KWIDE = 256      # LPI_SEARCH_KWIDE: the longest list of topk and the longest candidate list of rerank
+
+
+def rerank(queries, gallery, cand, k=None, *, operands=None):
+    """-> (idx int32 [nq, k], val f32 [nq, k]): per query row the k best of the gallery rows listed in ``cand`` [nq, kc] (integer, kc <= 256; k defaults
+    to kc), scored on the operands themselves, in ``topk``'s order.  An entry outside [0, ng) is padding (the -1 of a short list), an index that occurs
+    several times in a row counts once (lists of several coarse passes may simply be concatenated), unfilled slots are (-1, -inf) and come last.
+    ``val`` has the bits ``topk`` with the same ``operands`` returns for the pair, so a re-ranked list compares with ``==`` against a searched one.
+    ``operands``: None | "f32" | "bf16" | "f16" with ``topk``'s in-place rules; MX-FP8 is not a re-rank type (the second stage exists for the better
+    operand).  An int32 ``cand`` with unit inner stride is read in place, a row-strided view included; anything else is converted once.  One launch,
+    no workspace."""
+    typed = _operands(operands)
+    if typed == "mx8" or isinstance(queries, Mx8Rows) or isinstance(gallery, Mx8Rows):
+        raise ValueError('rerank scores f32 / bf16 / f16 operands: MX-FP8 ("mx8", an Mx8Rows) is a coarse type, not a re-rank type')
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype.is_floating_point or cand.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError("cand = an integer tensor [nq, kc]")
+    if queries.dim() != 2 or gallery.dim() != 2:
+        raise ValueError("expected [rows, E] tensors")
+    nq, E = queries.shape
+    ng = gallery.shape[0]
+    if gallery.shape[1] != E:
+        raise ValueError(f"queries have {E} features, the gallery {gallery.shape[1]}")
+    kc = cand.shape[1]
+    if cand.shape[0] != nq:
+        raise ValueError(f"cand has {cand.shape[0]} rows, the queries {nq}")
+    if not 1 <= kc <= _KWIDE:
+        raise ValueError(f"cand lists 1 .. {_KWIDE} candidates per row, not {kc}")
+    k = kc if k is None else int(k)
+    if not 1 <= k <= kc:
+        raise ValueError(f"1 <= k <= kc = {kc}, not {k}")
+    if typed is None:
+        q, g = _f32_rows(queries), _f32_rows(gallery)
+    else:
+        q, g = _rows16(queries, typed[1]), _rows16(gallery, typed[1])
+    dev = q.device
+    if cand.dtype != torch.int32 or cand.stride(1) != 1 or cand.stride(0) < kc or cand.device != dev:
+        if cand.dtype != torch.int32:      # an index that does not fit int32 must stay padding
+            cand = torch.where((cand < 0) | (cand >= ng), torch.full_like(cand, -1), cand)
+        cand = cand.to(device=dev, dtype=torch.int32).contiguous()
+    idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    val = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    tail = (cand, cand.stride(0), kc, k, idx, val, torch.cuda.current_stream().cuda_stream)
+    if typed is None:
+        _lib.call("lpi_search_rerank", nq, ng, E, q, q.stride(0), g, g.stride(0), *tail)
+    else:
+        _lib.call("lpi_search_rerank_t", typed[0], nq, ng, E, q, q.stride(0), g, g.stride(0), *tail)
+    return idx, val
+
+
+def topk_reranked(queries, gallery, k, *, coarse="mx8", candidates=None, coarse_queries=None, coarse_gallery=None, operands=None):
+    """Two-stage search -> (idx int32 [nq, k], val f32 [nq, k]): ``topk(coarse_queries or queries, coarse_gallery or gallery, candidates,
+    operands=coarse)`` (the narrow kernels up to 16 candidates, the wide ones above), then ``rerank(queries, gallery, its idx, k, operands=operands)``.
+    Where the coarse list of a row holds the row's exact top k, the row's result is ``topk(queries, gallery, k, operands=operands)``'s, bit for bit; a
+    neighbour the coarse pass ranks below ``candidates`` is lost.  ``candidates`` defaults to min(ng, 256, max(4 k, 32)), a choice, not a measurement
+    (DESIGN.md has what k, 2 k and 4 k recover), and must satisfy k <= candidates <= min(ng, 256).  ``coarse_gallery`` / ``coarse_queries``: the
+    ``Mx8Rows`` (``quantize_mx8``) or the 2-byte copy of the operand, held by the caller across calls; WITHOUT them the operand is quantised or cast
+    again on every call, which for the gallery costs a pass over it and its coarse copy in memory each time.  A coarse gallery searched in chunks
+    composes with ``rerank`` directly: ``topk(..., col_base=, into=)`` over the chunks, then one ``rerank`` on the whole exact gallery."""
+    _operands(coarse)      # an unknown name is refused here, before anything else
+    if _operands(operands) == "mx8":
+        raise ValueError('the re-rank operands are f32 / bf16 / f16, not "mx8"')
+    ng = gallery.shape[0]
+    k = int(k)
+    top = min(ng, _KWIDE)
+    candidates = min(top, max(4 * k, 32)) if candidates is None else int(candidates)
+    if not 1 <= k <= candidates <= top:
+        raise ValueError(f"1 <= k <= candidates <= min(ng, {_KWIDE}) = {top}, not k = {k}, candidates = {candidates}")
+    cq = queries if coarse_queries is None else coarse_queries
+    cg = gallery if coarse_gallery is None else coarse_gallery
+    if cq.shape[0] != queries.shape[0] or cg.shape[0] != ng:
+        raise ValueError("the coarse operands have the rows of the exact ones")
+    cidx, _ = topk(cq, cg, candidates, operands=coarse)
+    return rerank(queries, gallery, cidx, k, operands=operands)

@@ -16,7 +16,7 @@ kernels sum K in another order) and the count is recorded.  The bf16 / f16 arms 
 timed region and before the peak is taken, as a gallery held in that type is; their ranks are compared with the f32 streamed arm's, which is the
 baseline their time is read against in the same run (rounding the rows moves scores by up to 2u + u^2, so ranks differ: the count is a description).
 
-    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8 | --wide]
+    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8 | --wide | --rerank]
 
 writes profiles/search_stream_2byte.json (profiles/search_stream.json is the record of the f32 arms alone, before the 2-byte arms existed).
 
@@ -28,6 +28,12 @@ scores).  It writes profiles/search_stream_mx8.json and leaves the other two rec
 --wide: the wide top-k path (csrc/search_wide.hip) at k = 17, 100, 256 on f32, bf16 and MX-FP8 operands, the matrix path (score_matrix + lpi_topk, which
 takes any k) at the same k and the narrow streamed top-16, interleaved, at i2t; each streamed arm once at train unless --no-large (the matrix does not
 exist there).  Per arm: time, time relative to top-16 and to the matrix path, peak bytes.  It writes profiles/search_stream_wide.json only.
+
+--rerank: the two-stage search (lpi_amd.search.topk_reranked: a coarse MX-FP8 or bf16 top-kc on operands held in that type, then csrc/search_rerank.hip
+on the f32 rows) at k = 10 with kc = k, 2 k and 4 k, beside the f32 streamed top-10 (narrow) and top-17 (wide) of the same run, which are the parent's
+unchanged code and the baseline, and the re-rank launch alone on a held candidate list; interleaved at i2t, each arm once at train unless --no-large.
+Per arm: time, peak bytes, and the share of rows whose final (idx, val) equals the f32 top-10's bit for bit.  It writes
+profiles/search_stream_rerank.json only.
 
 An error ends the process: nothing further is started.  Run it under a time limit."""
 import argparse
@@ -219,6 +225,66 @@ def _wide_arms(a, res, img, txt, gen, matrix_topk, score_matrix):
     print("train", json.dumps(out), flush=True)
 
 
+def _rerank_arms(a, res, img, txt, gen):
+    """--rerank: coarse top-kc (mx8 / bf16, operands held) + the f32 re-rank to k = 10 at kc = k, 2 k, 4 k, against the f32 streamed top-10 / top-17."""
+    import torch
+    from lpi_amd import search
+    E, K = img.shape[1], 10
+    KCS = (K, 2 * K, 4 * K)
+
+    def build(q, g):
+        held = {"mx8": (search.quantize_mx8(q), search.quantize_mx8(g)), "bf16": (q.bfloat16(), g.bfloat16())}      # once, outside the timed region
+        arms = {"streamed_top10": lambda: search.topk(q, g, K), "streamed_top17": lambda: search.topk(q, g, 17)}
+        for ops, (cq, cg) in held.items():
+            for kc in KCS:
+                arms["two_stage_%s_kc%d" % (ops, kc)] = lambda ops=ops, cq=cq, cg=cg, kc=kc: search.topk_reranked(
+                    q, g, K, coarse=ops, candidates=kc, coarse_queries=cq, coarse_gallery=cg)
+        return held, arms
+
+    def same_rows(r, want):
+        return round(float(((r[0] == want[0]) & (r[1].view(torch.int32) == want[1].view(torch.int32))).all(1).float().mean()), 4)
+
+    q, g = img, txt
+    held, arms = build(q, g)
+    lists = {kc: search.topk(*held["mx8"], kc, operands="mx8")[0] for kc in KCS + (256,)}
+    for kc in lists:
+        arms["rerank_alone_kc%d" % kc] = lambda kc=kc: search.rerank(q, g, lists[kc], min(kc, K) if kc < 256 else 256)
+    out = _median_rounds(arms, a.rounds, a.steps)
+    want = arms["streamed_top10"]()
+    for name, fn in arms.items():
+        out[name]["peak_bytes"] = _peak(fn)
+        out[name]["vs_streamed_top10"] = round(out[name]["ms"] / out["streamed_top10"]["ms"], 3)
+        if name.startswith("two_stage"):
+            out[name]["rows_equal_f32_top10"] = same_rows(fn(), want)
+    out["rows"] = int(q.shape[0])
+    out["gallery_bytes"] = {"f32": g.shape[0] * E * 4, "bf16": g.shape[0] * E * 2, "mx8": held["mx8"][1].nbytes}
+    res["shapes"]["i2t_5000x25000"] = out
+    print("i2t_5000x25000", json.dumps(out), flush=True)
+    if a.no_large:
+        res["shapes"]["train_123287x616767"] = "not measured (--no-large)"
+        return
+    nq, ng = 123287, 616767
+    del q, g, held, arms, lists, want
+    torch.cuda.empty_cache()
+    q, g = _unit(nq, E, gen), _unit(ng, E, gen)
+    held, arms = build(q, g)
+    out, want = {}, None
+    for name, fn in arms.items():
+        r, ms, peak = _timed_once(fn)
+        out[name] = {"ms": round(ms, 2), "calls_timed": 1, "peak_bytes": peak}
+        if name == "streamed_top10":
+            want = r
+        out[name]["vs_streamed_top10"] = round(ms / out["streamed_top10"]["ms"], 3)
+        if name.startswith("two_stage"):
+            out[name]["rows_equal_f32_top10"] = same_rows(r, want)
+        del r
+        print(name, json.dumps(out[name]), flush=True)
+    out["rows"] = nq
+    out["gallery_bytes"] = {"f32": ng * E * 4, "bf16": ng * E * 2, "mx8": held["mx8"][1].nbytes}
+    res["shapes"]["train_123287x616767"] = out
+    print("train", json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -226,10 +292,12 @@ def main():
     ap.add_argument("--no-large", action="store_true")
     ap.add_argument("--mx8", action="store_true", help="the f32, bf16 and MX-FP8 streamed arms only -> profiles/search_stream_mx8.json")
     ap.add_argument("--wide", action="store_true", help="the wide top-k arms (k = 17, 100, 256) against the matrix path -> profiles/search_stream_wide.json")
+    ap.add_argument("--rerank", action="store_true", help="the two-stage search (coarse mx8 / bf16 + f32 re-rank) against the f32 top-10 -> profiles/search_stream_rerank.json")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "search_stream_wide.json" if a.wide else "search_stream_mx8.json" if a.mx8 else "search_stream_2byte.json")
+        a.out = os.path.join(REPO, "profiles", "search_stream_rerank.json" if a.rerank else "search_stream_wide.json" if a.wide
+                             else "search_stream_mx8.json" if a.mx8 else "search_stream_2byte.json")
     import torch
     from lpi_amd import _lib, search
     from lpi_amd.engine import score_matrix
@@ -254,11 +322,13 @@ def main():
         return idx, val
 
     res = {"device": torch.cuda.get_device_name(0), "abi": int(_lib.load().lpi_version()), "rounds": a.rounds, "steps": a.steps, "E": E, "shapes": {}}
-    if a.wide:
+    if a.rerank:
+        _rerank_arms(a, res, img, txt, gen)
+    elif a.wide:
         _wide_arms(a, res, img, txt, gen, matrix_topk, score_matrix)
     elif a.mx8:
         _mx8_arms(a, res, img, txt, gt_i, gt_t, gen)
-    if a.wide or a.mx8:
+    if a.rerank or a.wide or a.mx8:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
