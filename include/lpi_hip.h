@@ -494,7 +494,9 @@ int lpi_eot_index(int B, int L, const int64_t* ids, int32_t* idx, void* stream);
  * The tail of a training step — the pooled rows of the last block, the heads, the L2 norms (model.py:255-257, prompt_learner.py:57-61,
  * slinet.py:122,133), the prompt rows (model.py:189-193, 240-248) — is a chain of few-microsecond launches on B or B*P rows, one per tower
  * and op.  lpi_row_jobs issues up to LPI_ROW_JOBS_MAX INDEPENDENT ones (the two towers' launch of the same op; independent ops of one tower) as
- * one launch: every job runs the body of its single-op kernel, so the results are bit for bit those of the entry point named below.
+ * one launch: every job runs the body of its single-op kernel, so the results are bit for bit those of the entry point named below, and every
+ * job is checked by that entry point's own argument predicate (csrc/rowops.hip: pool_ln_fwd_ok, l2norm_bwd_ok, scatter_add_ok, ... — one rule per op,
+ * called from both; what a job form adds to it, such as out2, is written out in row_job_blocks).
  * Fields a job does not use are ignored.  dt_*: LPI_F32 / LPI_BF16 / LPI_F16.
  *   POOL_LN_FWD          lpi_pool_ln_fwd(dt_b, dt_a, B, L, d, a, idx, gamma, beta, out, ld_c, mean, rstd); out2 (optional) = the gathered row itself
  *                        as f32 [B, d] (lpi_gather_rows(dt_a, B, L, d, a, idx, out2))

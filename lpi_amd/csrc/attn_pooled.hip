@@ -198,21 +198,6 @@ __global__ __launch_bounds__(WAVE * WPB) void attn_pooled_bwd_pair_kernel(PoolBw
                                 p.ldo, p.lse, (T*)p.dq, p.lddq, (T*)p.dqkv, p.ldg, p.causal, p.pre, p.part);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void scatter_add_rows_kernel(int B, int L, int d, const T* __restrict__ src, int lds_, const int* __restrict__ idx,
-                                                                T* __restrict__ dst, int ldd)
-{
-    const int b = blockIdx.x;
-    const int row = idx ? idx[b] : 0;
-    T* o = dst + ((size_t)b * L + row) * ldd;
-    const T* i = src + (size_t)b * lds_;
-    for (int c = threadIdx.x * 4; c < d; c += 256 * 4) {
-        f32x4 a = Elem<T>::ld4(o + c), v = Elem<T>::ld4(i + c);
-        a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
-        Elem<T>::st4(o + c, a);
-    }
-}
-
 }  // namespace
 
 extern "C" int lpi_attn_pooled_fwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* q, int ldq, const void* qkv, int ld,
@@ -411,22 +396,4 @@ extern "C" int lpi_attn_pooled_bwd(int dtype, int B, int L, int H, const void* q
                                    void* stream)
 {
     return lpi_attn_pooled_bwd_varlen(dtype, B, L, nullptr, H, q, ldq, qkv, ld, idx, dctx, ldo, lse, dq, lddq, dqkv, ldg, causal, stream);
-}
-
-extern "C" int lpi_scatter_add_rows(int dtype, int B, int L, int d, const void* src, int ld_src, const int* idx, void* dst, int ld_dst,
-                                    void* stream)
-{
-    if (!src || !dst || B <= 0 || L < 0 || (L == 0 && !idx) || d <= 0 || (d & 3) || ld_src < d || ld_dst < d) return LPI_EINVAL;      // L == 0: idx holds absolute rows
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    // rows are moved four elements at a time (Elem<T>::ld4 / st4): 16 bytes of f32, 8 bytes of bf16 (up to 617 f32 rows were held to 8 bytes only)
-    if ((ld_src & 3) || (ld_dst & 3) || (((uintptr_t)src | (uintptr_t)dst) & (uintptr_t)(4 * esz - 1))) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LPI_F32)
-        LPI_LAUNCH((scatter_add_rows_kernel<float>), dim3(B), dim3(256), 0, s, B, L, d, (const float*)src, ld_src, idx, (float*)dst, ld_dst);
-    else if (dtype == LPI_BF16)
-        LPI_LAUNCH((scatter_add_rows_kernel<bf16_t>), dim3(B), dim3(256), 0, s, B, L, d, (const bf16_t*)src, ld_src, idx, (bf16_t*)dst, ld_dst);
-    else
-        return LPI_ENOSYS;
-    LPI_CHECK_LAST();
-    return 0;
 }

@@ -5,6 +5,7 @@
 // Format: mx8.h.  A 32-element block is held by 8 consecutive lanes, 4 elements each: the block maximum is three DPP steps, a lane stores one dword of
 // elements and the first of the 8 the scale byte.
 #include "mx8.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -80,10 +81,11 @@ extern "C" int lpi_mx8_quantize(int x_dtype, int rows, int K, const void* x, int
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
     hipStream_t s = (hipStream_t)stream;
     uint8_t *qp = (uint8_t*)q, *sp = (uint8_t*)scales;
-    if (x_dtype == LPI_F32) LPI_LAUNCH(mx8_quantize_kernel<float>, g, b, 0, s, n, K / 32, (const float*)x, ldx, qp, ldq, sp, lds);
-    else if (x_dtype == LPI_BF16) LPI_LAUNCH(mx8_quantize_kernel<bf16_t>, g, b, 0, s, n, K / 32, (const bf16_t*)x, ldx, qp, ldq, sp, lds);
-    else if (x_dtype == LPI_F16) LPI_LAUNCH(mx8_quantize_kernel<f16_t>, g, b, 0, s, n, K / 32, (const f16_t*)x, ldx, qp, ldq, sp, lds);
-    else return LPI_EINVAL;
+    if (!dispatch_types(TypeList<Types<float>, Types<bf16_t>, Types<f16_t>>{}, [&](auto t) {
+            typedef type_of<decltype(t)> TX;
+            LPI_LAUNCH(mx8_quantize_kernel<TX>, g, b, 0, s, n, K / 32, (const TX*)x, ldx, qp, ldq, sp, lds);
+        }, x_dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -93,17 +95,17 @@ extern "C" int lpi_layernorm_mx8_fwd(int x_dtype, int rows, int d, const void* x
 {
     if (!x || !gamma || !beta || !q || !scales || rows <= 0 || d <= 0 || (d & 31) || d > 1024 || ldx < d || ldq < d || lds < d / 32 || (ldq & 3) || (ldx & 3))
         return LPI_EINVAL;
-    if (x_dtype != LPI_F32 && x_dtype != LPI_F16) return LPI_EINVAL;
     if (((uintptr_t)x & (x_dtype == LPI_F32 ? 15 : 7)) || ((uintptr_t)q & 3) || (((uintptr_t)gamma | (uintptr_t)beta) & 15)) return LPI_EINVAL;
     const dim3 g((unsigned)((rows + 3) / 4)), b(256);
     hipStream_t s = (hipStream_t)stream;
     uint8_t *qp = (uint8_t*)q, *sp = (uint8_t*)scales;
-    const int nc = (d + 255) / 256;
-#define LNM(TX, NC) LPI_LAUNCH((ln_mx8_kernel<TX, NC>), g, b, 0, s, rows, d, (const TX*)x, ldx, gamma, beta, qp, ldq, sp, lds, mean, rstd)
-#define LNM_T(TX) do { if (nc == 1) LNM(TX, 1); else if (nc == 2) LNM(TX, 2); else if (nc == 3) LNM(TX, 3); else LNM(TX, 4); } while (0)
-    if (x_dtype == LPI_F32) LNM_T(float); else LNM_T(f16_t);
-#undef LNM_T
-#undef LNM
+    if (!dispatch_types(TypeList<Types<float>, Types<f16_t>>{}, [&](auto t) {
+            typedef type_of<decltype(t)> TX;
+            dispatch_nc<1, 2, 3, 4>(d, [&](auto nc) {
+                LPI_LAUNCH((ln_mx8_kernel<TX, nc>), g, b, 0, s, rows, d, (const TX*)x, ldx, gamma, beta, qp, ldq, sp, lds, mean, rstd);
+            });
+        }, x_dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }

@@ -11,6 +11,7 @@
 // 16-byte coalesced load/store.  These kernels are bounded by HBM bandwidth, not by the matrix cores.
 #include <type_traits>
 #include "common.h"
+#include "dispatch.h"
 
 // the guard of the one-sweep row statistics (lpi_rowstat_guard, include/lpi_hip.h): per HOST THREAD, like the stream the caller launches on.
 // counter: device memory; flag: the DEVICE alias of a word of pinned host memory (or of device memory), written once, by the row that takes the
@@ -805,6 +806,24 @@ __global__ __launch_bounds__(256) void transpose2_kernel(int rows0, int cols0, c
     }
 }
 
+// o[0 .. d) += i[0 .. d), by the 256 threads of a block: the row update of scatter_add_rows_kernel and of the SCATTER_ADD job
+template <typename T>
+__device__ __forceinline__ void scatter_add_body(int d, const T* __restrict__ i, T* __restrict__ o) {
+    for (int c = threadIdx.x * 4; c < d; c += 256 * 4) {
+        f32x4 a = Elem<T>::ld4(o + c), v = Elem<T>::ld4(i + c);
+        a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
+        Elem<T>::st4(o + c, a);
+    }
+}
+// dst[b*L + idx[b], :] += src[b, :] (idx NULL -> row 0): one block per sample
+template <typename T>
+__global__ __launch_bounds__(256) void scatter_add_rows_kernel(int B, int L, int d, const T* __restrict__ src, int lds_, const int* __restrict__ idx,
+                                                                T* __restrict__ dst, int ldd) {
+    const int b = blockIdx.x;
+    const int row = idx ? idx[b] : 0;
+    scatter_add_body<T>(d, src + (size_t)b * lds_, dst + ((size_t)b * L + row) * ldd);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // lpi_row_jobs: up to LPI_ROW_JOBS_MAX small row kernels of one dependency level in ONE launch.  The tail of a training step (pooled
 // heads, L2 norms, prompt rows: everything that works on B or B*P rows) is a chain of ~5 us launches, one per tower and op; the towers'
@@ -812,18 +831,23 @@ __global__ __launch_bounds__(256) void transpose2_kernel(int rows0, int cols0, c
 // job runs the BODY of the single-op kernel above with its own block index, so every result is bit for bit the single launch's.
 struct RowJobs { lpi_row_job j[LPI_ROW_JOBS_MAX]; int nb[LPI_ROW_JOBS_MAX]; int n; RowstatGuard guard; };
 
+// the type combinations the family instantiates, shared by the entry points and the job cases of one op (Types<...> in the order of the lambda's tags)
+typedef TypeList<Types<float, float>, Types<float, bf16_t>, Types<f16_t, bf16_t>, Types<float, f16_t>, Types<f16_t, f16_t>> PoolLnFwdXY;
+typedef TypeList<Types<float>, Types<bf16_t>> F32orBF16;
+typedef TypeList<Types<float>, Types<f16_t>> F32orF16;
+typedef TypeList<Types<float>, Types<bf16_t>, Types<f16_t>> AnyElem;
+typedef TypeList<Types<bf16_t, bf16_t>, Types<float, float>> LnBwdJobDyCast;
+
+// The lambdas capture BY VALUE: a reference to q held in a closure made the compiler copy the whole job list from the kernel arguments to scratch
+// (656 bytes, +10 VGPRs); with [=] the kernel reads the fields it uses with scalar loads, as the if-chains did.
 __device__ __forceinline__ void run_row_job(const lpi_row_job& q, int blk, RowstatGuard guard) {
     switch (q.op) {
-    case LPI_ROWOP_POOL_LN_FWD: {
-#define PLF(TX, TY) pool_ln_fwd_body<TX, TY>(blk, q.B, q.L, q.d, (const TX*)q.a, q.idx, q.gamma, q.beta, (TY*)q.out, q.ld_c, q.mean, q.rstd, (float*)q.out2)
-        if (q.dt_a == LPI_F32 && q.dt_b == LPI_F32) PLF(float, float);
-        else if (q.dt_a == LPI_F32 && q.dt_b == LPI_BF16) PLF(float, bf16_t);
-        else if (q.dt_a == LPI_F16 && q.dt_b == LPI_BF16) PLF(f16_t, bf16_t);
-        else if (q.dt_a == LPI_F32 && q.dt_b == LPI_F16) PLF(float, f16_t);
-        else PLF(f16_t, f16_t);
-#undef PLF
+    case LPI_ROWOP_POOL_LN_FWD:
+        dispatch_types(PoolLnFwdXY{}, [=](auto tx, auto ty) {
+            typedef type_of<decltype(tx)> TX; typedef type_of<decltype(ty)> TY;
+            pool_ln_fwd_body<TX, TY>(blk, q.B, q.L, q.d, (const TX*)q.a, q.idx, q.gamma, q.beta, (TY*)q.out, q.ld_c, q.mean, q.rstd, (float*)q.out2);
+        }, q.dt_a, q.dt_b);
         break;
-    }
     case LPI_ROWOP_L2NORM_FWD:
         l2norm_fwd_body(blk, q.B, q.d, (const float*)q.a, q.ld_a, (float*)q.out, q.ld_c, q.mean);
         break;
@@ -831,52 +855,49 @@ __device__ __forceinline__ void run_row_job(const lpi_row_job& q, int blk, Rowst
         l2norm_bwd_body(blk, q.B, q.d, (const float*)q.a, q.ld_a, (const float*)q.b, q.ld_b, q.mean_in, (float*)q.out, q.ld_c, (bf16_t*)q.out2);
         break;
     case LPI_ROWOP_POOL_LN_BWD:
-        if (q.dt_b == LPI_BF16) pool_ln_bwd_body<bf16_t>(blk, q.B, q.L, q.d, (const float*)q.a, q.ld_a, (const float*)q.b, q.idx, q.gamma, q.mean_in, q.rstd_in, (float*)q.out, (bf16_t*)q.out2);
-        else pool_ln_bwd_body<float>(blk, q.B, q.L, q.d, (const float*)q.a, q.ld_a, (const float*)q.b, q.idx, q.gamma, q.mean_in, q.rstd_in, (float*)q.out, (float*)q.out2);
+        dispatch_types(F32orBF16{}, [=](auto tc) {
+            typedef type_of<decltype(tc)> TC;
+            pool_ln_bwd_body<TC>(blk, q.B, q.L, q.d, (const float*)q.a, q.ld_a, (const float*)q.b, q.idx, q.gamma, q.mean_in, q.rstd_in, (float*)q.out, (TC*)q.out2);
+        }, q.dt_b);
         break;
-    case LPI_ROWOP_LN_BWD: {      // f32 x rows (the pooled rows of the last block); dy / cast in dt_a / dt_b
-#define LNBJ(TDY, TC, NC) ln_bwd_body<float, TDY, TC, NC>(blk, q.B, q.d, (const TDY*)q.a, q.ld_a, (const float*)q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, (float*)q.out, q.ld_c, (TC*)q.out2, q.ld_c, q.flag, 0, 0, 0, nullptr)
-        const int nc = (q.d + 255) / 256;
-        if (q.dt_a == LPI_BF16 && q.dt_b == LPI_BF16) { if (nc <= 1) LNBJ(bf16_t, bf16_t, 1); else if (nc == 2) LNBJ(bf16_t, bf16_t, 2); else if (nc == 3) LNBJ(bf16_t, bf16_t, 3); else if (nc == 4) LNBJ(bf16_t, bf16_t, 4); else LNBJ(bf16_t, bf16_t, 8); }
-        else { if (nc <= 1) LNBJ(float, float, 1); else if (nc == 2) LNBJ(float, float, 2); else if (nc == 3) LNBJ(float, float, 3); else if (nc == 4) LNBJ(float, float, 4); else LNBJ(float, float, 8); }
-#undef LNBJ
+    case LPI_ROWOP_LN_BWD:      // f32 x rows (the pooled rows of the last block); dy / cast in dt_a / dt_b
+        dispatch_types(LnBwdJobDyCast{}, [=](auto tdy, auto tc) {
+            typedef type_of<decltype(tdy)> TDY; typedef type_of<decltype(tc)> TC;
+            dispatch_nc<1, 2, 3, 4, 8>(q.d, [=](auto nc) {
+                ln_bwd_body<float, TDY, TC, nc>(blk, q.B, q.d, (const TDY*)q.a, q.ld_a, (const float*)q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, (float*)q.out, q.ld_c,
+                                                (TC*)q.out2, q.ld_c, q.flag, 0, 0, 0, nullptr);
+            });
+        }, q.dt_a, q.dt_b);
         break;
-    }
-    case LPI_ROWOP_SCATTER_ADD: {      // dst[b*L + idx[b], :] += src[b, :]: one block per sample (the arithmetic of scatter_add_rows_kernel, attn_pooled.hip)
-        const int b = blk;
-        if (b >= q.B) break;
-        const int row = q.idx ? q.idx[b] : 0;
-        auto body = [&](auto* o0, const auto* i0) {
-            typedef typename std::remove_const<typename std::remove_pointer<decltype(o0)>::type>::type T;
-            T* o = o0 + ((size_t)b * q.L + row) * q.ld_c;
-            const T* i = i0 + (size_t)b * q.ld_a;
-            for (int c = threadIdx.x * 4; c < q.d; c += 256 * 4) {
-                f32x4 a = Elem<T>::ld4(o + c), v = Elem<T>::ld4(i + c);
-                a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
-                Elem<T>::st4(o + c, a);
-            }
-        };
-        if (q.dt_a == LPI_BF16) body((bf16_t*)q.out, (const bf16_t*)q.a);
-        else body((float*)q.out, (const float*)q.a);
+    case LPI_ROWOP_SCATTER_ADD: {      // one block per sample: row blk of a onto row blk*L + idx[blk] of out
+        if (blk >= q.B) break;
+        const size_t row = (size_t)blk * q.L + (q.idx ? q.idx[blk] : 0);
+        dispatch_types(F32orBF16{}, [=](auto t) {
+            typedef type_of<decltype(t)> T;
+            scatter_add_body<T>(q.d, (const T*)q.a + (size_t)blk * q.ld_a, (T*)q.out + row * q.ld_c);
+        }, q.dt_a);
         break;
     }
     case LPI_ROWOP_GATHER_BATCH_ROWS:      // d = 16-byte chunks per row, ld_a / ld_c in 16-byte units
         gather_batch_rows_body(blk, q.B, q.L, q.row_start, q.row0, q.P, q.d, (const uint4*)q.a, q.ld_a, (uint4*)q.out, q.ld_c);
         break;
     case LPI_ROWOP_PROMPT_ADD:
-        if (q.dt_a == LPI_F16) prompt_add_body<f16_t>(blk, q.B, q.L, q.row_start, q.P, q.d, (f16_t*)q.out, (const float*)q.a, q.bstride, q.mean, q.rstd, guard);
-        else prompt_add_body<float>(blk, q.B, q.L, q.row_start, q.P, q.d, (float*)q.out, (const float*)q.a, q.bstride, q.mean, q.rstd, guard);
+        dispatch_types(F32orF16{}, [=](auto t) {
+            typedef type_of<decltype(t)> T;
+            prompt_add_body<T>(blk, q.B, q.L, q.row_start, q.P, q.d, (T*)q.out, (const float*)q.a, q.bstride, q.mean, q.rstd, guard);
+        }, q.dt_a);
         break;
-    case LPI_ROWOP_LN_BWD_ROWS_H16: {      // compact bf16 dy [B*P, d], fp16 x, bf16 gradient stream (in/out): ln_bwd_h16_kernel with the row map
-#define LNH(NC) ln_bwd_h16_body<NC>(blk, q.B * q.P, q.d, (const bf16_t*)q.a, q.ld_a, (const f16_t*)q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, (bf16_t*)q.out2, q.ld_c, q.flag, q.P, q.L, q.row0, q.row_start)
-        const int nc = (q.d + 255) / 256;
-        if (nc <= 1) LNH(1); else if (nc == 2) LNH(2); else if (nc == 3) LNH(3); else LNH(4);
-#undef LNH
+    case LPI_ROWOP_LN_BWD_ROWS_H16:      // compact bf16 dy [B*P, d], fp16 x, bf16 gradient stream (in/out): ln_bwd_h16_kernel with the row map
+        dispatch_nc<1, 2, 3, 4>(q.d, [=](auto nc) {
+            ln_bwd_h16_body<nc>(blk, q.B * q.P, q.d, (const bf16_t*)q.a, q.ld_a, (const f16_t*)q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, (bf16_t*)q.out2, q.ld_c, q.flag, q.P,
+                                q.L, q.row0, q.row_start);
+        });
         break;
-    }
     case LPI_ROWOP_VIS_PROMPT_ROWS_BWD:
-        if (q.dt_a == LPI_BF16) vis_prompt_rows_bwd_body<bf16_t>(blk, q.B, q.L, q.P, q.d, (bf16_t*)q.out, (const float*)q.a, q.bstride, q.gamma, q.mean_in, q.rstd_in);
-        else vis_prompt_rows_bwd_body<float>(blk, q.B, q.L, q.P, q.d, (float*)q.out, (const float*)q.a, q.bstride, q.gamma, q.mean_in, q.rstd_in);
+        dispatch_types(F32orBF16{}, [=](auto t) {
+            typedef type_of<decltype(t)> T;
+            vis_prompt_rows_bwd_body<T>(blk, q.B, q.L, q.P, q.d, (T*)q.out, (const float*)q.a, q.bstride, q.gamma, q.mean_in, q.rstd_in);
+        }, q.dt_a);
         break;
     default: break;
     }
@@ -899,18 +920,8 @@ inline int rows_grid(long rows) { return (int)((rows + 3) / 4); }
 
 #define S(stream) ((hipStream_t)(stream))
 
-// smallest instantiated chunk bound that covers d: ceil(d / 256) rounded up to one of 1, 2, 3, 4, 8
-#define LN_NC_SWITCH(d, CALL)                      \
-    do {                                           \
-        const int nc__ = ((d) + 255) / 256;        \
-        if (nc__ <= 1) { CALL(1); }                \
-        else if (nc__ == 2) { CALL(2); }           \
-        else if (nc__ == 3) { CALL(3); }           \
-        else if (nc__ == 4) { CALL(4); }           \
-        else { CALL(8); }                          \
-    } while (0)
-
-static int nc_of(int d) { const int n = (d + 255) / 256; return n <= 4 ? n : 0; }
+// the chunk bound of the half-wave pair kernels (1 .. 4), 0 if none covers d
+static int nc_of(int d) { int n = 0; dispatch_nc<1, 2, 3, 4>(d, [&](auto nc) { n = nc; }); return n; }
 static bool ln_h16_ok(int d, int ld0, int ld1, const void* p0, const void* p1) {
     return !(d & 7) && !(ld0 & 7) && !(ld1 & 7) && !(((uintptr_t)p0 | (uintptr_t)p1) & 15) && nc_of(d) != 0;
 }
@@ -933,44 +944,71 @@ static bool ln_bwd_args_ok(int dy_dtype, int cast_dtype, int x_dtype, int rows, 
     return row4_ok(dy, lddy, d, dy_dtype) && row4_ok(x, ldx, d, x_dtype) && al16(gamma) && (!dx || row4_ok(dx, lddx, d, LPI_F32)) &&
            (!dx_cast || row4_ok(dx_cast, ldcast, d, cast_dtype));
 }
+// which lpi_layernorm_bwd calls run the half-wave kernel: 2-byte operands, the bf16 gradient stream alone (no f32 dx), everything in 16-byte units
+static bool ln_bwd_is_h16(int dy_dtype, int cast_dtype, int x_dtype, int d, const void* dy, int lddy, const void* x, int ldx, const float* dx, const void* dx_cast, int ldcast) {
+    return x_dtype == LPI_F16 && dy_dtype == LPI_BF16 && cast_dtype == LPI_BF16 && !dx && !(d & 7) && !(lddy & 7) && !(ldx & 7) && !(ldcast & 7) &&
+           !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx_cast) & 15);
+}
+static bool batch_rows_ok(int B, int L, int row0, int P) { return B > 0 && L > 0 && P > 0 && row0 >= 0 && row0 + P <= L; }      // rows b*L + row0 + [0, P) of B samples
+// ---- ONE argument rule per op that is both an entry point and a row job (lpi_row_jobs): the entry point and row_job_blocks call the same predicate, and what
+// a job form adds to it is an explicit condition there.  (ln_bwd_args_ok above is the rule of LN_BWD and, with ln_bwd_is_h16, of LN_BWD_ROWS_H16.)
+static bool pool_ln_fwd_ok(int dtype, int x_dtype, int B, int L, int d, const void* x, const int32_t* idx, const float* gamma, const float* beta, const void* y, int ldy,
+                           const float* mean, const float* rstd) {
+    if (!x || !gamma || !beta || !y || !mean || !rstd || B <= 0 || L < 0 || (L == 0 && !idx) || bad_row_dim(d) || (ldy & 3)) return false;      // L == 0: idx holds absolute rows
+    return types_listed(PoolLnFwdXY{}, x_dtype, dtype) && row4_ok(x, d, d, x_dtype) && row4_ok(y, ldy, d, dtype) && al16(gamma) && al16(beta);
+}
+static bool pool_ln_bwd_ok(int cast_dtype, int B, int d, const float* dy, int lddy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dx,
+                           const void* dx_cast) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || B <= 0 || bad_row_dim(d) || (lddy & 3) || !types_listed(F32orBF16{}, cast_dtype)) return false;
+    return row4_ok(dy, lddy, d, LPI_F32) && al16(x) && al16(gamma) && al16(dx) && (!dx_cast || row4_ok(dx_cast, d, d, cast_dtype));
+}
+static bool l2norm_fwd_ok(int B, int E, const float* x, int ldx, const float* y, int ldy, const float* inv_norm) {
+    return x && y && inv_norm && B > 0 && !bad_row_dim(E) && row4_ok(x, ldx, E, LPI_F32) && row4_ok(y, ldy, E, LPI_F32);
+}
+static bool l2norm_bwd_ok(int B, int E, const float* y, int ldy, const float* dy, int lddy, const float* inv_norm, const float* dx, int lddx) {
+    return y && dy && inv_norm && dx && B > 0 && !bad_row_dim(E) && row4_ok(y, ldy, E, LPI_F32) && row4_ok(dy, lddy, E, LPI_F32) && row4_ok(dx, lddx, E, LPI_F32);
+}
+// without the dtype list: lpi_scatter_add_rows answers LPI_ENOSYS to an unlisted type, a job LPI_EINVAL
+static bool scatter_add_ok(int dtype, int B, int L, int d, const void* src, int ld_src, const int32_t* idx, const void* dst, int ld_dst) {
+    if (!src || !dst || B <= 0 || L < 0 || (L == 0 && !idx) || d <= 0 || (d & 3)) return false;      // L == 0: idx holds absolute rows
+    return row4_ok(src, ld_src, d, dtype) && row4_ok(dst, ld_dst, d, dtype);      // four elements at a time: 16 bytes of f32, 8 bytes of bf16
+}
+// in 16-byte units: chunks per row and the two row strides
+static bool gather_batch_rows_ok(int B, int L, int row0, int P, int chunks, const void* src, long ld_src, const void* dst, long ld_dst) {
+    return src && dst && B > 0 && P > 0 && row0 >= 0 && row0 + P <= L && chunks > 0 && ld_src >= chunks && ld_dst >= chunks && al16(src) && al16(dst);
+}
+static bool prompt_add_ok(int x_dtype, int B, int L, int P, int d, const void* x, const float* prompt_l, long prompt_bstride, const float* out_mean, const float* out_rstd) {
+    if ((out_mean != nullptr) != (out_rstd != nullptr)) return false;
+    if (!x || !prompt_l || B <= 0 || P <= 0 || P + 1 > L || bad_row_dim(d) || (prompt_bstride & 3)) return false;
+    return types_listed(F32orF16{}, x_dtype) && row4_ok(x, d, d, x_dtype) && al16(prompt_l);
+}
+static bool vis_prompt_rows_bwd_ok(int dtype, int B, int P, int d, const void* dx0, const float* prompt0, long prompt_bstride, const float* gamma, const float* mean,
+                                   const float* rstd) {
+    if (!dx0 || !prompt0 || !gamma || !mean || !rstd || B <= 0 || P <= 0 || bad_row_dim(d) || (prompt_bstride & 3)) return false;
+    return types_listed(F32orBF16{}, dtype) && row4_ok(dx0, d, d, dtype) && al16(prompt0) && al16(gamma);
+}
+
 extern "C" int lpi_layernorm_fwd(int dtype, int x_dtype, int rows, int d, const void* x, int ldx, const float* gamma, const float* beta,
                                  void* y, int ldy, float* mean, float* rstd, void* stream) {
-    if (!y) {      // statistics only (fp16 stream): mean / rstd of every row, nothing else written
-        if (!ln_fwd_args_ok(dtype, x_dtype, rows, d, x, ldx, gamma, beta, y, ldy, mean, rstd)) return LPI_EINVAL;
-#define LNS(NC) LPI_LAUNCH((ln_fwd_h16_kernel<NC, void>), dim3((rows + 7) / 8), dim3(256), 0, S(stream), rows, d, (const f16_t*)x, ldx, gamma, beta, (void*)nullptr, 0, mean, rstd)
-        LN_NC_SWITCH(d, LNS);
-#undef LNS
-        LPI_CHECK_LAST();
-        return 0;
-    }
     if (!ln_fwd_args_ok(dtype, x_dtype, rows, d, x, ldx, gamma, beta, y, ldy, mean, rstd)) return LPI_EINVAL;
-    dim3 g(rows_grid(rows)), b(256);
-#define LNF(TX, TY, NC) LPI_LAUNCH((ln_fwd_kernel<TX, TY, NC>), g, b, 0, S(stream), rows, d, (const TX*)x, ldx, gamma, beta, (TY*)y, ldy, mean, rstd)
-#define LNF_FF(NC) LNF(float, float, NC)
-#define LNF_FB(NC) LNF(float, bf16_t, NC)
-#define LNF_HB(NC) LNF(f16_t, bf16_t, NC)
-#define LNF_H16(NC) LPI_LAUNCH(ln_fwd_h16_kernel<NC>, dim3((rows + 7) / 8), b, 0, S(stream), rows, d, (const f16_t*)x, ldx, gamma, beta, (bf16_t*)y, ldy, mean, rstd)
-#define LNF_H16H(NC) LPI_LAUNCH((ln_fwd_h16_kernel<NC, f16_t>), dim3((rows + 7) / 8), b, 0, S(stream), rows, d, (const f16_t*)x, ldx, gamma, beta, (f16_t*)y, ldy, mean, rstd)
-#define LNF_HH(NC) LNF(f16_t, f16_t, NC)
-#define LNF_FH(NC) LNF(float, f16_t, NC)
-    if (dtype == LPI_F32 && x_dtype == LPI_F32) LN_NC_SWITCH(d, LNF_FF);
-    else if (dtype == LPI_F16 && x_dtype == LPI_F16 && !(d & 7) && !(ldx & 7) && !(ldy & 7) && !(((uintptr_t)x | (uintptr_t)y) & 15))
-        LN_NC_SWITCH(d, LNF_H16H);          // f16 operand mode: fp16 stream in, fp16 operand out
-    else if (dtype == LPI_F16 && x_dtype == LPI_F16) LN_NC_SWITCH(d, LNF_HH);
-    else if (dtype == LPI_F16 && x_dtype == LPI_F32) LN_NC_SWITCH(d, LNF_FH);
-    else if (dtype == LPI_BF16 && x_dtype == LPI_F32) LN_NC_SWITCH(d, LNF_FB);
-    else if (dtype == LPI_BF16 && x_dtype == LPI_F16 && !(d & 7) && !(ldx & 7) && !(ldy & 7) && !(((uintptr_t)x | (uintptr_t)y) & 15))
-        LN_NC_SWITCH(d, LNF_H16);
-    else if (dtype == LPI_BF16 && x_dtype == LPI_F16) LN_NC_SWITCH(d, LNF_HB);
-    else return LPI_EINVAL;
-#undef LNF
-#undef LNF_FF
-#undef LNF_FB
-#undef LNF_HB
-#undef LNF_H16
-#undef LNF_H16H
-#undef LNF_HH
-#undef LNF_FH
+    // the half-wave kernel (fp16 stream in, 16-byte accesses): TY = void is the statistics only, mean / rstd of every row and nothing else written
+    auto h16 = [&](auto ty) {
+        typedef type_of<decltype(ty)> TY;
+        dispatch_nc<1, 2, 3, 4, 8>(d, [&](auto nc) {
+            LPI_LAUNCH((ln_fwd_h16_kernel<nc, TY>), dim3((rows + 7) / 8), dim3(256), 0, S(stream), rows, d, (const f16_t*)x, ldx, gamma, beta, (TY*)y, ldy, mean, rstd);
+        });
+    };
+    const bool half = x_dtype == LPI_F16 && !(d & 7) && !(ldx & 7) && !(ldy & 7) && !(((uintptr_t)x | (uintptr_t)y) & 15);
+    if (!y) h16(Tag<void>{});
+    else if (half && dtype == LPI_F16) h16(Tag<f16_t>{});          // f16 operand mode: fp16 stream in, fp16 operand out
+    else if (half && dtype == LPI_BF16) h16(Tag<bf16_t>{});
+    else if (!dispatch_types(TypeList<Types<float, float>, Types<f16_t, f16_t>, Types<float, f16_t>, Types<float, bf16_t>, Types<f16_t, bf16_t>>{}, [&](auto tx, auto ty) {
+                 typedef type_of<decltype(tx)> TX; typedef type_of<decltype(ty)> TY;
+                 dispatch_nc<1, 2, 3, 4, 8>(d, [&](auto nc) {
+                     LPI_LAUNCH((ln_fwd_kernel<TX, TY, nc>), dim3(rows_grid(rows)), dim3(256), 0, S(stream), rows, d, (const TX*)x, ldx, gamma, beta, (TY*)y, ldy, mean, rstd);
+                 });
+             }, x_dtype, dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -979,33 +1017,20 @@ static int ln_bwd_impl(int dy_dtype, int cast_dtype, int x_dtype, int rows, int 
                        const float* gamma, const float* mean, const float* rstd, float* dx, int lddx, void* dx_cast,
                        int ldcast, int accumulate, int mapP, int mapL, int map0, const int* map_rs, void* stream) {
     if (!ln_bwd_args_ok(dy_dtype, cast_dtype, x_dtype, rows, d, dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, dx_cast, ldcast)) return LPI_EINVAL;
-    dim3 g(rows_grid(rows)), b(256);
-#define LNB(TX, TDY, TC, NC) LPI_LAUNCH((ln_bwd_kernel<TX, TDY, TC, NC>), g, b, 0, S(stream), rows, d, (const TDY*)dy, lddy, (const TX*)x, ldx, gamma, mean, rstd, dx, lddx, (TC*)dx_cast, ldcast, accumulate, mapP, mapL, map0, map_rs)
-#define LNB_HBB(NC) LNB(f16_t, bf16_t, bf16_t, NC)
-#define LNB_FFF(NC) LNB(float, float, float, NC)
-#define LNB_FFB(NC) LNB(float, float, bf16_t, NC)
-#define LNB_FBB(NC) LNB(float, bf16_t, bf16_t, NC)
-#define LNB_FBF(NC) LNB(float, bf16_t, float, NC)
-#define LNB_H16(NC) LPI_LAUNCH(ln_bwd_h16_kernel<NC>, dim3((rows + 7) / 8), b, 0, S(stream), rows, d, (const bf16_t*)dy, lddy, (const f16_t*)x, ldx, gamma, mean, rstd, (bf16_t*)dx_cast, ldcast, accumulate, mapP, mapL, map0, map_rs)
-    if (x_dtype == LPI_F16) {
-        if (dy_dtype == LPI_BF16 && cast_dtype == LPI_BF16 && !dx && !(d & 7) && !(lddy & 7) && !(ldx & 7) && !(ldcast & 7) &&
-            !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx_cast) & 15))
-            LN_NC_SWITCH(d, LNB_H16);
-        else if (dy_dtype == LPI_BF16 && cast_dtype == LPI_BF16) LN_NC_SWITCH(d, LNB_HBB);
-        else return LPI_EINVAL;
-    } else if (x_dtype != LPI_F32) return LPI_EINVAL;
-    else if (dy_dtype == LPI_F32 && cast_dtype == LPI_F32) LN_NC_SWITCH(d, LNB_FFF);
-    else if (dy_dtype == LPI_F32 && cast_dtype == LPI_BF16) LN_NC_SWITCH(d, LNB_FFB);
-    else if (dy_dtype == LPI_BF16 && cast_dtype == LPI_BF16) LN_NC_SWITCH(d, LNB_FBB);
-    else if (dy_dtype == LPI_BF16 && cast_dtype == LPI_F32) LN_NC_SWITCH(d, LNB_FBF);
-    else return LPI_EINVAL;
-#undef LNB
-#undef LNB_HBB
-#undef LNB_FFF
-#undef LNB_FFB
-#undef LNB_FBB
-#undef LNB_FBF
-#undef LNB_H16
+    if (ln_bwd_is_h16(dy_dtype, cast_dtype, x_dtype, d, dy, lddy, x, ldx, dx, dx_cast, ldcast))
+        dispatch_nc<1, 2, 3, 4, 8>(d, [&](auto nc) {
+            LPI_LAUNCH(ln_bwd_h16_kernel<nc>, dim3((rows + 7) / 8), dim3(256), 0, S(stream), rows, d, (const bf16_t*)dy, lddy, (const f16_t*)x, ldx, gamma, mean, rstd,
+                       (bf16_t*)dx_cast, ldcast, accumulate, mapP, mapL, map0, map_rs);
+        });
+    else if (!dispatch_types(TypeList<Types<f16_t, bf16_t, bf16_t>, Types<float, float, float>, Types<float, float, bf16_t>, Types<float, bf16_t, bf16_t>,
+                                      Types<float, bf16_t, float>>{}, [&](auto tx, auto tdy, auto tc) {
+                 typedef type_of<decltype(tx)> TX; typedef type_of<decltype(tdy)> TDY; typedef type_of<decltype(tc)> TC;
+                 dispatch_nc<1, 2, 3, 4, 8>(d, [&](auto nc) {
+                     LPI_LAUNCH((ln_bwd_kernel<TX, TDY, TC, nc>), dim3(rows_grid(rows)), dim3(256), 0, S(stream), rows, d, (const TDY*)dy, lddy, (const TX*)x, ldx, gamma, mean,
+                                rstd, dx, lddx, (TC*)dx_cast, ldcast, accumulate, mapP, mapL, map0, map_rs);
+                 });
+             }, x_dtype, dy_dtype, cast_dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1022,7 +1047,7 @@ extern "C" int lpi_layernorm_bwd(int dy_dtype, int cast_dtype, int x_dtype, int 
 extern "C" int lpi_layernorm_bwd_rows_varlen(int dy_dtype, int cast_dtype, int x_dtype, int B, int L, const int32_t* row_start, int row0, int P, int d,
                                              const void* dy, int lddy, const void* x, int ldx, const float* gamma, const float* mean, const float* rstd,
                                              float* dx, int lddx, void* dx_cast, int ldcast, int accumulate, void* stream) {
-    if (B <= 0 || L <= 0 || P <= 0 || row0 < 0 || row0 + P > L) return LPI_EINVAL;
+    if (!batch_rows_ok(B, L, row0, P)) return LPI_EINVAL;
     return ln_bwd_impl(dy_dtype, cast_dtype, x_dtype, B * P, d, dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, dx_cast, ldcast, accumulate, P, L, row0,
                        row_start, stream);
 }
@@ -1037,45 +1062,21 @@ extern "C" int lpi_layernorm_bwd_rows(int dy_dtype, int cast_dtype, int x_dtype,
 template <typename TY>
 static int ln_fwd_pair_launch(const LnFwdP& a, const LnFwdP& b, hipStream_t s) {
     const int nb0 = (a.rows + 7) / 8, nb1 = (b.rows + 7) / 8;
-    const int n0 = nc_of(a.d), n1 = nc_of(b.d);
-#define LNP(A, B) LPI_LAUNCH((ln_fwd_h16_pair_kernel<A, B, TY>), dim3(nb0 + nb1), dim3(256), 0, s, a, b, nb0); LPI_CHECK_LAST(); return 0
-    switch (n0 * 8 + n1) {
-    case 1 * 8 + 1: LNP(1, 1);
-    case 2 * 8 + 1: LNP(2, 1);
-    case 2 * 8 + 2: LNP(2, 2);
-    case 3 * 8 + 1: LNP(3, 1);
-    case 3 * 8 + 2: LNP(3, 2);
-    case 3 * 8 + 3: LNP(3, 3);
-    case 4 * 8 + 1: LNP(4, 1);
-    case 4 * 8 + 2: LNP(4, 2);
-    case 4 * 8 + 3: LNP(4, 3);
-    case 4 * 8 + 4: LNP(4, 4);
-    }
-#undef LNP
-    return LPI_ENOSYS;
+    if (!dispatch_nc_pair<1, 2, 3, 4>(a.d, b.d, [&](auto n0, auto n1) {
+            LPI_LAUNCH((ln_fwd_h16_pair_kernel<n0, n1, TY>), dim3(nb0 + nb1), dim3(256), 0, s, a, b, nb0);
+        }))
+        return LPI_ENOSYS;
+    LPI_CHECK_LAST();
+    return 0;
 }
 extern "C" int lpi_layernorm_fwd_pair(int dtype, int x_dtype, const lpi_ln_fwd_desc* d, void* stream) {
     if (!d) return LPI_EINVAL;
-    if (!d[0].y && !d[1].y) {      // statistics only, both problems (y = NULL): see lpi_layernorm_fwd
-        for (int i = 0; i < 2; ++i)
-            if (!ln_fwd_args_ok(dtype, x_dtype, d[i].rows, d[i].d, d[i].x, d[i].ldx, d[i].gamma, d[i].beta, nullptr, 0, d[i].mean, d[i].rstd)) return LPI_EINVAL;
-        const int o = nc_of(d[0].d) >= nc_of(d[1].d) ? 0 : 1;
-        LnFwdP p[2];
-        for (int i = 0; i < 2; ++i) {
-            const lpi_ln_fwd_desc& q = d[i ^ o];
-            p[i] = LnFwdP{q.rows, q.d, q.ldx, 0, (const f16_t*)q.x, q.gamma, q.beta, nullptr, q.mean, q.rstd};
-        }
-        const int rc = ln_fwd_pair_launch<void>(p[0], p[1], S(stream));
-        if (rc != LPI_ENOSYS) return rc;
-        for (int i = 0; i < 2; ++i)
-            if (int e = lpi_layernorm_fwd(dtype, x_dtype, d[i].rows, d[i].d, d[i].x, d[i].ldx, d[i].gamma, d[i].beta, nullptr, 0, d[i].mean, d[i].rstd, stream)) return e;
-        return 0;
-    }
+    const bool stats = !d[0].y && !d[1].y;      // statistics only, both problems (y = NULL, ldy unused): see lpi_layernorm_fwd; its rule includes the half-wave kernel's
     for (int i = 0; i < 2; ++i)
-        if (!d[i].y || !ln_fwd_args_ok(dtype, x_dtype, d[i].rows, d[i].d, d[i].x, d[i].ldx, d[i].gamma, d[i].beta, d[i].y, d[i].ldy, d[i].mean, d[i].rstd))
+        if ((!stats && !d[i].y) || !ln_fwd_args_ok(dtype, x_dtype, d[i].rows, d[i].d, d[i].x, d[i].ldx, d[i].gamma, d[i].beta, d[i].y, d[i].ldy, d[i].mean, d[i].rstd))
             return LPI_EINVAL;      // both problems are checked before the first launch (a pair off the fused path is two launches)
-    const bool fast = x_dtype == LPI_F16 && (dtype == LPI_BF16 || dtype == LPI_F16) && ln_h16_ok(d[0].d, d[0].ldx, d[0].ldy, d[0].x, d[0].y) &&
-                      ln_h16_ok(d[1].d, d[1].ldx, d[1].ldy, d[1].x, d[1].y);
+    const bool fast = stats || (x_dtype == LPI_F16 && (dtype == LPI_BF16 || dtype == LPI_F16) && ln_h16_ok(d[0].d, d[0].ldx, d[0].ldy, d[0].x, d[0].y) &&
+                                ln_h16_ok(d[1].d, d[1].ldx, d[1].ldy, d[1].x, d[1].y));
     if (fast) {
         const int o = nc_of(d[0].d) >= nc_of(d[1].d) ? 0 : 1;      // the wider row first (the instantiated pairs have NC0 >= NC1)
         LnFwdP p[2];
@@ -1083,7 +1084,8 @@ extern "C" int lpi_layernorm_fwd_pair(int dtype, int x_dtype, const lpi_ln_fwd_d
             const lpi_ln_fwd_desc& q = d[i ^ o];
             p[i] = LnFwdP{q.rows, q.d, q.ldx, q.ldy, (const f16_t*)q.x, q.gamma, q.beta, q.y, q.mean, q.rstd};
         }
-        const int rc = dtype == LPI_BF16 ? ln_fwd_pair_launch<bf16_t>(p[0], p[1], S(stream)) : ln_fwd_pair_launch<f16_t>(p[0], p[1], S(stream));
+        const int rc = stats ? ln_fwd_pair_launch<void>(p[0], p[1], S(stream))
+                             : dtype == LPI_BF16 ? ln_fwd_pair_launch<bf16_t>(p[0], p[1], S(stream)) : ln_fwd_pair_launch<f16_t>(p[0], p[1], S(stream));
         if (rc != LPI_ENOSYS) return rc;
     }
     for (int i = 0; i < 2; ++i)
@@ -1093,22 +1095,12 @@ extern "C" int lpi_layernorm_fwd_pair(int dtype, int x_dtype, const lpi_ln_fwd_d
 }
 static int ln_bwd_pair_launch(const LnBwdP& a, const LnBwdP& b, hipStream_t s) {
     const int nb0 = (a.rows + 7) / 8, nb1 = (b.rows + 7) / 8;
-    const int n0 = nc_of(a.d), n1 = nc_of(b.d);
-#define LNP(A, B) LPI_LAUNCH((ln_bwd_h16_pair_kernel<A, B>), dim3(nb0 + nb1), dim3(256), 0, s, a, b, nb0); LPI_CHECK_LAST(); return 0
-    switch (n0 * 8 + n1) {
-    case 1 * 8 + 1: LNP(1, 1);
-    case 2 * 8 + 1: LNP(2, 1);
-    case 2 * 8 + 2: LNP(2, 2);
-    case 3 * 8 + 1: LNP(3, 1);
-    case 3 * 8 + 2: LNP(3, 2);
-    case 3 * 8 + 3: LNP(3, 3);
-    case 4 * 8 + 1: LNP(4, 1);
-    case 4 * 8 + 2: LNP(4, 2);
-    case 4 * 8 + 3: LNP(4, 3);
-    case 4 * 8 + 4: LNP(4, 4);
-    }
-#undef LNP
-    return LPI_ENOSYS;
+    if (!dispatch_nc_pair<1, 2, 3, 4>(a.d, b.d, [&](auto n0, auto n1) {
+            LPI_LAUNCH((ln_bwd_h16_pair_kernel<n0, n1>), dim3(nb0 + nb1), dim3(256), 0, s, a, b, nb0);
+        }))
+        return LPI_ENOSYS;
+    LPI_CHECK_LAST();
+    return 0;
 }
 extern "C" int lpi_layernorm_bwd_pair(int dy_dtype, int cast_dtype, int x_dtype, const lpi_ln_bwd_desc* d, void* stream) {
     if (!d) return LPI_EINVAL;
@@ -1136,42 +1128,39 @@ extern "C" int lpi_layernorm_bwd_pair(int dy_dtype, int cast_dtype, int x_dtype,
     return 0;
 }
 
+// the shared prologue of the two patchify entry points: the padded row width Kp (K rounded up to 128 bytes of dtype) and the grid, one thread per four columns;
+// false = refuse (the callers have checked B > 0, ps > 0, R % ps == 0 and their image pointer)
+static bool patchify_shape(int dtype, int B, int R, int ps, const void* cols, int ldcols, int& G, int& Kp, dim3& grid) {
+    G = R / ps;
+    const int K = 3 * ps * ps, bk = 128 / esz_of(dtype);
+    Kp = (K + bk - 1) / bk * bk;
+    if (!types_listed(AnyElem{}, dtype) || !row4_ok(cols, ldcols, Kp, dtype)) return false;
+    grid = dim3((unsigned)(((long)B * G * G * (Kp >> 2) + 255) / 256));
+    return true;
+}
 extern "C" int lpi_patchify(int dtype, int B, int R, int ps, const float* image, void* cols, int ldcols, void* stream) {
-    if (!image || !cols || B <= 0 || ps <= 0 || R % ps) return LPI_EINVAL;
-    const int G = R / ps, K = 3 * ps * ps;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    const int bk = 128 / esz;
-    const int Kp = (K + bk - 1) / bk * bk;
-    if (dtype != LPI_F32 && dtype != LPI_BF16 && dtype != LPI_F16) return LPI_EINVAL;
-    if (!row4_ok(cols, ldcols, Kp, dtype)) return LPI_EINVAL;
-    const long total = (long)B * G * G * (Kp >> 2);
-    dim3 g((unsigned)((total + 255) / 256)), b(256);
+    int G, Kp;
+    dim3 g;
+    if (!image || !cols || B <= 0 || ps <= 0 || R % ps || !patchify_shape(dtype, B, R, ps, cols, ldcols, G, Kp, g)) return LPI_EINVAL;
     const bool vec4 = (ps & 3) == 0 && (R & 3) == 0 && ((uintptr_t)image & 15) == 0;
-#define PATCHIFY(T) do { if (vec4) LPI_LAUNCH((patchify_kernel<T, true>), g, b, 0, S(stream), B, R, ps, G, Kp, image, (T*)cols, ldcols); \
-                         else LPI_LAUNCH((patchify_kernel<T, false>), g, b, 0, S(stream), B, R, ps, G, Kp, image, (T*)cols, ldcols); } while (0)
-    if (dtype == LPI_F32) PATCHIFY(float);
-    else if (dtype == LPI_BF16) PATCHIFY(bf16_t);
-    else if (dtype == LPI_F16) PATCHIFY(f16_t);
-    else return LPI_EINVAL;
-#undef PATCHIFY
+    dispatch_types(AnyElem{}, [&](auto t) {
+        typedef type_of<decltype(t)> T;
+        auto launch = [&](auto v4) { LPI_LAUNCH((patchify_kernel<T, v4>), g, dim3(256), 0, S(stream), B, R, ps, G, Kp, image, (T*)cols, ldcols); };
+        if (vec4) launch(std::true_type{}); else launch(std::false_type{});
+    }, dtype);
     LPI_CHECK_LAST();
     return 0;
 }
 
 extern "C" int lpi_patchify_u8(int dtype, int B, int R, int ps, const uint8_t* image, const float* lut, void* cols, int ldcols, void* stream) {
-    if (!image || !lut || !cols || B <= 0 || ps <= 0 || R % ps || (ps & 3) || (R & 3) || ((uintptr_t)image & 3)) return LPI_EINVAL;
-    const int G = R / ps, K = 3 * ps * ps;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    const int bk = 128 / esz;
-    const int Kp = (K + bk - 1) / bk * bk;
-    if (dtype != LPI_F32 && dtype != LPI_BF16 && dtype != LPI_F16) return LPI_EINVAL;
-    if (!row4_ok(cols, ldcols, Kp, dtype)) return LPI_EINVAL;
-    const long total = (long)B * G * G * (Kp >> 2);
-    dim3 g((unsigned)((total + 255) / 256)), b(256);
-    if (dtype == LPI_F32) LPI_LAUNCH(patchify_u8_kernel<float>, g, b, 0, S(stream), B, R, ps, G, Kp, image, lut, (float*)cols, ldcols);
-    else if (dtype == LPI_BF16) LPI_LAUNCH(patchify_u8_kernel<bf16_t>, g, b, 0, S(stream), B, R, ps, G, Kp, image, lut, (bf16_t*)cols, ldcols);
-    else if (dtype == LPI_F16) LPI_LAUNCH(patchify_u8_kernel<f16_t>, g, b, 0, S(stream), B, R, ps, G, Kp, image, lut, (f16_t*)cols, ldcols);
-    else return LPI_EINVAL;
+    int G, Kp;
+    dim3 g;
+    if (!image || !lut || !cols || B <= 0 || ps <= 0 || R % ps || (ps & 3) || (R & 3) || ((uintptr_t)image & 3) || !patchify_shape(dtype, B, R, ps, cols, ldcols, G, Kp, g))
+        return LPI_EINVAL;
+    dispatch_types(AnyElem{}, [&](auto t) {
+        typedef type_of<decltype(t)> T;
+        LPI_LAUNCH(patchify_u8_kernel<T>, g, dim3(256), 0, S(stream), B, R, ps, G, Kp, image, lut, (T*)cols, ldcols);
+    }, dtype);
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1183,30 +1172,28 @@ extern "C" int lpi_vis_assemble_fwd(int x_dtype, int B, int G2, int P, int d, co
     if (!patch_emb || !cls || !pos || !gamma || !beta || !x0 || !mean || !rstd || B <= 0 || G2 <= 0 || P < 0 || bad_row_dim(d) || (ldpe & 3))
         return LPI_EINVAL;
     if (P > 0 && (!prompt0 || (prompt_bstride & 3) || !al16(prompt0))) return LPI_EINVAL;
-    if (x_dtype != LPI_F32 && x_dtype != LPI_F16) return LPI_EINVAL;
+    if (!types_listed(F32orF16{}, x_dtype)) return LPI_EINVAL;
     if (!row4_ok(patch_emb, ldpe, d, LPI_F32) || !al16(cls) || !al16(pos) || !al16(gamma) || !al16(beta) || !row4_ok(x0, d, d, x_dtype)) return LPI_EINVAL;
     const long rows = (long)B * (1 + P + G2);
-    if (x_dtype == LPI_F32)
-        LPI_LAUNCH(vis_assemble_fwd_kernel<float>, dim3(rows_grid(rows)), dim3(256), 0, S(stream), B, G2, P, d, patch_emb, ldpe, cls, pos,
-                   prompt0, prompt_bstride, gamma, beta, (float*)x0, mean, rstd, out_mean, out_rstd, t_rowstat_guard);
-    else if (x_dtype == LPI_F16)
-        LPI_LAUNCH(vis_assemble_fwd_kernel<f16_t>, dim3(rows_grid(rows)), dim3(256), 0, S(stream), B, G2, P, d, patch_emb, ldpe, cls, pos,
-                   prompt0, prompt_bstride, gamma, beta, (f16_t*)x0, mean, rstd, out_mean, out_rstd, t_rowstat_guard);
-    else
-        return LPI_EINVAL;
+    dispatch_types(F32orF16{}, [&](auto t) {
+        typedef type_of<decltype(t)> T;
+        LPI_LAUNCH(vis_assemble_fwd_kernel<T>, dim3(rows_grid(rows)), dim3(256), 0, S(stream), B, G2, P, d, patch_emb, ldpe, cls, pos, prompt0, prompt_bstride, gamma, beta,
+                   (T*)x0, mean, rstd, out_mean, out_rstd, t_rowstat_guard);
+    }, x_dtype);
     LPI_CHECK_LAST();
     return 0;
 }
 
 extern "C" int lpi_gather_batch_rows_varlen(int dtype, int B, int L, const int32_t* row_start, int row0, int P, int cols, const void* src, int ld_src,
                                             void* dst, int ld_dst, void* stream) {
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if (!src || !dst || B <= 0 || P <= 0 || row0 < 0 || row0 + P > L || cols <= 0 || ld_src < cols || ld_dst < cols) return LPI_EINVAL;
-    if ((cols * esz) % 16 || (ld_src * esz) % 16 || (ld_dst * esz) % 16 || (((uintptr_t)src | (uintptr_t)dst) & 15)) return LPI_EINVAL;
+    const int esz = esz_of(dtype);      // the rule is in 16-byte units (a job's own): whole units here, then the shared predicate
+    if ((cols * esz) % 16 || (ld_src * esz) % 16 || (ld_dst * esz) % 16) return LPI_EINVAL;
     const int chunks = cols * esz / 16;
+    const long lds16 = (long)ld_src * esz / 16, ldd16 = (long)ld_dst * esz / 16;
+    if (!gather_batch_rows_ok(B, L, row0, P, chunks, src, lds16, dst, ldd16)) return LPI_EINVAL;
     const long n = (long)B * P * chunks;
-    LPI_LAUNCH(gather_batch_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), B, L, row_start, row0, P, chunks, (const uint4*)src,
-               (long)ld_src * esz / 16, (uint4*)dst, (long)ld_dst * esz / 16);
+    LPI_LAUNCH(gather_batch_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), B, L, row_start, row0, P, chunks, (const uint4*)src, lds16, (uint4*)dst,
+               ldd16);
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1218,9 +1205,11 @@ extern "C" int lpi_gather_batch_rows(int dtype, int B, int L, int row0, int P, i
 extern "C" int lpi_rows_sum_over_batch_varlen(int dtype, int B, int L, const int32_t* row_start, int row0, int P, int d, const void* dx, float* out,
                                               int accumulate, void* stream) {
     if (!dx || !out || B <= 0 || P <= 0 || row0 < 0 || row0 + P > L || bad_row_dim(d)) return LPI_EINVAL;
-    if (dtype == LPI_F32) LPI_LAUNCH(rows_sum_kernel<float>, dim3(P, (d + 255) / 256), dim3(1024), 0, S(stream), B, L, row_start, row0, P, d, (const float*)dx, out, accumulate);
-    else if (dtype == LPI_BF16) LPI_LAUNCH(rows_sum_kernel<bf16_t>, dim3(P, (d + 255) / 256), dim3(1024), 0, S(stream), B, L, row_start, row0, P, d, (const bf16_t*)dx, out, accumulate);
-    else return LPI_EINVAL;
+    if (!dispatch_types(F32orBF16{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH(rows_sum_kernel<T>, dim3(P, (d + 255) / 256), dim3(1024), 0, S(stream), B, L, row_start, row0, P, d, (const T*)dx, out, accumulate);
+        }, dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1230,13 +1219,12 @@ extern "C" int lpi_rows_sum_over_batch(int dtype, int B, int L, int row0, int P,
 
 extern "C" int lpi_vis_assemble_bwd(int dtype, int B, int G2, int P, int d, void* dx0, const float* prompt0, long prompt_bstride,
                                     const float* gamma, const float* mean, const float* rstd, float* dprompt, void* stream) {
-    if (!dx0 || !prompt0 || !gamma || !mean || !rstd || !dprompt || B <= 0 || P <= 0 || bad_row_dim(d) || (prompt_bstride & 3)) return LPI_EINVAL;
-    if ((dtype != LPI_F32 && dtype != LPI_BF16) || !row4_ok(dx0, d, d, dtype) || !al16(prompt0) || !al16(gamma) || !al16(dprompt)) return LPI_EINVAL;
+    if (!vis_prompt_rows_bwd_ok(dtype, B, P, d, dx0, prompt0, prompt_bstride, gamma, mean, rstd) || !dprompt || !al16(dprompt)) return LPI_EINVAL;      // dprompt: the sum below
     const int L = 1 + P + G2;
-    dim3 g(rows_grid((long)B * P)), bl(256);
-    if (dtype == LPI_F32) LPI_LAUNCH(vis_prompt_rows_bwd_kernel<float>, g, bl, 0, S(stream), B, L, P, d, (float*)dx0, prompt0, prompt_bstride, gamma, mean, rstd);
-    else if (dtype == LPI_BF16) LPI_LAUNCH(vis_prompt_rows_bwd_kernel<bf16_t>, g, bl, 0, S(stream), B, L, P, d, (bf16_t*)dx0, prompt0, prompt_bstride, gamma, mean, rstd);
-    else return LPI_EINVAL;
+    dispatch_types(F32orBF16{}, [&](auto t) {
+        typedef type_of<decltype(t)> T;
+        LPI_LAUNCH(vis_prompt_rows_bwd_kernel<T>, dim3(rows_grid((long)B * P)), dim3(256), 0, S(stream), B, L, P, d, (T*)dx0, prompt0, prompt_bstride, gamma, mean, rstd);
+    }, dtype);
     LPI_CHECK_LAST();
     return lpi_rows_sum_over_batch(dtype, B, L, 1, P, d, dx0, dprompt, 0, stream);
 }
@@ -1253,11 +1241,11 @@ static int txt_embed_launch(int x_dtype, int B, int L, const int32_t* row_start,
                             const float* ctx, long ctx_bstride, void* x0, float* out_mean, float* out_rstd, void* stream) {
     if ((out_mean != nullptr) != (out_rstd != nullptr)) return LPI_EINVAL;
     if (!ids || !tok_emb || !pos || !x0 || B <= 0 || L <= 0 || P < 0 || P + 1 > L || bad_row_dim(d) || (ctx_bstride & 3)) return LPI_EINVAL;
-    if (x_dtype == LPI_F32)
-        LPI_LAUNCH(txt_embed_kernel<float>, dim3(rows_grid((long)B * L)), dim3(256), 0, S(stream), B, L, row_start, P, d, ids, tok_emb, pos, ctx, ctx_bstride, (float*)x0, out_mean, out_rstd, t_rowstat_guard, pre);
-    else if (x_dtype == LPI_F16)
-        LPI_LAUNCH(txt_embed_kernel<f16_t>, dim3(rows_grid((long)B * L)), dim3(256), 0, S(stream), B, L, row_start, P, d, ids, tok_emb, pos, ctx, ctx_bstride, (f16_t*)x0, out_mean, out_rstd, t_rowstat_guard, pre);
-    else
+    if (!dispatch_types(F32orF16{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH(txt_embed_kernel<T>, dim3(rows_grid((long)B * L)), dim3(256), 0, S(stream), B, L, row_start, P, d, ids, tok_emb, pos, ctx, ctx_bstride, (T*)x0, out_mean,
+                       out_rstd, t_rowstat_guard, pre);
+        }, x_dtype))
         return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
@@ -1273,15 +1261,12 @@ extern "C" int lpi_txt_embed_fwd(int x_dtype, int B, int L, int P, int d, const 
 
 extern "C" int lpi_prompt_add_varlen(int x_dtype, int B, int L, const int32_t* row_start, int P, int d, void* x, const float* prompt_l, long prompt_bstride,
                                      float* out_mean, float* out_rstd, void* stream) {
-    if ((out_mean != nullptr) != (out_rstd != nullptr)) return LPI_EINVAL;
-    if (!x || !prompt_l || B <= 0 || P <= 0 || P + 1 > L || bad_row_dim(d) || (prompt_bstride & 3)) return LPI_EINVAL;
-    if ((x_dtype != LPI_F32 && x_dtype != LPI_F16) || !row4_ok(x, d, d, x_dtype) || !al16(prompt_l)) return LPI_EINVAL;
-    if (x_dtype == LPI_F32)
-        LPI_LAUNCH(prompt_add_kernel<float>, dim3(rows_grid((long)B * P)), dim3(256), 0, S(stream), B, L, row_start, P, d, (float*)x, prompt_l, prompt_bstride, out_mean, out_rstd, t_rowstat_guard);
-    else if (x_dtype == LPI_F16)
-        LPI_LAUNCH(prompt_add_kernel<f16_t>, dim3(rows_grid((long)B * P)), dim3(256), 0, S(stream), B, L, row_start, P, d, (f16_t*)x, prompt_l, prompt_bstride, out_mean, out_rstd, t_rowstat_guard);
-    else
-        return LPI_EINVAL;
+    if (!prompt_add_ok(x_dtype, B, L, P, d, x, prompt_l, prompt_bstride, out_mean, out_rstd)) return LPI_EINVAL;
+    dispatch_types(F32orF16{}, [&](auto t) {
+        typedef type_of<decltype(t)> T;
+        LPI_LAUNCH(prompt_add_kernel<T>, dim3(rows_grid((long)B * P)), dim3(256), 0, S(stream), B, L, row_start, P, d, (T*)x, prompt_l, prompt_bstride, out_mean, out_rstd,
+                   t_rowstat_guard);
+    }, x_dtype);
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1292,41 +1277,33 @@ extern "C" int lpi_prompt_add(int x_dtype, int B, int L, int P, int d, void* x, 
 
 extern "C" int lpi_pool_ln_fwd(int dtype, int x_dtype, int B, int L, int d, const void* x, const int32_t* idx, const float* gamma, const float* beta,
                                void* y, int ldy, float* mean, float* rstd, void* stream) {
-    if (!x || !gamma || !beta || !y || !mean || !rstd || B <= 0 || L < 0 || (L == 0 && !idx) || bad_row_dim(d) || (ldy & 3)) return LPI_EINVAL;      // L == 0: idx holds absolute rows
-    if (!row4_ok(x, d, d, x_dtype) || !row4_ok(y, ldy, d, dtype) || !al16(gamma) || !al16(beta)) return LPI_EINVAL;
-    dim3 g(rows_grid(B)), b(256);
-    if (dtype == LPI_F32 && x_dtype == LPI_F32)
-        LPI_LAUNCH((pool_ln_fwd_kernel<float, float>), g, b, 0, S(stream), B, L, d, (const float*)x, idx, gamma, beta, (float*)y, ldy, mean, rstd);
-    else if (dtype == LPI_BF16 && x_dtype == LPI_F32)
-        LPI_LAUNCH((pool_ln_fwd_kernel<float, bf16_t>), g, b, 0, S(stream), B, L, d, (const float*)x, idx, gamma, beta, (bf16_t*)y, ldy, mean, rstd);
-    else if (dtype == LPI_BF16 && x_dtype == LPI_F16)
-        LPI_LAUNCH((pool_ln_fwd_kernel<f16_t, bf16_t>), g, b, 0, S(stream), B, L, d, (const f16_t*)x, idx, gamma, beta, (bf16_t*)y, ldy, mean, rstd);
-    else if (dtype == LPI_F16 && x_dtype == LPI_F32)
-        LPI_LAUNCH((pool_ln_fwd_kernel<float, f16_t>), g, b, 0, S(stream), B, L, d, (const float*)x, idx, gamma, beta, (f16_t*)y, ldy, mean, rstd);
-    else if (dtype == LPI_F16 && x_dtype == LPI_F16)
-        LPI_LAUNCH((pool_ln_fwd_kernel<f16_t, f16_t>), g, b, 0, S(stream), B, L, d, (const f16_t*)x, idx, gamma, beta, (f16_t*)y, ldy, mean, rstd);
-    else return LPI_EINVAL;
+    if (!pool_ln_fwd_ok(dtype, x_dtype, B, L, d, x, idx, gamma, beta, y, ldy, mean, rstd)) return LPI_EINVAL;
+    dispatch_types(PoolLnFwdXY{}, [&](auto tx, auto ty) {
+        typedef type_of<decltype(tx)> TX; typedef type_of<decltype(ty)> TY;
+        LPI_LAUNCH((pool_ln_fwd_kernel<TX, TY>), dim3(rows_grid(B)), dim3(256), 0, S(stream), B, L, d, (const TX*)x, idx, gamma, beta, (TY*)y, ldy, mean, rstd);
+    }, x_dtype, dtype);
     LPI_CHECK_LAST();
     return 0;
 }
 
 extern "C" int lpi_pool_ln_bwd(int cast_dtype, int B, int L, int d, const float* dy, int lddy, const float* x, const int32_t* idx,
                                const float* gamma, const float* mean, const float* rstd, float* dx, void* dx_cast, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || B <= 0 || bad_row_dim(d) || (lddy & 3)) return LPI_EINVAL;
-    if (!row4_ok(dy, lddy, d, LPI_F32) || !al16(x) || !al16(gamma) || !al16(dx) || (dx_cast && !row4_ok(dx_cast, d, d, cast_dtype))) return LPI_EINVAL;
-    dim3 g(rows_grid(B)), b(256);
-    if (cast_dtype == LPI_F32) LPI_LAUNCH(pool_ln_bwd_kernel<float>, g, b, 0, S(stream), B, L, d, dy, lddy, x, idx, gamma, mean, rstd, dx, (float*)dx_cast);
-    else if (cast_dtype == LPI_BF16) LPI_LAUNCH(pool_ln_bwd_kernel<bf16_t>, g, b, 0, S(stream), B, L, d, dy, lddy, x, idx, gamma, mean, rstd, dx, (bf16_t*)dx_cast);
-    else return LPI_EINVAL;
+    if (!pool_ln_bwd_ok(cast_dtype, B, d, dy, lddy, x, gamma, mean, rstd, dx, dx_cast)) return LPI_EINVAL;
+    dispatch_types(F32orBF16{}, [&](auto tc) {
+        typedef type_of<decltype(tc)> TC;
+        LPI_LAUNCH(pool_ln_bwd_kernel<TC>, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, L, d, dy, lddy, x, idx, gamma, mean, rstd, dx, (TC*)dx_cast);
+    }, cast_dtype);
     LPI_CHECK_LAST();
     return 0;
 }
 
 extern "C" int lpi_gather_rows(int x_dtype, int B, int L, int d, const void* src, const int32_t* idx, float* dst, void* stream) {
     if (!src || !dst || B <= 0 || L < 0 || (L == 0 && !idx) || bad_row_dim(d)) return LPI_EINVAL;      // L == 0: idx holds absolute rows
-    if (x_dtype == LPI_F32) LPI_LAUNCH(gather_rows_kernel<float>, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, L, d, (const float*)src, idx, dst);
-    else if (x_dtype == LPI_F16) LPI_LAUNCH(gather_rows_kernel<f16_t>, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, L, d, (const f16_t*)src, idx, dst);
-    else return LPI_EINVAL;
+    if (!dispatch_types(F32orF16{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH(gather_rows_kernel<T>, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, L, d, (const T*)src, idx, dst);
+        }, x_dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1334,16 +1311,28 @@ extern "C" int lpi_gather_rows(int x_dtype, int B, int L, int d, const void* src
 extern "C" int lpi_scatter_rows(int cast_dtype, int B, int L, int d, const float* src, const int32_t* idx, float* dst, void* dst_cast,
                                 void* stream) {
     if (!src || (!dst && !dst_cast) || B <= 0 || L < 0 || (L == 0 && !idx) || bad_row_dim(d)) return LPI_EINVAL;      // L == 0: idx holds absolute rows
-    dim3 g(rows_grid(B)), b(256);
-    if (cast_dtype == LPI_F32) LPI_LAUNCH(scatter_rows_kernel<float>, g, b, 0, S(stream), B, L, d, src, idx, dst, (float*)dst_cast);
-    else if (cast_dtype == LPI_BF16) LPI_LAUNCH(scatter_rows_kernel<bf16_t>, g, b, 0, S(stream), B, L, d, src, idx, dst, (bf16_t*)dst_cast);
-    else return LPI_EINVAL;
+    if (!dispatch_types(F32orBF16{}, [&](auto tc) {
+            typedef type_of<decltype(tc)> TC;
+            LPI_LAUNCH(scatter_rows_kernel<TC>, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, L, d, src, idx, dst, (TC*)dst_cast);
+        }, cast_dtype))
+        return LPI_EINVAL;
+    LPI_CHECK_LAST();
+    return 0;
+}
+
+extern "C" int lpi_scatter_add_rows(int dtype, int B, int L, int d, const void* src, int ld_src, const int32_t* idx, void* dst, int ld_dst, void* stream) {
+    if (!scatter_add_ok(dtype, B, L, d, src, ld_src, idx, dst, ld_dst)) return LPI_EINVAL;
+    if (!dispatch_types(F32orBF16{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH(scatter_add_rows_kernel<T>, dim3(B), dim3(256), 0, S(stream), B, L, d, (const T*)src, ld_src, idx, (T*)dst, ld_dst);
+        }, dtype))
+        return LPI_ENOSYS;
     LPI_CHECK_LAST();
     return 0;
 }
 
 extern "C" int lpi_l2norm_fwd(int B, int E, const float* x, int ldx, float* y, int ldy, float* inv_norm, void* stream) {
-    if (!x || !y || !inv_norm || B <= 0 || bad_row_dim(E) || !row4_ok(x, ldx, E, LPI_F32) || !row4_ok(y, ldy, E, LPI_F32)) return LPI_EINVAL;
+    if (!l2norm_fwd_ok(B, E, x, ldx, y, ldy, inv_norm)) return LPI_EINVAL;
     LPI_LAUNCH(l2norm_fwd_kernel, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, E, x, ldx, y, ldy, inv_norm);
     LPI_CHECK_LAST();
     return 0;
@@ -1351,8 +1340,7 @@ extern "C" int lpi_l2norm_fwd(int B, int E, const float* x, int ldx, float* y, i
 
 extern "C" int lpi_l2norm_bwd(int B, int E, const float* y, int ldy, const float* dy, int lddy, const float* inv_norm, float* dx, int lddx,
                               void* stream) {
-    if (!y || !dy || !inv_norm || !dx || B <= 0 || bad_row_dim(E) || !row4_ok(y, ldy, E, LPI_F32) || !row4_ok(dy, lddy, E, LPI_F32) || !row4_ok(dx, lddx, E, LPI_F32))
-        return LPI_EINVAL;
+    if (!l2norm_bwd_ok(B, E, y, ldy, dy, lddy, inv_norm, dx, lddx)) return LPI_EINVAL;
     LPI_LAUNCH(l2norm_bwd_kernel, dim3(rows_grid(B)), dim3(256), 0, S(stream), B, E, y, ldy, dy, lddy, inv_norm, dx, lddx);
     LPI_CHECK_LAST();
     return 0;
@@ -1396,50 +1384,43 @@ extern "C" int lpi_ln_stats_finalize(int rows, int d, const float* part, int ld,
     return lpi_ln_stats_finalize_pair(rows, d, part, ld, mean, rstd, 0, 0, nullptr, 0, nullptr, nullptr, eps, stream);
 }
 
-// ---- lpi_row_jobs (see row_jobs_kernel): validation per op = the single-op entry point's
+// ---- lpi_row_jobs (see row_jobs_kernel): the blocks of one job, -1 = refuse.  Each op's rule is its entry point's predicate; what the job form adds is spelled out here.
 static int row_job_blocks(const lpi_row_job& q) {
-    if (q.B <= 0) return -1;
     switch (q.op) {
-    case LPI_ROWOP_POOL_LN_FWD:
-        if (!q.a || !q.gamma || !q.beta || !q.out || !q.mean || !q.rstd || q.L < 0 || (q.L == 0 && !q.idx) || bad_row_dim(q.d) || (q.ld_c & 3)) return -1;
-        if (!((q.dt_a == LPI_F32 && (q.dt_b == LPI_F32 || q.dt_b == LPI_BF16 || q.dt_b == LPI_F16)) || (q.dt_a == LPI_F16 && (q.dt_b == LPI_BF16 || q.dt_b == LPI_F16)))) return -1;
-        if (!row4_ok(q.a, q.d, q.d, q.dt_a) || !row4_ok(q.out, q.ld_c, q.d, q.dt_b) || !al16(q.gamma) || !al16(q.beta) || !al16(q.out2)) return -1;      // out2: f32 rows
+    case LPI_ROWOP_POOL_LN_FWD:      // + out2, the job's optional f32 copy of the rows (full f32x4 stores)
+        if (!pool_ln_fwd_ok(q.dt_b, q.dt_a, q.B, q.L, q.d, q.a, q.idx, q.gamma, q.beta, q.out, q.ld_c, q.mean, q.rstd) || !al16(q.out2)) return -1;
         return rows_grid(q.B);
     case LPI_ROWOP_L2NORM_FWD:
-        if (!q.a || !q.out || !q.mean || bad_row_dim(q.d) || !row4_ok(q.a, q.ld_a, q.d, LPI_F32) || !row4_ok(q.out, q.ld_c, q.d, LPI_F32)) return -1;
+        if (!l2norm_fwd_ok(q.B, q.d, (const float*)q.a, q.ld_a, (const float*)q.out, q.ld_c, q.mean)) return -1;
         return rows_grid(q.B);
-    case LPI_ROWOP_L2NORM_BWD:
-        if (!q.a || !q.b || !q.mean_in || !q.out || bad_row_dim(q.d) || (q.ld_a & 3) || (q.ld_b & 3) || (q.ld_c & 3) || (q.out2 && q.dt_b != LPI_BF16)) return -1;
-        if (!row4_ok(q.a, q.ld_a, q.d, LPI_F32) || !row4_ok(q.b, q.ld_b, q.d, LPI_F32) || !row4_ok(q.out, q.ld_c, q.d, LPI_F32) || !row4_ok(q.out2, q.ld_c, q.d, LPI_BF16)) return -1;
+    case LPI_ROWOP_L2NORM_BWD:      // + out2, the job's optional bf16 copy of dx: dt_b says bf16, rows at ld_c like dx
+        if (!l2norm_bwd_ok(q.B, q.d, (const float*)q.a, q.ld_a, (const float*)q.b, q.ld_b, q.mean_in, (const float*)q.out, q.ld_c)) return -1;
+        if (q.out2 && (q.dt_b != LPI_BF16 || !row4_ok(q.out2, q.ld_c, q.d, LPI_BF16))) return -1;
         return rows_grid(q.B);
     case LPI_ROWOP_POOL_LN_BWD:
-        if (!q.a || !q.b || !q.gamma || !q.mean_in || !q.rstd_in || !q.out || bad_row_dim(q.d) || (q.ld_a & 3) || (q.dt_b != LPI_BF16 && q.dt_b != LPI_F32)) return -1;
-        if (!row4_ok(q.a, q.ld_a, q.d, LPI_F32) || !al16(q.b) || !al16(q.gamma) || !al16(q.out) || !row4_ok(q.out2, q.d, q.d, q.dt_b)) return -1;
+        if (!pool_ln_bwd_ok(q.dt_b, q.B, q.d, (const float*)q.a, q.ld_a, (const float*)q.b, q.gamma, q.mean_in, q.rstd_in, (const float*)q.out, q.out2)) return -1;
         return rows_grid(q.B);
-    case LPI_ROWOP_LN_BWD:
-        if (!q.a || !q.b || !q.gamma || !q.mean_in || !q.rstd_in || (!q.out && !q.out2) || bad_row_dim(q.d) || (q.ld_a & 3) || (q.ld_b & 3) || (q.ld_c & 3)) return -1;
-        if (!((q.dt_a == LPI_BF16 && q.dt_b == LPI_BF16) || (q.dt_a == LPI_F32 && q.dt_b == LPI_F32))) return -1;
+    case LPI_ROWOP_LN_BWD:      // f32 x; dy / cast both bf16 or both f32 (the bodies the job kernel holds); out and out2 share the one ld_c
+        if (!types_listed(LnBwdJobDyCast{}, q.dt_a, q.dt_b)) return -1;
         if (!ln_bwd_args_ok(q.dt_a, q.dt_b, LPI_F32, q.B, q.d, q.a, q.ld_a, q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, (const float*)q.out, q.ld_c, q.out2, q.ld_c)) return -1;
         return rows_grid(q.B);
-    case LPI_ROWOP_SCATTER_ADD: {
-        if (!q.a || !q.out || q.L < 0 || (q.L == 0 && !q.idx) || q.d <= 0 || (q.d & 3) || q.ld_a < q.d || q.ld_c < q.d || (q.dt_a != LPI_BF16 && q.dt_a != LPI_F32)) return -1;
-        if (!row4_ok(q.a, q.ld_a, q.d, q.dt_a) || !row4_ok(q.out, q.ld_c, q.d, q.dt_a)) return -1;
+    case LPI_ROWOP_SCATTER_ADD:
+        if (!scatter_add_ok(q.dt_a, q.B, q.L, q.d, q.a, q.ld_a, q.idx, q.out, q.ld_c) || !types_listed(F32orBF16{}, q.dt_a)) return -1;
         return q.B;
-    }
-    case LPI_ROWOP_GATHER_BATCH_ROWS:
-        if (!q.a || !q.out || q.P <= 0 || q.row0 < 0 || q.row0 + q.P > q.L || q.d <= 0 || q.ld_a < q.d || q.ld_c < q.d || !al16(q.a) || !al16(q.out)) return -1;
+    case LPI_ROWOP_GATHER_BATCH_ROWS:      // the job gives d, ld_a and ld_c in 16-byte units already
+        if (!gather_batch_rows_ok(q.B, q.L, q.row0, q.P, q.d, q.a, q.ld_a, q.out, q.ld_c)) return -1;
         return (int)(((long)q.B * q.P * q.d + 255) / 256);
     case LPI_ROWOP_PROMPT_ADD:
-        if (!q.out || !q.a || q.P <= 0 || q.P + 1 > q.L || bad_row_dim(q.d) || (q.bstride & 3) || ((q.mean != nullptr) != (q.rstd != nullptr)) || (q.dt_a != LPI_F16 && q.dt_a != LPI_F32)) return -1;
-        if (!row4_ok(q.out, q.d, q.d, q.dt_a) || !al16(q.a)) return -1;
+        if (!prompt_add_ok(q.dt_a, q.B, q.L, q.P, q.d, q.out, (const float*)q.a, q.bstride, q.mean, q.rstd)) return -1;
         return rows_grid((long)q.B * q.P);
-    case LPI_ROWOP_LN_BWD_ROWS_H16:
-        if (!q.a || !q.b || !q.gamma || !q.mean_in || !q.rstd_in || !q.out2 || q.P <= 0 || q.row0 < 0 || q.row0 + q.P > q.L || bad_row_dim(q.d)) return -1;
-        if (!ln_h16_ok(q.d, q.ld_a, q.ld_b, q.a, q.b) || (q.ld_c & 7) || !al16(q.out2) || q.ld_a < q.d || q.ld_b < q.d || q.ld_c < q.d || !al16(q.gamma)) return -1;
+    case LPI_ROWOP_LN_BWD_ROWS_H16:      // lpi_layernorm_bwd_rows_varlen where it runs the half-wave kernel, and only there; d <= 1024 (the NC the job kernel holds)
+        if (!batch_rows_ok(q.B, q.L, q.row0, q.P) || nc_of(q.d) == 0) return -1;
+        if (!ln_bwd_args_ok(LPI_BF16, LPI_BF16, LPI_F16, q.B * q.P, q.d, q.a, q.ld_a, q.b, q.ld_b, q.gamma, q.mean_in, q.rstd_in, nullptr, 0, q.out2, q.ld_c) ||
+            !ln_bwd_is_h16(LPI_BF16, LPI_BF16, LPI_F16, q.d, q.a, q.ld_a, q.b, q.ld_b, nullptr, q.out2, q.ld_c))
+            return -1;
         return (q.B * q.P + 7) / 8;
     case LPI_ROWOP_VIS_PROMPT_ROWS_BWD:
-        if (!q.out || !q.a || !q.gamma || !q.mean_in || !q.rstd_in || q.P <= 0 || bad_row_dim(q.d) || (q.bstride & 3) || (q.dt_a != LPI_BF16 && q.dt_a != LPI_F32)) return -1;
-        if (!row4_ok(q.out, q.d, q.d, q.dt_a) || !al16(q.a) || !al16(q.gamma)) return -1;
+        if (!vis_prompt_rows_bwd_ok(q.dt_a, q.B, q.P, q.d, q.out, (const float*)q.a, q.bstride, q.gamma, q.mean_in, q.rstd_in)) return -1;
         return rows_grid((long)q.B * q.P);
     }
     return -1;
@@ -1474,9 +1455,8 @@ extern "C" int lpi_rows_sum_over_batch_pair(int dtype, const lpi_rows_sum_desc* 
         gx = std::max(gx, q.P);
         gy = std::max(gy, (q.d + 255) / 256);
     }
-    if (dtype == LPI_F32) LPI_LAUNCH(rows_sum_pair_kernel<float>, dim3(gx, gy, 2), dim3(1024), 0, S(stream), p[0], p[1]);
-    else if (dtype == LPI_BF16) LPI_LAUNCH(rows_sum_pair_kernel<bf16_t>, dim3(gx, gy, 2), dim3(1024), 0, S(stream), p[0], p[1]);
-    else return LPI_EINVAL;
+    if (!dispatch_types(F32orBF16{}, [&](auto t) { LPI_LAUNCH(rows_sum_pair_kernel<type_of<decltype(t)>>, dim3(gx, gy, 2), dim3(1024), 0, S(stream), p[0], p[1]); }, dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1492,10 +1472,11 @@ extern "C" int lpi_cast(int src_dtype, int dst_dtype, long n, const void* src, v
     if (!src || !dst || n <= 0 || (n & 3)) return LPI_EINVAL;
     const long n4 = n >> 2;
     dim3 g((unsigned)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256)), b(256);
-    if (src_dtype == LPI_F32 && dst_dtype == LPI_BF16) LPI_LAUNCH((cast_kernel<float, bf16_t>), g, b, 0, S(stream), n4, (const float*)src, (bf16_t*)dst);
-    else if (src_dtype == LPI_BF16 && dst_dtype == LPI_F32) LPI_LAUNCH((cast_kernel<bf16_t, float>), g, b, 0, S(stream), n4, (const bf16_t*)src, (float*)dst);
-    else if (src_dtype == LPI_F32 && dst_dtype == LPI_F32) LPI_LAUNCH((cast_kernel<float, float>), g, b, 0, S(stream), n4, (const float*)src, (float*)dst);
-    else return LPI_EINVAL;
+    if (!dispatch_types(TypeList<Types<float, bf16_t>, Types<bf16_t, float>, Types<float, float>>{}, [&](auto ts, auto td) {
+            typedef type_of<decltype(ts)> TS; typedef type_of<decltype(td)> TD;
+            LPI_LAUNCH((cast_kernel<TS, TD>), g, b, 0, S(stream), n4, (const TS*)src, (TD*)dst);
+        }, src_dtype, dst_dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1505,10 +1486,8 @@ extern "C" int lpi_transpose2(int dtype, int rows0, int cols0, const void* src0,
     if (!src0 || !dst0 || !src1 || !dst1 || rows0 <= 0 || cols0 <= 0 || rows1 <= 0 || cols1 <= 0 || lds0 < cols0 || ldd0 < rows0 || lds1 < cols1 || ldd1 < rows1)
         return LPI_EINVAL;
     dim3 g((std::max(cols0, cols1) + 31) / 32, (std::max(rows0, rows1) + 31) / 32, 2), b(256);
-    if (dtype == LPI_F32)
-        LPI_LAUNCH(transpose2_kernel<float>, g, b, 0, S(stream), rows0, cols0, (const float*)src0, lds0, (float*)dst0, ldd0, rows1, cols1, (const float*)src1, lds1,
-                   (float*)dst1, ldd1);
-    else return LPI_EINVAL;
+    if (dtype != LPI_F32) return LPI_EINVAL;      // the one type it is built for
+    LPI_LAUNCH(transpose2_kernel<float>, g, b, 0, S(stream), rows0, cols0, (const float*)src0, lds0, (float*)dst0, ldd0, rows1, cols1, (const float*)src1, lds1, (float*)dst1, ldd1);
     LPI_CHECK_LAST();
     return 0;
 }
@@ -1516,9 +1495,11 @@ extern "C" int lpi_transpose2(int dtype, int rows0, int cols0, const void* src0,
 extern "C" int lpi_transpose(int dtype, int rows, int cols, const void* src, int lds, void* dst, int ldd, void* stream) {
     if (!src || !dst || rows <= 0 || cols <= 0 || lds < cols || ldd < rows) return LPI_EINVAL;
     dim3 g((cols + 31) / 32, (rows + 31) / 32), b(256);
-    if (dtype == LPI_F32) LPI_LAUNCH(transpose_kernel<float>, g, b, 0, S(stream), rows, cols, (const float*)src, lds, (float*)dst, ldd);
-    else if (dtype == LPI_BF16) LPI_LAUNCH(transpose_kernel<bf16_t>, g, b, 0, S(stream), rows, cols, (const bf16_t*)src, lds, (bf16_t*)dst, ldd);
-    else return LPI_EINVAL;
+    if (!dispatch_types(F32orBF16{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH(transpose_kernel<T>, g, b, 0, S(stream), rows, cols, (const T*)src, lds, (T*)dst, ldd);
+        }, dtype))
+        return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
 }
