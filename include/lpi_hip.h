@@ -728,6 +728,36 @@ int lpi_search_rerank(int nq, int ng, int E, const float* Q, int ldq, const floa
                       int32_t* idx, float* val, void* stream);
 int lpi_search_rerank_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, const int32_t* cand, int ldc, int kc, int k,
                         int32_t* idx, float* val, void* stream);
+/* The top-k calls on MX-FP4 operands read in place (search_mx4.hip, search_wide.hip, mx4_rows.hip; since 622): a COARSE operand for a two-stage search,
+ * half a byte per gallery element plus the scales (0.53 bytes), four times the bf16 matrix rate.  Its lists are candidate lists for lpi_search_rerank
+ * (scores are off by a few 1e-2 on unit rows), so there is no rank form and no re-rank form: lpi_search_topk_t, lpi_search_topk_wide_t,
+ * lpi_search_rank_t and lpi_search_rerank_t refuse dt = LPI_MX4 exactly as they refuse LPI_MX8.
+ * THE MX-FP4 FORMAT.  Codes: uint8 [n, E / 2], OCP e2m1 nibbles, a sign bit (8) and a magnitude code 0 .. 7 = {0, 0.5, 1, 1.5, 2, 3, 4, 6}; element 2 j of
+ * a row is the LOW nibble of byte j, element 2 j + 1 the high one, so a row's bytes are the matrix instruction's operand bytes in K order and the search
+ * reads them in place.  (Measured on an MI355X, tools/probe/mx4_map_probe.hip: a lane of v_mfma_scale_f32_16x16x128_f8f6f4 holds 32 consecutive K elements
+ * in 16 bytes and the scale of exactly those; the instruction pairs nibble positions of its two operands, and a product of two operands packed alike
+ * is the same in either nibble order, so the order is this format's choice.)  Scales: uint8 [n, E / 32], E8M0 (value 2^(byte - 127)), one per 32
+ * consecutive elements.  Scale rule: for a block maximum amax with biased f32 exponent Eb, byte = max(Eb - 2, 0): the OCP rule e = floor(log2 amax) - 2.
+ * Element rule: y 2^(127 - byte) (exact) rounded to nearest even on the e2m1 grid and saturating at +-6: values in (6, 8) become 6.  A zero or subnormal
+ * amax gives byte 0.  Non-finite inputs and the scale byte 0xFF are out of contract, as for MX-FP8.  tests/mx4_emulate.py restates the format on the CPU.
+ * lpi_mx4_quantize: rows of x (`x_dtype`: LPI_F32 | LPI_BF16 | LPI_F16, [rows, ldx], ldx >= K in multiples of 4, x aligned to 4 elements) -> q (codes
+ *   [rows, ldq bytes], ldq >= K / 2 and a multiple of 4, q 4-byte aligned) + scales ([rows, lds >= K / 32], one byte per store), one launch, bit for bit
+ *   the emulator.  rows > 0, K a positive multiple of 32, no NULL pointer.  Anything else is LPI_EINVAL before any launch.
+ * lpi_search_topk_mx4 (1 <= k <= 16) / lpi_search_topk_wide_mx4 (1 <= k <= LPI_SEARCH_KWIDE): lpi_search_topk_mx8 / lpi_search_topk_wide_mx8 on such
+ *   operands.  s[i,j] is the f32 result of the chain of E / 128 block-scaled instructions over the two rows in one fixed order: its bits depend on its two
+ *   rows (codes and scales) only, so a chunked search equals one call bit for bit, the narrow and the wide call give the same bits for the same pair, and
+ *   the order is lpi_topk's.  val holds the scores of the QUANTISED rows: within 8.6e-5 |q| . |g| of the exact product of the dequantised rows
+ *   (tests/test_search_mx4_gpu.py has the measured figure), exact where the partial sums are exact.  Envelope: nq, ng > 0; E (in ELEMENTS) a multiple of
+ *   128 and <= 1024; ldq / ldg in BYTES, >= E / 2 and multiples of 16, Q and G 16-byte aligned; ldqs / ldgs >= E / 32 and multiples of 4, the scale bases
+ *   4-byte aligned; no NULL pointer; k, col_base, accumulate, idx, val, ws and lpi_search_workspace / lpi_search_wide_workspace as for the f32 calls.
+ *   Anything else is LPI_EINVAL before any launch.  Nothing outside the n x E / 2 code bytes and the n x E / 32 scale bytes is read.  Two launches. */
+#define LPI_MX4 5
+int lpi_mx4_quantize(int x_dtype, int rows, int K, const void* x, int ldx, void* q, int ldq, void* scales, int lds, void* stream);
+int lpi_search_topk_mx4(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg, const void* g_scales,
+                        int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes, void* stream);
+int lpi_search_topk_wide_mx4(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
+                             const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes,
+                             void* stream);
 
 /* ---- a6 (host side): CLIP byte-level BPE      replaces: models/clip/simple_tokenizer.py:62-132, clip.py:185-221 ------
  * HOST functions (no GPU work, no stream).  create: `merges_utf8` is the decompressed text of bpe_simple_vocab_16e6.txt(.gz) —

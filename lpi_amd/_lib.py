@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LPI_LIB") or os.path.join(_HERE, "csrc", "liblpi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
+MX4 = 5      # LPI_MX4: the code the typed search calls refuse (the MX-FP4 search has entry points of its own)
 MX8 = 3      # lpi_gemm_nt_mx8's c_dtype for an MX-FP8 output (e4m3 bytes + E8M0 scales along N)
 GEMM_K_128, GEMM_K_256, GEMM_K_256_TAIL, GEMM_K_256X128, GEMM_K_ROWS = 0, 1, 2, 3, 4      # LPI_GEMM_K_* of lpi_gemm_last_kernel
 GEMM_K_MX8 = 5      # LPI_GEMM_K_MX8 of lpi_gemm_last_kernel
@@ -149,6 +150,10 @@ SIGNATURES = {
     "lpi_search_topk_wide": [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "lpi_search_topk_wide_t": [_I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "lpi_search_topk_wide_mx8": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    # MX-FP4 operands (a coarse type: top-k only): e2m1 nibbles + E8M0 scales per operand, byte leading dimensions (search_mx4.hip, mx4_rows.hip)
+    "lpi_mx4_quantize": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
+    "lpi_search_topk_mx4": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "lpi_search_topk_wide_mx4": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     # second stage: exact scores of a candidate list per query row, the k best of them (search_rerank.hip); the _t form takes dt first
     "lpi_search_rerank": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     "lpi_search_rerank_t": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P],
@@ -181,7 +186,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 621
+EXPECTED_ABI = 622
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -1,5 +1,5 @@
-// The tile code of the streamed search and the host logic of its two calls, for an operand type T: float (search.hip), bf16_t / f16_t (search16.hip) or
-// mx8_t (search_mx8.hip: e4m3 bytes + one E8M0 scale per 32 elements, mx8.h).
+// The tile code of the streamed search and the host logic of its two calls, for an operand type T: float (search.hip), bf16_t / f16_t (search16.hip),
+// mx8_t (search_mx8.hip: e4m3 bytes + one E8M0 scale per 32 elements, mx8.h) or mx4_t (search_mx4.hip: e2m1 nibbles + the same scales, mx4.h; top-k only).
 //
 // Design:
 //  * the main loop is gemm.hip's: 128x128 tile, 4 waves as 2x2, K-contiguous operands staged one 128-byte row piece (BK = 32 f32 / 64 2-byte k-values) at
@@ -20,6 +20,13 @@
 //    elements) and read back with ds_read_u8 at row * 4 + (l >> 4): the register a lane hands the instruction holds the scale of row l & 15, K block
 //    l >> 4 (gemm_mx8.hip has the measured operand map).  Gallery = the instruction's first operand, queries its second, as mma_chunk's: the lane ends
 //    with the same acc[n][m], and the epilogues below are the same lines for every type;
+//  * MX-FP4 (T = mx4_t, everything under `if constexpr (kIsMx4<T>)`): the element is a BYTE of two nibbles and SearchArgs::E the row length in bytes, so
+//    staging, swizzle, the edges and the shortened last slab (E % 256 == 128 elements) are the 1-byte type's lines.  A staged 128-byte row piece is 256
+//    elements = TWO instructions' K: a slab is two k steps, and step ks reads ONE ds_read_b128 per lane and sub tile, chunk 4 ks + g, the 32 consecutive
+//    elements the instruction wants from that lane (mx4.h has the measured operand map; MX-FP8 reads chunks g and 4 + g of one step).  A slab has 8 scale
+//    bytes per tile row: two global_load_lds of a dword per lane (global_load_lds has no 8-byte form), step-major behind the element tiles,
+//    [operand][step][row][4 bytes] = 4 x 512 B per stage, read back with ds_read_u8 at step * 512 + row * 4 + g; the second dword of a shortened last slab
+//    lies past the row's scales and is staged from the first again, never read.  No rank form;
 //  * top-k: every wave keeps a sorted list per row of its 64x64 quadrant's columns in LDS; scores are compared in registers with the row's current k-th
 //    and only survivors are inserted (the four lanes that share a row take turns).  Per-(split, wave column) lists go to the workspace, the merge
 //    kernel (search.hip, one for every operand type: it sees f32 scores only) writes idx / val;
@@ -28,11 +35,16 @@
 #pragma once
 #include "common.h"
 #include "mx8.h"
+#include "mx4.h"
 #include <math.h>
 
 // search.hip: the launch of search_merge_kernel, the partial lists (and, with accumulate, the list idx / val already hold) -> idx / val
 int lpi_search_merge(int nq, int k, int nparts, const float* part_val, const int32_t* part_idx, int col_base, int accumulate, int32_t* idx, float* val,
                      hipStream_t s);
+
+// search_wide.hip: the launch of search_wide_merge_kernel, the splits' sorted lists in the candidate buffers (and, with accumulate, the held list) -> idx / val
+int lpi_search_wide_merge(int nq, int k, int nparts, int cap, const float* part_val, const int32_t* part_idx, int col_base, int accumulate, int32_t* idx,
+                          float* val, hipStream_t s);
 
 namespace {
 
@@ -41,7 +53,9 @@ constexpr int ROW_BYTES = 128;
 constexpr int TILE_BYTES = BM * ROW_BYTES;
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;
 constexpr int SCALE_BYTES = BM * 4;      // MX-FP8: the scale bytes of one operand's tile rows for one slab
-template <typename T> inline constexpr int kStageBytes = STAGE_BYTES + (kIsMx8<T> ? 2 * SCALE_BYTES : 0);
+template <typename T> inline constexpr bool kHasScales = kIsMx8<T> || kIsMx4<T>;
+template <typename T> inline constexpr int kScaleOperandBytes = kIsMx4<T> ? 2 * SCALE_BYTES : SCALE_BYTES;      // MX-FP4: two k steps per slab
+template <typename T> inline constexpr int kStageBytes = STAGE_BYTES + (kHasScales<T> ? 2 * kScaleOperandBytes<T> : 0);
 constexpr int NTHREADS = 256;
 constexpr int KMAX = 16;
 constexpr int WG_TARGET = 512;      // workgroups wanted per launch: two per CU of an MI355X
@@ -74,6 +88,27 @@ struct SearchArgs<mx8_t> {
     const mx8_t* Q;
     int ldq;
     const mx8_t* G;
+    int ldg;
+    int k, tiles, splits;
+    const int32_t* gt;
+    int gpr;
+    float* thr;
+    int32_t* gstar;
+    int32_t* rank;
+    float* part_val;
+    int32_t* part_idx;
+    const uint8_t* Qs;
+    int ldqs;
+    const uint8_t* Gs;
+    int ldgs;
+};
+// MX-FP4: the same, with E, ldq and ldg in BYTES (two elements each): the kernel's element is the byte
+template <>
+struct SearchArgs<mx4_t> {
+    int nq, ng, E;
+    const mx4_t* Q;
+    int ldq;
+    const mx4_t* G;
     int ldg;
     int k, tiles, splits;
     const int32_t* gt;
@@ -241,7 +276,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.G + (size_t)gr * a.ldg + koff),
                                              (__attribute__((address_space(3))) void*)(base + TILE_BYTES + i * 4096), 16, 0, 0);
         }
-        if constexpr (kIsMx8<T>) {      // the slab's scales: lane = tile row (wave & 1) * 64 + lane of the queries (waves 0, 1) / the gallery (waves 2, 3)
+        if constexpr (kHasScales<T>) {      // the slab's scales: lane = tile row (wave & 1) * 64 + lane of the queries (waves 0, 1) / the gallery (waves 2, 3)
             const int r = (wave & 1) * 64 + lane;
             const uint8_t* sp;
             if (wave < 2) {
@@ -257,8 +292,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
                 }
                 sp = a.Gs + (size_t)gr * a.ldgs;
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp + kt * 4),
-                                             (__attribute__((address_space(3))) void*)(smem + buf * STAGE + 2 * TILE_BYTES + (wave >> 1) * SCALE_BYTES + (wave & 1) * 256), 4, 0, 0);
+            if constexpr (kIsMx4<T>) {      // 8 bytes per row: step 0's dword, then step 1's (a row has E / 16 scale bytes; past them: step 0's again)
+                char* dst = smem + buf * STAGE + 2 * TILE_BYTES + (wave >> 1) * 2 * SCALE_BYTES + (wave & 1) * 256;
+                const int s0 = kt * 8, s1 = s0 + 4 < (a.E >> 4) ? s0 + 4 : s0;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp + s0),
+                                                 (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp + s1),
+                                                 (__attribute__((address_space(3))) void*)(dst + SCALE_BYTES), 4, 0, 0);
+            } else {
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp + kt * 4),
+                                                 (__attribute__((address_space(3))) void*)(smem + buf * STAGE + 2 * TILE_BYTES + (wave >> 1) * SCALE_BYTES + (wave & 1) * 256), 4, 0, 0);
+            }
         }
     };
 
@@ -270,7 +314,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
     const int a_frag_base = (wm * 64) * ROW_BYTES;               // query rows
     const int b_frag_base = TILE_BYTES + (wn * 64) * ROW_BYTES;  // gallery rows
     const int a_sc_base = 2 * TILE_BYTES + (wm * 64 + r16) * 4 + g;                // MX-FP8: the lane's scale byte of its first query / gallery row
-    const int b_sc_base = 2 * TILE_BYTES + SCALE_BYTES + (wn * 64 + r16) * 4 + g;
+    const int b_sc_base = 2 * TILE_BYTES + kScaleOperandBytes<T> + (wn * 64 + r16) * 4 + g;      // MX-FP4: + SCALE_BYTES for the slab's second step
 
     // ---- per-mode state.  A lane owns rows m0 + wm*64 + mi*16 + r16 (mi = 0..3) and, of each, columns wn*64 + ni*16 + 4g + 0..3 of the tile
     lds_f32* Lv = nullptr;      // MODE_TOPK: this wave's lists, [64 rows][k]
@@ -342,6 +386,28 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
                 // hipcc sinks block-scaled instructions past barriers (gemm256_tile.h): an empty statement that "uses" the accumulators keeps them in their slab
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) asm volatile("" : "+v"(acc[ni][0]), "+v"(acc[ni][1]), "+v"(acc[ni][2]), "+v"(acc[ni][3]));
+            } else if constexpr (kIsMx4<T>) {
+                const int nks = kt == nk - 1 ? ks_last : 2;
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    if (ks < nks) {
+                        Chunk fa[4], fb[4];
+                        int sa[4], sb[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            fa[i].u = *reinterpret_cast<const uint4*>(buf + a_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                            fb[i].u = *reinterpret_cast<const uint4*>(buf + b_frag_base + i * 16 * ROW_BYTES + foff[ks]);
+                            sa[i] = *reinterpret_cast<const uint8_t*>(buf + a_sc_base + ks * SCALE_BYTES + i * 64);
+                            sb[i] = *reinterpret_cast<const uint8_t*>(buf + b_sc_base + ks * SCALE_BYTES + i * 64);
+                        }
+#pragma unroll
+                        for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                            for (int mi = 0; mi < 4; ++mi) mx4_mma(acc[ni][mi], fb[ni], fa[mi], sb[ni], sa[mi]);
+#pragma unroll
+                        for (int ni = 0; ni < 4; ++ni) asm volatile("" : "+v"(acc[ni][0]), "+v"(acc[ni][1]), "+v"(acc[ni][2]), "+v"(acc[ni][3]));      // as above
+                    }
+                }
             } else {
                 const int nks = kt == nk - 1 ? ks_last : 2;
 #pragma unroll
@@ -521,16 +587,17 @@ inline int search_splits(int nq, int ng)
     return tiles < want ? tiles : want;
 }
 
-// the envelope both calls share: E a multiple of half a slab (f32: 16, 2-byte: 32; MX-FP8: of a whole one, 128), rows of whole 16-byte pieces; MX-FP8:
-// scale rows of whole dwords
+// the envelope both calls share: E a multiple of half a slab (f32: 16, 2-byte: 32; MX-FP8: of a whole one, 128; MX-FP4: 128 elements, half a slab), rows of
+// whole 16-byte pieces (MX-FP4: leading dimensions in bytes, a row has E / 2); MX-FP8 / MX-FP4: scale rows of whole dwords
 template <typename T>
 int search_check(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const SearchScales& sc)
 {
-    constexpr int EPC = Elem<T>::EPC, HALF = kIsMx8<T> ? ROW_BYTES : ROW_BYTES / (int)sizeof(T) / 2;
+    constexpr int EPC = Elem<T>::EPC, HALF = kHasScales<T> ? ROW_BYTES : ROW_BYTES / (int)sizeof(T) / 2;
     if (nq <= 0 || ng <= 0 || E <= 0 || (E & (HALF - 1)) || E > 1024) return LPI_EINVAL;
-    if (ldq < E || ldg < E || (ldq & (EPC - 1)) || (ldg & (EPC - 1))) return LPI_EINVAL;
+    const int row = kIsMx4<T> ? E / 2 : E;      // in the units of ldq / ldg
+    if (ldq < row || ldg < row || (ldq & (EPC - 1)) || (ldg & (EPC - 1))) return LPI_EINVAL;
     if (!Q || !G || (((uintptr_t)Q | (uintptr_t)G) & 15)) return LPI_EINVAL;
-    if constexpr (kIsMx8<T>) {
+    if constexpr (kHasScales<T>) {
         if (!sc.q || !sc.g || (((uintptr_t)sc.q | (uintptr_t)sc.g) & 3)) return LPI_EINVAL;
         if (sc.ldq < E / 32 || sc.ldg < E / 32 || (sc.ldq & 3) || (sc.ldg & 3)) return LPI_EINVAL;
     }
@@ -546,8 +613,8 @@ int search_topk(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg,
     if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, k)) return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     SearchArgs<T> a{};
-    a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
-    if constexpr (kIsMx8<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
+    a.nq = nq; a.ng = ng; a.E = kIsMx4<T> ? E / 2 : E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
+    if constexpr (kHasScales<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
     a.tiles = (ng + BN - 1) / BN;
     a.splits = search_splits(nq, ng);
     const size_t nlist = (size_t)2 * a.splits * nq * k;
@@ -561,6 +628,34 @@ int search_topk(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg,
     LPI_CHECK_LAST();
     return lpi_search_merge(nq, k, 2 * a.splits, a.part_val, a.part_idx, col_base, accumulate, idx, val, s);
 }
+
+// the wide call (search_wide.hip has the design and the merge kernel): the sweep with the MODE_WIDE epilogue, then the merge of the splits' lists
+template <typename T>
+int search_topk_wide(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, int k, int col_base, int accumulate, int32_t* idx, float* val,
+                     void* ws, long ws_bytes, void* stream, SearchScales sc = SearchScales{})
+{
+    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
+    if (k < 1 || k > KWIDE || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
+    if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_wide_workspace(nq, ng, k)) return LPI_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    SearchArgs<T> a{};
+    a.nq = nq; a.ng = ng; a.E = kIsMx4<T> ? E / 2 : E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;      // MX-FP4: the row length in bytes
+    if constexpr (kHasScales<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
+    a.tiles = (ng + BN - 1) / BN;
+    a.splits = search_splits(nq, ng);
+    const int cap = wide_cap(k);
+    const size_t nlist = (size_t)a.splits * nq * cap;      // [splits][nq][cap] values, then as many indices
+    a.part_val = (float*)ws;
+    a.part_idx = (int32_t*)ws + nlist;
+    auto kern = search_kernel<T, MODE_WIDE>;
+    static LdsOnce once;
+    constexpr int LDS = 2 * kStageBytes<T> + BM * 12;
+    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS)) return e;
+    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), LDS, s, a);
+    LPI_CHECK_LAST();
+    return lpi_search_wide_merge(nq, k, a.splits, cap, a.part_val, a.part_idx, col_base, accumulate, idx, val, s);
+}
+
 
 template <typename T>
 int search_rank(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const int32_t* gt, int gt_per_row, int32_t* rank, void* ws,

@@ -1,6 +1,6 @@
 // Streamed search, wide lists: the k best gallery rows of every query row for k up to 256 in ONE sweep of the gallery, for every operand type.
 //
-//   lpi_search_topk_wide / _wide_t / _wide_mx8: what lpi_search_topk / _t / _mx8 give, with 1 <= k <= 256
+//   lpi_search_topk_wide / _wide_t / _wide_mx8: what lpi_search_topk / _t / _mx8 give, with 1 <= k <= 256 (_wide_mx4: search_mx4.hip, the same code)
 //
 // The scores are the narrow kernels', bit for bit: the sweep is search_tile.h's kernel (same tile, staging, accumulator chain and masking) with another
 // epilogue, MODE_WIDE.  Keeping a sorted list of 256 per row in LDS is out of reach (64 rows x 256 x 8 bytes per wave), so the selection is lazy:
@@ -61,36 +61,17 @@ __global__ __launch_bounds__(64 * MERGE_ROWS) void search_wide_merge_kernel(int 
     }
 }
 
-template <typename T>
-int search_topk_wide(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, int k, int col_base, int accumulate, int32_t* idx, float* val,
-                     void* ws, long ws_bytes, void* stream, SearchScales sc = SearchScales{})
+}  // namespace
+
+// the launch of search_wide_merge_kernel (search_tile.h's search_topk_wide calls it from every object that instantiates a wide sweep)
+int lpi_search_wide_merge(int nq, int k, int nparts, int cap, const float* part_val, const int32_t* part_idx, int col_base, int accumulate, int32_t* idx,
+                          float* val, hipStream_t s)
 {
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
-    if (k < 1 || k > KWIDE || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
-    if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_wide_workspace(nq, ng, k)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    SearchArgs<T> a{};
-    a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
-    if constexpr (kIsMx8<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
-    a.tiles = (ng + BN - 1) / BN;
-    a.splits = search_splits(nq, ng);
-    const int cap = wide_cap(k);
-    const size_t nlist = (size_t)a.splits * nq * cap;      // [splits][nq][cap] values, then as many indices
-    a.part_val = (float*)ws;
-    a.part_idx = (int32_t*)ws + nlist;
-    auto kern = search_kernel<T, MODE_WIDE>;
-    static LdsOnce once;
-    constexpr int LDS = 2 * kStageBytes<T> + BM * 12;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS)) return e;
-    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), LDS, s, a);
-    LPI_CHECK_LAST();
-    LPI_LAUNCH(search_wide_merge_kernel, dim3((nq + MERGE_ROWS - 1) / MERGE_ROWS), dim3(64 * MERGE_ROWS), 0, s, nq, k, a.splits, cap, a.part_val,
-               a.part_idx, col_base, accumulate, idx, val);
+    LPI_LAUNCH(search_wide_merge_kernel, dim3((nq + MERGE_ROWS - 1) / MERGE_ROWS), dim3(64 * MERGE_ROWS), 0, s, nq, k, nparts, cap, part_val, part_idx,
+               col_base, accumulate, idx, val);
     LPI_CHECK_LAST();
     return 0;
 }
-
-}  // namespace
 
 // An upper bound of what the launches use that never shrinks when an argument grows: lpi_search_workspace's block bound, one candidate buffer per block row.
 extern "C" long lpi_search_wide_workspace(int nq, int ng, int k)

@@ -7,7 +7,12 @@ tensor of that dtype is read in place, a score is the f32 sum in one fixed order
 holds.  ``operands="mx8"`` searches MX-FP8 operands (csrc/search_mx8.hip): e4m3 bytes with one E8M0 scale byte per 32 elements, an ``Mx8Rows`` (what
 ``quantize_mx8`` returns), one byte per element plus the scales; an ``Mx8Rows`` is read in place, a float tensor is quantised once; a score is the f32
 result of the block-scaled instruction chain over E in one fixed order, of the QUANTISED rows, and the properties above hold.  There is no fall-back:
-a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, of 128 for MX-FP8, <= 1024; 1 <= k <= 256) raises.
+a shape outside the envelope (E a multiple of 16, of 32 for 2-byte operands, of 128 for MX-FP8 and MX-FP4, <= 1024; 1 <= k <= 256) raises.
+
+``operands="mx4"`` searches MX-FP4 operands (csrc/search_mx4.hip): e2m1 nibbles, two per byte, with the same scales, an ``Mx4Rows`` (what
+``quantize_mx4`` returns), 0.53 bytes per element.  It is a COARSE type: ``topk`` and the coarse stage of ``topk_reranked`` take it, with every property
+above (a score is the block-scaled chain over the quantised rows), but its scores are off by a few 1e-2 on unit rows, so ``gt_rank`` and ``rerank``
+refuse it: an MX-FP4 list is a candidate list for ``rerank``, not a result.
 
 ``topk`` with k <= 16 keeps a sorted list per row in LDS (the narrow entry points).  17 <= k <= 256 goes to the wide entry points (csrc/search_wide.hip):
 the same scores, bit for bit, in one sweep of the gallery; scores that beat a row's current k-th best are appended to a candidate buffer in the
@@ -39,13 +44,13 @@ _OPERANDS = {"bf16": (_lib.BF16, torch.bfloat16), "f16": (_lib.F16, torch.float1
 
 
 def _operands(operands):
-    """None | 'f32' -> None (the f32 entry points); 'bf16' | 'f16' -> (LPI code, torch dtype); 'mx8' -> 'mx8'."""
+    """None | 'f32' -> None (the f32 entry points); 'bf16' | 'f16' -> (LPI code, torch dtype); 'mx8' -> 'mx8'; 'mx4' -> 'mx4'."""
     if operands is None or operands == "f32":
         return None
-    if operands == "mx8":
-        return "mx8"
+    if operands == "mx8" or operands == "mx4":
+        return operands
     if not isinstance(operands, str) or operands not in _OPERANDS:
-        raise ValueError(f"unknown operands {operands!r} (f32 | bf16 | f16 | mx8)")
+        raise ValueError(f"unknown operands {operands!r} (f32 | bf16 | f16 | mx8 | mx4)")
     return _OPERANDS[operands]
 
 
@@ -96,6 +101,54 @@ class Mx8Rows:
         return Mx8Rows(self.codes[rows], self.scales[rows])
 
 
+class Mx4Rows:
+    """Rows in the project's MX-FP4 format (include/lpi_hip.h): ``codes`` uint8 [n, E / 2] (e2m1 nibbles, element 2 j in the low nibble of byte j) and
+    ``scales`` uint8 [n, E / 32] (E8M0, one per 32 consecutive elements), as the search reads them in place: unit inner strides, a 16-byte row stride and
+    base for the codes, a 4-byte row stride and base for the scales.  Immutable; ``rows[a:b]`` is a view of rows a..b-1.  ``shape`` is (n, E) in
+    ELEMENTS.  A coarse operand: ``topk`` and the coarse stage of ``topk_reranked`` take it, ``gt_rank`` and ``rerank`` do not."""
+    __slots__ = ("codes", "scales")
+
+    def __init__(self, codes, scales):
+        for name, t in (("codes", codes), ("scales", scales)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2:
+                raise ValueError(f"Mx4Rows: {name} must be a uint8 tensor [rows, ...]")
+        n, E = codes.shape[0], 2 * codes.shape[1]
+        if E == 0 or E % 32 or tuple(scales.shape) != (n, E // 32):
+            raise ValueError(f"Mx4Rows: codes [n, E / 2] with E a multiple of 32 and scales [n, E / 32], got {tuple(codes.shape)} and {tuple(scales.shape)}")
+        if codes.device != scales.device:
+            raise ValueError("Mx4Rows: codes and scales on different devices")
+        for name, t, align in (("codes", codes, 16), ("scales", scales, 4)):
+            if t.stride(1) != 1 or t.stride(0) % align or t.stride(0) < t.shape[1] or t.data_ptr() % align:
+                raise ValueError(f"Mx4Rows: {name} needs a unit inner stride and a row stride and base that are multiples of {align} bytes")
+        object.__setattr__(self, "codes", codes)
+        object.__setattr__(self, "scales", scales)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Mx4Rows is immutable")
+
+    @property
+    def shape(self):
+        return torch.Size((self.codes.shape[0], 2 * self.codes.shape[1]))
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    @property
+    def nbytes(self):
+        """The bytes of the codes and scales themselves (gaps of a strided view are not counted)."""
+        n, E = self.shape
+        return n * (E // 2) + n * (E // 32)
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    def __getitem__(self, rows):
+        if not isinstance(rows, slice) or rows.step not in (None, 1):
+            raise TypeError("Mx4Rows[a:b]: a slice of rows with step 1")
+        return Mx4Rows(self.codes[rows], self.scales[rows])
+
+
 _QUANT_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 
 
@@ -117,25 +170,49 @@ def quantize_mx8(x):
     return Mx8Rows(codes, scales)
 
 
+def quantize_mx4(x):
+    """f32 / bf16 / f16 [n, E] on the device (E a multiple of 32) -> Mx4Rows: one lpi_mx4_quantize launch (bit for bit tests/mx4_emulate.quantize)."""
+    if x.dim() != 2:
+        raise ValueError("expected a [rows, E] tensor")
+    if x.dtype not in _QUANT_DT:
+        x = x.float()
+    n, E = x.shape
+    if n == 0 or E == 0 or E % 32:
+        raise ValueError(f"quantize_mx4: [n, E] with n > 0 and E a positive multiple of 32, got {tuple(x.shape)}")
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < E or x.data_ptr() % (4 * x.element_size()):
+        x = x.contiguous()
+    codes = torch.empty(n, E // 2, dtype=torch.uint8, device=x.device)
+    lds = (E // 32 + 3) // 4 * 4      # scale rows of whole dwords
+    scales = torch.empty(n, lds, dtype=torch.uint8, device=x.device)[:, :E // 32]
+    _lib.call("lpi_mx4_quantize", _QUANT_DT[x.dtype], n, E, x, x.stride(0), codes, E // 2, scales, lds, torch.cuda.current_stream().cuda_stream)
+    return Mx4Rows(codes, scales)
+
+
 def _prepare(queries, gallery, typed, form):
     """The operands as `typed` (_operands) wants them -> (nq, ng, E, device, entry point of `form` = 'topk' | 'rank', its arguments up to the gallery's)."""
     if typed != "mx8" and (isinstance(queries, Mx8Rows) or isinstance(gallery, Mx8Rows)):
         raise ValueError('an Mx8Rows operand is searched with operands="mx8"')
+    if typed != "mx4" and (isinstance(queries, Mx4Rows) or isinstance(gallery, Mx4Rows)):
+        raise ValueError('an Mx4Rows operand is searched with operands="mx4"')
+    if typed == "mx4" and form != "topk":
+        raise ValueError('MX-FP4 ("mx4", an Mx4Rows) is a coarse top-k type: there is no rank form on its scores')
     if typed is None:
         q, g = _f32_rows(queries), _f32_rows(gallery)
     elif typed == "mx8":
         q, g = (t if isinstance(t, Mx8Rows) else quantize_mx8(t) for t in (queries, gallery))
+    elif typed == "mx4":
+        q, g = (t if isinstance(t, Mx4Rows) else quantize_mx4(t) for t in (queries, gallery))
     else:
         q, g = _rows16(queries, typed[1]), _rows16(gallery, typed[1])
     nq, E = q.shape
     ng = g.shape[0]
     if g.shape[1] != E:
         raise ValueError(f"queries have {E} features, the gallery {g.shape[1]}")
-    if typed == "mx8":
+    if typed == "mx8" or typed == "mx4":
         if E % 128:
-            raise ValueError(f"MX-FP8 operands are searched with E a multiple of 128, not {E}")
-        return nq, ng, E, q.device, f"lpi_search_{form}_mx8", (nq, ng, E, q.codes, q.codes.stride(0), q.scales, q.scales.stride(0),
-                                                                g.codes, g.codes.stride(0), g.scales, g.scales.stride(0))
+            raise ValueError(f"MX-FP{typed[2]} operands are searched with E a multiple of 128, not {E}")
+        return nq, ng, E, q.device, f"lpi_search_{form}_{typed}", (nq, ng, E, q.codes, q.codes.stride(0), q.scales, q.scales.stride(0),
+                                                                    g.codes, g.codes.stride(0), g.scales, g.scales.stride(0))
     if typed is None:
         return nq, ng, E, q.device, f"lpi_search_{form}", (nq, ng, E, q, q.stride(0), g, g.stride(0))
     return nq, ng, E, q.device, f"lpi_search_{form}_t", (typed[0], nq, ng, E, q, q.stride(0), g, g.stride(0))
@@ -170,7 +247,8 @@ def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
     """-> (idx int32 [nq, k], val f32 [nq, k]), 1 <= k <= 256: per query row the k largest scores in the order (value descending, then index
     descending), lpi_topk's.  ``col_base`` is added to the indices.  ``into`` = the (idx, val) of earlier calls over other gallery chunks: the lists are merged in
     place and returned.  ``operands``: None | "f32" (anything not f32 is cast to f32) | "bf16" | "f16" (both operands end in that type; val stays f32)
-    | "mx8" (an Mx8Rows is read in place, a float tensor is quantised once; val = the scores of the quantised rows)."""
+    | "mx8" (an Mx8Rows is read in place, a float tensor is quantised once; val = the scores of the quantised rows) | "mx4" (the same with an Mx4Rows:
+    a coarse list, to be re-ranked)."""
     typed = _operands(operands)
     nq, ng, E, dev, name, lead = _prepare(queries, gallery, typed, "topk")
     if into is None:
@@ -190,7 +268,7 @@ def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
 
 def gt_rank(queries, gallery, gt, *, operands=None):
     """-> rank int32 [nq]: lpi_retrieval_rank of the score matrix the two feature sets would give, over the ground-truth list ``gt`` int32 [nq] or
-    [nq, gt_per_row] (entries < 0 are padding).  ``operands`` as in ``topk``."""
+    [nq, gt_per_row] (entries < 0 are padding).  ``operands`` as in ``topk``, without "mx4": MX-FP4 scores are no basis for a metric."""
     typed = _operands(operands)
     nq, ng, E, dev, name, lead = _prepare(queries, gallery, typed, "rank")
     gt = torch.as_tensor(gt).to(device=dev, dtype=torch.int32).reshape(nq, -1).contiguous()
@@ -208,12 +286,14 @@ def rerank(queries, gallery, cand, k=None, *, operands=None):
     to kc), scored on the operands themselves, in ``topk``'s order.  An entry outside [0, ng) is padding (the -1 of a short list), an index that occurs
     several times in a row counts once (lists of several coarse passes may simply be concatenated), unfilled slots are (-1, -inf) and come last.
     ``val`` has the bits ``topk`` with the same ``operands`` returns for the pair, so a re-ranked list compares with ``==`` against a searched one.
-    ``operands``: None | "f32" | "bf16" | "f16" with ``topk``'s in-place rules; MX-FP8 is not a re-rank type (the second stage exists for the better
-    operand).  An int32 ``cand`` with unit inner stride is read in place, a row-strided view included; anything else is converted once.  One launch,
+    ``operands``: None | "f32" | "bf16" | "f16" with ``topk``'s in-place rules; MX-FP8 and MX-FP4 are not re-rank types (the second stage exists for the
+    better operand).  An int32 ``cand`` with unit inner stride is read in place, a row-strided view included; anything else is converted once.  One launch,
     no workspace."""
     typed = _operands(operands)
     if typed == "mx8" or isinstance(queries, Mx8Rows) or isinstance(gallery, Mx8Rows):
         raise ValueError('rerank scores f32 / bf16 / f16 operands: MX-FP8 ("mx8", an Mx8Rows) is a coarse type, not a re-rank type')
+    if typed == "mx4" or isinstance(queries, Mx4Rows) or isinstance(gallery, Mx4Rows):
+        raise ValueError('rerank scores f32 / bf16 / f16 operands: MX-FP4 ("mx4", an Mx4Rows) is a coarse type, not a re-rank type')
     if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype.is_floating_point or cand.dtype in (torch.bool, torch.complex64, torch.complex128):
         raise ValueError("cand = an integer tensor [nq, kc]")
     if queries.dim() != 2 or gallery.dim() != 2:
@@ -254,17 +334,24 @@ def topk_reranked(queries, gallery, k, *, coarse="mx8", candidates=None, coarse_
     operands=coarse)`` (the narrow kernels up to 16 candidates, the wide ones above), then ``rerank(queries, gallery, its idx, k, operands=operands)``.
     Where the coarse list of a row holds the row's exact top k, the row's result is ``topk(queries, gallery, k, operands=operands)``'s, bit for bit; a
     neighbour the coarse pass ranks below ``candidates`` is lost.  ``candidates`` defaults to min(ng, 256, max(4 k, 32)), a choice, not a measurement
-    (DESIGN.md has what k, 2 k and 4 k recover), and must satisfy k <= candidates <= min(ng, 256).  ``coarse_gallery`` / ``coarse_queries``: the
-    ``Mx8Rows`` (``quantize_mx8``) or the 2-byte copy of the operand, held by the caller across calls; WITHOUT them the operand is quantised or cast
-    again on every call, which for the gallery costs a pass over it and its coarse copy in memory each time.  A coarse gallery searched in chunks
+    (DESIGN.md has what k, 2 k and 4 k recover), and must satisfy k <= candidates <= min(ng, 256).  With ``coarse="mx4"`` the default is
+    min(ng, 256, max(16 k, 128)): a choice taken from a CPU emulation of the format on random unit rows ("MX-FP4 operands": at k = 10 the f32
+    top 10 lay inside the MX-FP4 top 128 for every row tried, inside the top 64 for 98 - 100 %), to be revisited with the measured table: at
+    123 287 x 616 767 random unit rows 128 candidates lost a neighbour on 0.18 % of the rows and 256 on none, so pass ``candidates=256`` where every
+    row matters.
+    ``coarse_gallery`` / ``coarse_queries``: the ``Mx8Rows`` (``quantize_mx8``), the ``Mx4Rows`` (``quantize_mx4``) or the 2-byte copy of the operand,
+    held by the caller across calls; WITHOUT them the operand is quantised or cast again on every call, which for the gallery costs a pass over it and
+    its coarse copy in memory each time.  A coarse gallery searched in chunks
     composes with ``rerank`` directly: ``topk(..., col_base=, into=)`` over the chunks, then one ``rerank`` on the whole exact gallery."""
-    _operands(coarse)      # an unknown name is refused here, before anything else
-    if _operands(operands) == "mx8":
-        raise ValueError('the re-rank operands are f32 / bf16 / f16, not "mx8"')
+    ctyped = _operands(coarse)      # an unknown name is refused here, before anything else
+    if _operands(operands) in ("mx8", "mx4"):
+        raise ValueError(f'the re-rank operands are f32 / bf16 / f16, not "{operands}"')
     ng = gallery.shape[0]
     k = int(k)
     top = min(ng, _KWIDE)
-    candidates = min(top, max(4 * k, 32)) if candidates is None else int(candidates)
+    if candidates is None:
+        candidates = min(top, max(16 * k, 128) if ctyped == "mx4" else max(4 * k, 32))
+    candidates = int(candidates)
     if not 1 <= k <= candidates <= top:
         raise ValueError(f"1 <= k <= candidates <= min(ng, {_KWIDE}) = {top}, not k = {k}, candidates = {candidates}")
     cq = queries if coarse_queries is None else coarse_queries

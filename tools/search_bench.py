@@ -16,7 +16,7 @@ kernels sum K in another order) and the count is recorded.  The bf16 / f16 arms 
 timed region and before the peak is taken, as a gallery held in that type is; their ranks are compared with the f32 streamed arm's, which is the
 baseline their time is read against in the same run (rounding the rows moves scores by up to 2u + u^2, so ranks differ: the count is a description).
 
-    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8 | --wide | --rerank]
+    python tools/search_bench.py [--rounds 5] [--steps 5] [--no-large] [--mx8 | --wide | --rerank | --mx4]
 
 writes profiles/search_stream_2byte.json (profiles/search_stream.json is the record of the f32 arms alone, before the 2-byte arms existed).
 
@@ -34,6 +34,12 @@ on the f32 rows) at k = 10 with kc = k, 2 k and 4 k, beside the f32 streamed top
 unchanged code and the baseline, and the re-rank launch alone on a held candidate list; interleaved at i2t, each arm once at train unless --no-large.
 Per arm: time, peak bytes, and the share of rows whose final (idx, val) equals the f32 top-10's bit for bit.  It writes
 profiles/search_stream_rerank.json only.
+
+--mx4: the two-stage search with an MX-FP4 coarse pass (coarse="mx4" on Mx4Rows quantised ONCE and held, csrc/search_mx4.hip) at kc = 64, 128 and 256, beside
+the f32 streamed top-10 and the MX-FP8 two-stage search at kc = 40 of the same run, which are the parent's unchanged code and the baseline; k = 10,
+interleaved at i2t (the record of this mode was taken with --rounds 3 --steps 3), each arm once at train unless --no-large.  Per arm: time, peak bytes
+and the share of rows whose final (idx, val) equals the f32 top-10's bit for bit; and the gallery's bytes per type.  It writes
+profiles/search_stream_mx4.json only.
 
 An error ends the process: nothing further is started.  Run it under a time limit."""
 import argparse
@@ -285,6 +291,59 @@ def _rerank_arms(a, res, img, txt, gen):
     print("train", json.dumps(out), flush=True)
 
 
+def _mx4_arms(a, res, img, txt, gen):
+    """--mx4: f32 top-10; MX-FP8 coarse (kc = 40) + f32 re-rank; MX-FP4 coarse (kc = 64, 128, 256) + f32 re-rank.  Coarse operands held."""
+    import torch
+    from lpi_amd import search
+    E, K = img.shape[1], 10
+
+    def build(q, g):
+        q8, g8, q4, g4 = search.quantize_mx8(q), search.quantize_mx8(g), search.quantize_mx4(q), search.quantize_mx4(g)      # once, outside the timed region
+        arms = {"streamed_top10": lambda: search.topk(q, g, K),
+                "two_stage_mx8_kc40": lambda: search.topk_reranked(q, g, K, coarse="mx8", candidates=40, coarse_queries=q8, coarse_gallery=g8)}
+        for kc in (64, 128, 256):
+            arms["two_stage_mx4_kc%d" % kc] = lambda kc=kc: search.topk_reranked(q, g, K, coarse="mx4", candidates=kc, coarse_queries=q4, coarse_gallery=g4)
+        return arms, {"f32": g.shape[0] * E * 4, "bf16": g.shape[0] * E * 2, "mx8": g8.nbytes, "mx4": g4.nbytes}
+
+    def same_rows(r, want):
+        return round(float(((r[0] == want[0]) & (r[1].view(torch.int32) == want[1].view(torch.int32))).all(1).float().mean()), 4)
+
+    q, g = img, txt
+    arms, gbytes = build(q, g)
+    out = _median_rounds(arms, a.rounds, a.steps)
+    want = arms["streamed_top10"]()
+    for name, fn in arms.items():
+        out[name]["peak_bytes"] = _peak(fn)
+        out[name]["vs_streamed_top10"] = round(out[name]["ms"] / out["streamed_top10"]["ms"], 3)
+        out[name]["rows_equal_f32_top10"] = same_rows(fn(), want)
+    out["rows"] = int(q.shape[0])
+    out["gallery_bytes"] = gbytes
+    res["shapes"]["i2t_5000x25000"] = out
+    print("i2t_5000x25000", json.dumps(out), flush=True)
+    if a.no_large:
+        res["shapes"]["train_123287x616767"] = "not measured (--no-large)"
+        return
+    nq, ng = 123287, 616767
+    del q, g, arms, want
+    torch.cuda.empty_cache()
+    q, g = _unit(nq, E, gen), _unit(ng, E, gen)
+    arms, gbytes = build(q, g)
+    out, want = {}, None
+    for name, fn in arms.items():
+        r, ms, peak = _timed_once(fn)
+        out[name] = {"ms": round(ms, 2), "calls_timed": 1, "peak_bytes": peak}
+        if name == "streamed_top10":
+            want = r
+        out[name]["vs_streamed_top10"] = round(ms / out["streamed_top10"]["ms"], 3)
+        out[name]["rows_equal_f32_top10"] = same_rows(r, want)
+        del r
+        print(name, json.dumps(out[name]), flush=True)
+    out["rows"] = nq
+    out["gallery_bytes"] = gbytes
+    res["shapes"]["train_123287x616767"] = out
+    print("train", json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -293,10 +352,11 @@ def main():
     ap.add_argument("--mx8", action="store_true", help="the f32, bf16 and MX-FP8 streamed arms only -> profiles/search_stream_mx8.json")
     ap.add_argument("--wide", action="store_true", help="the wide top-k arms (k = 17, 100, 256) against the matrix path -> profiles/search_stream_wide.json")
     ap.add_argument("--rerank", action="store_true", help="the two-stage search (coarse mx8 / bf16 + f32 re-rank) against the f32 top-10 -> profiles/search_stream_rerank.json")
+    ap.add_argument("--mx4", action="store_true", help="the two-stage search with an MX-FP4 coarse pass against f32 and MX-FP8 -> profiles/search_stream_mx4.json")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "search_stream_rerank.json" if a.rerank else "search_stream_wide.json" if a.wide
+        a.out = os.path.join(REPO, "profiles", "search_stream_mx4.json" if a.mx4 else "search_stream_rerank.json" if a.rerank else "search_stream_wide.json" if a.wide
                              else "search_stream_mx8.json" if a.mx8 else "search_stream_2byte.json")
     import torch
     from lpi_amd import _lib, search
@@ -322,13 +382,15 @@ def main():
         return idx, val
 
     res = {"device": torch.cuda.get_device_name(0), "abi": int(_lib.load().lpi_version()), "rounds": a.rounds, "steps": a.steps, "E": E, "shapes": {}}
-    if a.rerank:
+    if a.mx4:
+        _mx4_arms(a, res, img, txt, gen)
+    elif a.rerank:
         _rerank_arms(a, res, img, txt, gen)
     elif a.wide:
         _wide_arms(a, res, img, txt, gen, matrix_topk, score_matrix)
     elif a.mx8:
         _mx8_arms(a, res, img, txt, gt_i, gt_t, gen)
-    if a.rerank or a.wide or a.mx8:
+    if a.mx4 or a.rerank or a.wide or a.mx8:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
