@@ -71,6 +71,7 @@ extern "C" {
 #define LPI_EPI_QUICKGELU 1   /* u = acc+bias; C = u*sigmoid(1.702u) (model.py:163-165); aux (if given) = d/du[u*sigmoid(1.702u)] — the
                                * DERIVATIVE, evaluated here from the same sigmoid and saved for the backward                          */
 #define LPI_EPI_DQUICKGELU 2  /* C = acc * aux, aux = the derivative the forward saved          (backward of the activation)          */
+                              /* It multiplies by WHATEVER derivative the forward saved: QuickGELU's from the epilogues above, erf-GELU's from lpi_gelu_erf_fwd. */
 #define LPI_EPI_LN 3          /* LayerNorm FOLDED into the GEMM: A is the LayerNorm's INPUT x, B = gamma o W (columns scaled), and
                                * C = rstd[row] * (acc - mean[row] * c1[col]) + bias[col] (alpha must be 1: LPI_EINVAL otherwise), c1[n] = sum_k B[n,k], bias = W beta + b — i.e.
                                * LN(x) W^T + b without ever writing LN(x) (model.py:172-177: ln_1 -> attn in_proj, ln_2 -> c_fc).  `residual`
@@ -179,6 +180,17 @@ int lpi_ln_stats_finalize_pair(int rows0, int d0, const float* part0, int ld0, f
  * sums in another f32 order, half the time (profiles/r06_experiments.md section 10).  Attributed to LPI_GEMM_K_ROWS. */
 int lpi_gemm_nt_rows_supported(int dtype, int M, int N, int K);
 int lpi_gemm_nt_rows(int dtype, int c_dtype, int epilogue, float alpha, int count, const lpi_gemm_desc* descs, void* stream);
+
+/* ---- erf-GELU behind a plain c_fc GEMM (since 623)        replaces: nn.GELU() in the MLP of a checkpoint trained with it (OpenCLIP ViT-B/32, B/16, L/14) ----
+ * IN PLACE: on entry g[rows, cols] (`dtype`, row stride ldg) holds the pre-activation u = c_fc output with its bias; on exit gelu(u) = u Phi(u).  aux (row
+ * stride ldaux) receives gelu'(u) = Phi(u) + u phi(u), the tile LPI_EPI_DQUICKGELU multiplies by; aux == NULL: not wanted (ldaux is not looked at), and the
+ * bits written to g are the same.  (dtype, aux_dtype) = (LPI_F32, LPI_F32) | (LPI_BF16, LPI_BF16) | (LPI_F16, LPI_BF16) — the GEMM epilogues' rule for the
+ * saved derivative — anything else is LPI_EINVAL, with or without aux.  f32 arithmetic in registers: Phi(u) = erfc(-u / sqrt 2) / 2 (erfc, not 1 + erf: the
+ * negative tail keeps its relative accuracy), phi(u) = exp(-u^2 / 2) / sqrt(2 pi).  Every finite u the type holds gives finite values (+-0, a square that
+ * overflows, the f16 / bf16 / f32 maxima); NaN / Inf are out of contract.  A lane moves 16 bytes: cols a positive multiple of 8, ldg and ldaux >= cols and
+ * multiples of 8 elements, g and aux 16-byte aligned, rows >= 1 — LPI_EINVAL before any launch otherwise.  Only the rows x cols elements are read or written;
+ * the ld gaps are never touched.  One launch. */
+int lpi_gelu_erf_fwd(int dtype, int aux_dtype, long rows, int cols, void* g, long ldg, void* aux, long ldaux, void* stream);
 
 /* ---- a5: LayerNorm (fp32 statistics, eps 1e-5)            replaces: models/clip/model.py:154-160 ------
  * x_dtype: storage type of the residual stream x — LPI_F32, or LPI_F16 in bf16 mode (statistics and arithmetic are f32 either way).

@@ -52,6 +52,7 @@ SIGNATURES = {
     "lpi_ln_stats_finalize_pair": [_I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P, _F, _P],
     "lpi_gemm_nt_rows": [_I, _I, _I, _F, _I, _P, _P],
     "lpi_gemm_nt_rows_supported": [_I, _I, _I, _I],
+    "lpi_gelu_erf_fwd": [_I, _I, _L, _I, _P, _L, _P, _L, _P],      # erf-GELU in place behind a plain c_fc GEMM (act.hip, EngineOptions.erf_gelu)
     # MX-FP8 forward (gemm_mx8.hip, mx8_rows.hip)
     "lpi_gemm_mx8_ok": [_I, _I, _I],
     "lpi_gemm_nt_mx8": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _F, _P],
@@ -186,7 +187,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 622
+EXPECTED_ABI = 623
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -11,6 +11,11 @@ converts to fp16 (``convert_weights``, :394-415) and loads.  There is no network
   * ``ParamTree``              an nn.Module tree whose ``state_dict()`` keys are exactly the given dotted names — how SliNet registers the frozen CLIP
                                tensors, so that ``count_parameters(model._network)`` (trainer.py:50-51) sees 149.78 M like the reference's network.
 
+OpenCLIP's ViT-B/32, B/16 and L/14 state dicts use the same parameter names and are taken as they are: a non-parameter entry such as their persistent
+``attn_mask`` buffer is carried along and read by nothing (the shape inference and the engine ask for their tensors by name).  What such a dict does NOT
+say is the MLP activation: OpenAI's weights were trained with QuickGELU, OpenCLIP's with ``nn.GELU`` (erf), and the names and shapes are identical — the
+activation cannot be inferred here.  The config says it: ``activation: "gelu"`` (``EngineOptions.erf_gelu``; default ``"quick_gelu"``).
+
 The engine keeps its own operand copies (bf16 / fp16 / f32, some transposed); fp16 checkpoints are widened to f32 first (exact), so a checkpoint that
 went through ``convert_weights`` gives the same operands as its f32 original wherever the mode rounds to fp16 / bf16 anyway.
 """

@@ -91,7 +91,13 @@ class EngineOptions:
         to lpi_gemm_nt go out with the operand code LPI_F32X3: every operand element is split in registers into hi + lo bf16 and a product is
         hi.hi + hi.lo + lo.hi on the bf16 matrix instruction with f32 accumulation — about 2^-16 per product where f32 has 2^-24 and bf16 2^-8.  Memory
         formats stay f32: weights (no extra copy), attention, LayerNorm, row kernels, the few-row GEMMs (lpi_gemm_nt_rows), losses and the optimiser are
-        the f32 mode's, workspace and launch count unchanged.  f32 mode only (ValueError with 'bf16' / 'f16')."""
+        the f32 mode's, workspace and launch count unchanged.  f32 mode only (ValueError with 'bf16' / 'f16').
+    erf_gelu: the MLP activation is nn.GELU's u Phi(u) (erf) instead of QuickGELU's u sigmoid(1.702 u) — what the OpenCLIP ViT-B/32, B/16 and L/14 checkpoints were
+        trained with (the parameter names and shapes are the same: nothing in a state dict says which).  c_fc goes out as a plain GEMM (LPI_EPI_NONE, or LPI_EPI_LN
+        with the fold) and lpi_gelu_erf_fwd (csrc/act.hip) rewrites its output in place and, in a training forward, saves gelu'(u) in the buffer the QuickGELU
+        epilogue fills: the backward is unchanged, its d c_proj epilogue multiplies by whatever derivative the forward saved.  One more launch per tower and block
+        in the forward and one more pass over the [M, 4 d] tile; every mode and both forwards (train=True / False).  Not with mx8_forward (ValueError: that path's
+        c_fc writes MX-FP8 straight from its QuickGELU epilogue)."""
     residual_f16: bool = True
     ln_fold: int = 2
     rowstats: int = 2
@@ -104,10 +110,13 @@ class EngineOptions:
     mx8_forward: bool = False
     mx8_tile256: bool = True
     gemm_bf16x3: bool = False
+    erf_gelu: bool = False
 
     def __post_init__(self):
         if self.ln_fold not in (0, 1, 2) or self.rowstats not in (0, 1, 2):
             raise ValueError("ln_fold and rowstats are 0, 1 or 2")
+        if self.erf_gelu and self.mx8_forward:
+            raise ValueError("erf_gelu does not combine with mx8_forward: the MX-FP8 c_fc writes c_proj's operand straight from its QuickGELU epilogue")
         if not isinstance(self.pixel_norm, str):      # a pair from a config file is a list of lists: stored as tuples (hashable, like every field)
             try:
                 mean, std = self.pixel_norm
@@ -758,6 +767,13 @@ class Tower:
             return st[0], st[1]
         return None, None
 
+    def _erf_act(self, tag, g, u, rows):
+        """EngineOptions.erf_gelu: the launch behind a plain c_fc GEMM — g[:rows] <- gelu(g) in place (erf), u[:rows] <- gelu'(g) if the forward saves it (u = None:
+        a train=False forward).  A SoloReq under a tag both towers share: the two go out one after the other."""
+        cols = g.shape[1]
+        return SoloReq(tag, lambda: call("lpi_gelu_erf_fwd", _cdt(g), BF16 if g.dtype != torch.float32 else F32, rows, cols, g, g.stride(0), u,
+                                         u.stride(0) if u is not None else 0, _stream()))
+
     def forward_gen(self, ws, prompts=None, prompt_bstride=0, depth=1, train=True, pool_idx=None, ln1_ready=False):
         """GENERATOR (see GemmReq): runs the blocks over ws['x'][0], yielding its GEMMs; returns the POOLED rows of the output residual stream, [Bp, d] f32: row b is token
         pool_idx[b] of sample b (None: token 0 = CLS).  Only those rows are ever read by the heads (model.py:255,
@@ -767,6 +783,7 @@ class Tower:
         sp, dt, xdt, s = self.spec, self.dt, self.xdt, _stream()
         mdt = _gemm_code(dt, self.opt)      # what the GemmReqs carry: dt, or F32X3 (EngineOptions.gemm_bf16x3)
         POOLED_LAST, LN_FOLD = self.opt.pooled_last, self.opt.ln_fold
+        ERF = self.opt.erf_gelu      # c_fc as a plain GEMM + lpi_gelu_erf_fwd behind it (EngineOptions.erf_gelu)
         d, H = sp.width, sp.heads
         B, L, Mp, M = ws["B"], ws["L"], ws["Mp"], ws["M"]
         rs = ws["rs"]                                  # ragged batch: row starts (device int32 [B+1]); None = B x L rows
@@ -845,7 +862,11 @@ class Tower:
                 yield GemmReq(f"{lt}.cout", mdt, ws["c_ctx"], blk["out"].w, ws["c_xmid"], Bp, d, d, bias=blk["out"].b, residual=ws["c_xin"], m_real=B)
                 yield RowReq(f"{lt}.pln2", [_lib.row_job(_lib.ROWOP_POOL_LN_FWD, B=B, L=1, d=d, dt_a=F32, dt_b=dt, a=ws["c_xmid"], gamma=blk["ln_2.w"],
                                                          beta=blk["ln_2.b"], out=ws["c_h"], ld_c=d, mean=cst[0], rstd=cst[1])])
-                yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=ws["c_u"], m_real=B)
+                if ERF:
+                    yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, m_real=B)
+                    yield self._erf_act(f"{lt}.cact", ws["c_g"], ws["c_u"], B)
+                else:
+                    yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=ws["c_u"], m_real=B)
                 yield GemmReq(f"{lt}.cproj", mdt, ws["c_g"], blk["proj"].w, ws["c_xout"], Bp, d, 4 * d, bias=blk["proj"].b, residual=ws["c_xmid"], m_real=B)
                 return ws["c_xout"]
             if fold:
@@ -871,10 +892,18 @@ class Tower:
                 fl = blk["fc_ln"]
                 if not ln2_stats:
                     yield LnReq(f"{lt}.ln2", "fwd", (dt, xdt), M, d, xmid, d, None, None, None, 0, st[2], st[3], optional=True)
-                yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, 4 * d, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN_QUICKGELU, aux=u, m_real=M)
+                if ERF:
+                    yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, 4 * d, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN, m_real=M)
+                else:
+                    yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, 4 * d, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN_QUICKGELU, aux=u, m_real=M)
             else:
                 yield LnReq(f"{lt}.ln2", "fwd", (dt, xdt), M, d, xmid, d, blk["ln_2.w"], blk["ln_2.b"], ws["h"], d, st[2], st[3], optional=True)
-                yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=u, m_real=M)
+                if ERF:
+                    yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, m_real=M)
+                else:
+                    yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=u, m_real=M)
+            if ERF:
+                yield self._erf_act(f"{lt}.act", ws["g"], u, M)
             yield GemmReq(f"{lt}.proj", mdt, ws["g"], blk["proj"].w, x_out, Mp, d, 4 * d, **proj_kw)
             if have_ln1:
                 nst = ws["stat"][nxt]

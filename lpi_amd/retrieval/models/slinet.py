@@ -17,7 +17,8 @@ Differences that are deliberate:
     loss kernels seed the towers' backward, no scalar loss graph) — what SPrompts.train_function runs; forward / cal_loss stay for every other caller;
   * ``text`` may be a list of captions (tokenised on the host like PromptLearner.forward) or a LongTensor [B,77] of ids;
   * extra keys: ``compute_dtype`` ('f32' parity mode | 'bf16' throughput mode), ``honor_prompt_depth`` (default False: the
-    shipped reference never reads ``prompt_depth`` and behaves as depth 1 — SURVEY.md F1), ``r`` (default 4).
+    shipped reference never reads ``prompt_depth`` and behaves as depth 1 — SURVEY.md F1), ``r`` (default 4), ``activation`` ('quick_gelu', the
+    default | 'gelu': nn.GELU's erf form for checkpoints trained with it, e.g. OpenCLIP's — EngineOptions.erf_gelu; see engine_erf_gelu).
 """
 import copy
 import os
@@ -52,6 +53,28 @@ def _resolve_weights(args):
     if known is not None and not same_architecture(known, cfg):
         raise ValueError(f"clip_state_dict holds a {cfg.as_clip_args()} CLIP, backbonename {name!r} names {known.as_clip_args()}")
     return cfg, sd
+
+
+ACTIVATIONS = {"quick_gelu": False, "gelu": True}      # config key `activation` -> EngineOptions.erf_gelu
+
+
+def engine_erf_gelu(args):
+    """The EngineOptions.erf_gelu a config asks for with its `activation` key: 'quick_gelu' (default: OpenAI's CLIP, model.py:163-165) or 'gelu' (nn.GELU, erf:
+    what the OpenCLIP ViT-B/32, B/16 and L/14 checkpoints were trained with).  Nothing in a state dict says which — the names and shapes are the same — so the
+    config has to.  Any other value is a ValueError, so is 'gelu' with engine_options.mx8_forward, and so are engine_options whose erf_gelu says otherwise than the key (an EngineOptions object always carries
+    one): the same rule as `normalize` against engine_options.pixel_norm (utils/data.py engine_pixel_norm)."""
+    act = args.get("activation", "quick_gelu")
+    if not isinstance(act, str) or act not in ACTIVATIONS:
+        raise ValueError(f"activation must be 'quick_gelu' or 'gelu', not {act!r}")
+    want = ACTIVATIONS[act]
+    eo = args.get("engine_options")
+    given = eo.get("erf_gelu") if isinstance(eo, dict) else getattr(eo, "erf_gelu", None)
+    if given is not None and bool(given) != want:
+        raise ValueError(f"activation is {act!r} but engine_options.erf_gelu is {given!r}: the config key decides the MLP activation, the two must agree")
+    mx8 = eo.get("mx8_forward") if isinstance(eo, dict) else getattr(eo, "mx8_forward", None)
+    if want and mx8:      # EngineOptions refuses the pair too, but a dict of options meets it only when the engine is built: refused here, with the rest
+        raise ValueError("activation 'gelu' does not combine with engine_options.mx8_forward: the MX-FP8 c_fc writes c_proj's operand from its QuickGELU epilogue")
+    return want
 
 
 class _TaskTerm:
@@ -102,6 +125,7 @@ class SliNet(nn.Module):
         if args["visual_dim"] != self.clip_cfg.vision_width or args["textual_dim"] != self.clip_cfg.transformer_width:
             raise ValueError("visual_dim / textual_dim do not match the backbone")
         self.compute_dtype = args.get("compute_dtype", "f32")
+        self.erf_gelu = engine_erf_gelu(args)      # config key `activation`: refused HERE, before anything is built
         self.depth = int(args["prompt_depth"]) if args.get("honor_prompt_depth", False) else 1
         self.prompts = nn.ModuleList([
             DecomposedPrompt(9, args["prompt_length"], args["visual_dim"], args["textual_dim"], r=args.get("r", 4))   # slinet.py:44-47
@@ -134,6 +158,8 @@ class SliNet(nn.Module):
             norm = engine_pixel_norm(self.args, self.clip_cfg.image_resolution)
             if norm is not None and not isinstance(eo, EngineOptions):
                 eo = dict(eo or {}, pixel_norm=norm)
+            if self.erf_gelu and not isinstance(eo, EngineOptions):      # `activation`: 'gelu' (an EngineOptions object agrees already: engine_erf_gelu)
+                eo = dict(eo or {}, erf_gelu=True)
             if isinstance(eo, dict):
                 eo = EngineOptions.from_env(**eo)
             self.engine = DualEncoder(self.clip_cfg, self.clip_model.state_dict(), dtype=self.compute_dtype, device=dev, n_ctx=self.cfg.NCTX, options=eo)
