@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .synth import ClipConfig
+from .synth import CONFIGS, ClipConfig
 
 _SCALARS = ("input_resolution", "context_length", "vocab_size")      # model.py:443-445
 
@@ -76,9 +76,10 @@ def load_clip_state_dict(src, trusted: bool = False) -> dict:
     return sd
 
 
-def infer_config(sd: dict, name: str = "checkpoint") -> ClipConfig:
+def infer_config(sd: dict, name: str = "checkpoint", vision_head_width: int | None = None) -> ClipConfig:
     """build_model's shape inference (model.py:419-441).  Raises CheckpointError for ModifiedResNet checkpoints (no ``visual.proj``) and for tensors
-    the ViT path needs but the dict lacks."""
+    the ViT path needs but the dict lacks.  A state dict does not say how wide its vision heads are: ``vision_head_width`` None takes the width of the
+    known config called ``name``, else 64 (build_model's width // 64); a width that does not divide the vision width is a CheckpointError."""
     if "visual.proj" not in sd:
         rn = any(k.startswith("visual.layer1") for k in sd)
         raise CheckpointError(("this is a ModifiedResNet (RN50-style) CLIP checkpoint: only the ViT backbones of the LPI configs are built"
@@ -101,12 +102,16 @@ def infer_config(sd: dict, name: str = "checkpoint") -> ClipConfig:
     transformer_width = shape("ln_final.weight")[0]
     transformer_heads = transformer_width // 64
     transformer_layers = len(set(k.split(".")[2] for k in sd if k.startswith("transformer.resblocks")))
+    if vision_head_width is None:
+        vision_head_width = CONFIGS[name].vision_head_width if name in CONFIGS else 64
+    if isinstance(vision_head_width, bool) or not isinstance(vision_head_width, int) or vision_head_width <= 0 or vision_width % vision_head_width:
+        raise CheckpointError(f"vision head width {vision_head_width!r} does not divide the checkpoint's vision width {vision_width}")
     return ClipConfig(name, embed_dim, vision_patch_size * grid, vision_layers, vision_width, vision_patch_size, context_length, vocab_size,
-                      transformer_width, transformer_heads, transformer_layers)
+                      transformer_width, transformer_heads, transformer_layers, vision_head_width=vision_head_width)
 
 
 def same_architecture(a: ClipConfig, b: ClipConfig) -> bool:
-    return a.as_clip_args() == b.as_clip_args()
+    return a.as_clip_args() == b.as_clip_args() and a.vision_head_width == b.vision_head_width
 
 
 class ParamTree(nn.Module):

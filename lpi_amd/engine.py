@@ -65,7 +65,9 @@ class EngineOptions:
         mean^2 > 64 var (lpi_rowstat_guard), the engine reads the count without synchronising and drops BOTH towers to rowstats = 0 from the next forward
         on, with a warning (tests/test_round6_gpu.py: rows 12 sigma off zero).
     pooled_last: exact dead-row elimination in the last block (only the pooled token's query / softmax row / out_proj / MLP are evaluated, K and V for
-        every token).  False evaluates the whole block: the reference's literal order, kept for the test that holds the two equal.
+        every token).  False evaluates the whole block: the reference's literal order, kept for the test that holds the two equal.  A tower whose heads are
+        not 64 wide (ViT-H/14's vision tower: 80, csrc/attn_hd.hip) always evaluates the whole block — the pooled-row kernels are kernels for heads of 64 —, and
+        stream_pool and qkv_grouped are off for it too; the other tower keeps what the options say (Tower.pooled_last).  mx8_forward with such a tower: ValueError.
     stream_pool (round 6; needs pooled_last): the last block of a tower with uniform sequences (the vision tower) does not compute K and V at all — with one
         live query per (sample, head), q.k_l = LN1(x_l).(W_k^T q) + const and sum_l p_l v_l = W_v (sum_l p_l LN1(x_l)) + b_v, so two passes over the sample's
         rows of the residual stream replace the [B L, 2 d] projection, its dgrad and the single-query attention over them (lpi_spool_attn_fwd / _bwd,
@@ -604,7 +606,18 @@ class Tower:
         # the kernels take the layout as strides and give the same bits).  The non-causal tower in the 2-byte modes; its last block keeps the
         # interleaved order (the pooled-row kernels read K and V as the rows d .. 3 d of the weight).  EngineOptions.qkv_grouped: OFF by default (in the step
         # it measured nothing: see there).
-        self.qkv_grouped = bool(opt.qkv_grouped and dt != F32 and not spec.causal and spec.layers > 1)
+        # HEADS THAT ARE NOT 64 WIDE (OpenCLIP ViT-H/14's vision tower: 80): attention goes to lpi_attn_hd_fwd / _bwd (csrc/attn_hd.hip: non-causal, uniform
+        # sequences, the interleaved layout) and the tower's last block runs in full with the pooled row gathered behind it — the pooled-row, no-K/V and
+        # head-grouped forms are kernels for heads of 64, so pooled_last, stream_pool and qkv_grouped are OFF for THIS tower (the other keeps its own).
+        if spec.heads <= 0 or spec.width % spec.heads:
+            raise ValueError(f"tower width {spec.width} is no multiple of its {spec.heads} heads")
+        self.hd = spec.width // spec.heads
+        if self.hd != 64 and (spec.causal or _lib.load().lpi_attn_hd_supported(1, spec.heads, self.hd) != 1):
+            raise ValueError(f"heads of {self.hd}: the attention kernels take 64 (any tower) or 80 (a non-causal tower)")
+        if self.hd != 64 and opt.mx8_forward:
+            raise ValueError(f"mx8_forward does not combine with heads of {self.hd}: lpi_layernorm_mx8_fwd takes d <= 1024")
+        self.pooled_last = bool(opt.pooled_last and self.hd == 64)
+        self.qkv_grouped = bool(opt.qkv_grouped and dt != F32 and not spec.causal and spec.layers > 1 and self.hd == 64)
         if opt.mx8_forward and dt == F32:
             raise ValueError("mx8_forward is an option of the 2-byte modes")
         self.mx8 = mx8 = bool(opt.mx8_forward)
@@ -613,7 +626,7 @@ class Tower:
             raise ValueError(f"mx8_forward: tower width {spec.width} is not a multiple of 128")
         d_, H_ = spec.width, spec.heads
         self.qkv_lay = (3 * 64, 64, 64)                                 # (head stride, q -> k -> v stride, ctx head stride) of a grouped block
-        perm = torch.arange(3 * d_).view(3, H_, 64).permute(1, 0, 2).reshape(-1)      # new feature h*192 + w*64 + c  <-  old w*d + h*64 + c
+        perm = torch.arange(3 * d_).view(3, H_, 64).permute(1, 0, 2).reshape(-1) if self.hd == 64 else None      # new feature h*192 + w*64 + c  <-  old w*d + h*64 + c
         for i in range(spec.layers):
             p = f"{prefix}resblocks.{i}."
             grouped = self.qkv_grouped and i < spec.layers - 1
@@ -649,8 +662,13 @@ class Tower:
         """True if the last block of this tower may run without K and V for sequences of L tokens (EngineOptions.stream_pool): a non-causal tower (uniform
         sequences, the pooled token attends to every row) in a 2-byte mode with the fp16 stream, and a shape the kernels take."""
         sp = self.spec
-        return bool(self.opt.stream_pool and self.opt.pooled_last and self.dt != F32 and self.xdt == F16 and not sp.causal and len(self.blocks) > 1
+        return bool(self.opt.stream_pool and self.pooled_last and self.dt != F32 and self.xdt == F16 and not sp.causal and len(self.blocks) > 1
                     and _lib.load().lpi_spool_attn_supported(int(L), sp.heads, sp.width) == 1)
+
+    @staticmethod
+    def _hd_uniform(rs, pre):
+        if rs is not None or pre:
+            raise ValueError("a tower whose heads are not 64 wide takes uniform sequences only (no packed batch, no shared prefix)")
 
     def _check_depth(self, prompts, depth):
         """model.py:191 indexes prompts[:, layer_id]: the reference raises IndexError past the stack; so do we (before any kernel)."""
@@ -694,7 +712,7 @@ class Tower:
         for k in [k for k in self._ws if k[1] == train]:
             del self._ws[k]
         d, H, nl = self.spec.width, self.spec.heads, self.spec.layers
-        POOLED_LAST = self.opt.pooled_last
+        POOLED_LAST = self.pooled_last
         Lreal, L = L, max(L, cap or L)
         Mp = _pad(B * L, 256)      # whole 256x256 GEMM tiles (the 128x128 kernel takes any multiple of 128)
         Bp = _pad(B)
@@ -782,7 +800,7 @@ class Tower:
         prompts: f32 tensor whose element (b, layer, p, :) sits at  b*prompt_bstride + (layer*P + p)*d."""
         sp, dt, xdt, s = self.spec, self.dt, self.xdt, _stream()
         mdt = _gemm_code(dt, self.opt)      # what the GemmReqs carry: dt, or F32X3 (EngineOptions.gemm_bf16x3)
-        POOLED_LAST, LN_FOLD = self.opt.pooled_last, self.opt.ln_fold
+        POOLED_LAST, LN_FOLD = self.pooled_last, self.opt.ln_fold
         ERF = self.opt.erf_gelu      # c_fc as a plain GEMM + lpi_gelu_erf_fwd behind it (EngineOptions.erf_gelu)
         d, H = sp.width, sp.heads
         B, L, Mp, M = ws["B"], ws["L"], ws["Mp"], ws["M"]
@@ -874,7 +892,11 @@ class Tower:
                 yield GemmReq(f"{lt}.qkv", F16, x_in, ql.w, qkv, Mp, 3 * d, d, bias=ql.c2, residual=lnb[0], ldr=ln_ld, epi=EPI_LN, m_real=M)
             else:
                 yield GemmReq(f"{lt}.qkv", mdt, ws["h"], blk["qkv"].w, qkv, Mp, 3 * d, d, bias=blk["qkv"].b, m_real=M)
-            yield AttnFwdReq(f"{lt}.attn", dt, B, L, rs, H, qkv, 3 * d, ctx, d, lse, int(sp.causal), pre, self.qkv_lay if blk["grouped"] else None)
+            if self.hd != 64:      # its own launch under the block's attention tag: the partner's forward goes out alone
+                self._hd_uniform(rs, pre)
+                yield SoloReq(f"{lt}.attn", lambda qkv=qkv, ctx=ctx, lse=lse: call("lpi_attn_hd_fwd", dt, B, L, H, self.hd, qkv, 3 * d, ctx, d, lse, _stream()))
+            else:
+                yield AttnFwdReq(f"{lt}.attn", dt, B, L, rs, H, qkv, 3 * d, ctx, d, lse, int(sp.causal), pre, self.qkv_lay if blk["grouped"] else None)
             ln2_stats = rowstats >= 1 and LN_FOLD >= 2 and not (i == len(self.blocks) - 1 and POOLED_LAST)
             if ln2_stats:      # x + attn(..) and the slot sums of its rows in one epilogue; ln_2's mean / rstd from them
                 yield GemmReq(f"{lt}.out", mdt, ctx, blk["out"].w, xmid, Mp, d, d, bias=blk["out"].b, residual=x_in, m_real=M, epi=EPI_RES_ROWSTATS,
@@ -923,7 +945,7 @@ class Tower:
         sp, dt, xdt, s = self.spec, self.gdt, self.xdt, _stream()        # dt: the BACKWARD's operand / storage type from here on
         mdt = _gemm_code(dt, self.opt)
         adt = F16 if self.dt == F16 else dt       # attention backward: F16 = "saved q, k, v, ctx are fp16; gradients and operands bf16"
-        POOLED_LAST, L0_PROMPT_ROWS = self.opt.pooled_last, self.opt.l0_prompt_rows
+        POOLED_LAST, L0_PROMPT_ROWS = self.pooled_last, self.opt.l0_prompt_rows
         d, H = sp.width, sp.heads
         B, L, Mp, M = ws["B"], ws["L"], ws["Mp"], ws["M"]
         rs = ws["rs"]                                  # ragged batch: row starts (device int32 [B+1]); None = B x L rows
@@ -986,7 +1008,10 @@ class Tower:
             yield GemmReq(f"{lt}.dout", mdt, dxT, blk["out"].wt, dctx, Mp, d, d, m_real=M)                                         # d out_proj
             l0_rows = i == 0 and L0_PROMPT_ROWS and prompts is not None and 0 < P <= 32 and len(self.blocks) > 1
             # first block: only dQ / dK / dV of the prompt rows 1 .. P are read below -> the attention backward skips the row blocks behind them
-            if pre:
+            if self.hd != 64:      # every row of dqkv is written (no rows_needed form)
+                self._hd_uniform(rs, pre)
+                call("lpi_attn_hd_bwd", adt, B, L, H, self.hd, qkv, 3 * d, ctx, d, dctx, d, lse, ws["delta"], dqkv, 3 * d, s)
+            elif pre:
                 call("lpi_attn_bwd_shared", adt, B, L, rs, pre, (1 + P) if l0_rows else L, H, qkv, 3 * d, ctx, d, dctx, d, lse, ws["delta"], dqkv, 3 * d,
                      ws["shared_dkv"], s)
             elif blk["grouped"]:
@@ -1006,7 +1031,7 @@ class Tower:
                 yield RowReq(f"{lt}.gath", [_lib.row_job(_lib.ROWOP_GATHER_BATCH_ROWS, B=Bq, L=Lq, row_start=rsq, row0=1, P=P, d=3 * d * esz // 16, a=dqkv,
                                                          ld_a=3 * d * esz // 16, out=pq, ld_c=3 * d * esz // 16)])
                 yield GemmReq(f"{lt}.dqkv_p", mdt, pq, blk["qkv"].wt, ph, _pad(Bq * P, 256), d, 3 * d, m_real=Bq * P)
-                if dt == BF16 and xdt == F16 and d % 8 == 0:      # the 16-byte half-wave kernel, with the towers' launches paired
+                if dt == BF16 and xdt == F16 and d % 8 == 0 and d <= 1024:      # the 16-byte half-wave kernel (LPI_ROWOP_LN_BWD_ROWS_H16: d <= 1024), with the towers' launches paired
                     yield RowReq(f"{lt}.dln1p", [_lib.row_job(_lib.ROWOP_LN_BWD_ROWS_H16, B=Bq, L=Lq, row_start=rsq, row0=1, P=P, d=d, a=ph, ld_a=d, b=x_in, ld_b=d,
                                                               gamma=blk["ln_1.w"], mean_in=st[0], rstd_in=st[1], out2=dxT, ld_c=d, flag=1)])
                 else:
@@ -1033,6 +1058,8 @@ class DualEncoder:
         self.cfg = cfg
         self.opt = options if options is not None else EngineOptions.from_env()
         self.opt.check_dtype(dtype)
+        if self.opt.mx8_forward and cfg.vision_width // cfg.vision_heads != 64:      # (before anything touches the GPU; Tower.__init__ says it again)
+            raise ValueError(f"mx8_forward does not combine with vision heads of {cfg.vision_width // cfg.vision_heads}: lpi_layernorm_mx8_fwd takes d <= 1024")
         self.device = torch.device(device)
         _require_gpu(self.device)
         _lib.load()

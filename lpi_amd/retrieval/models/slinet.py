@@ -42,16 +42,21 @@ def _resolve_weights(args):
     ``backbonename`` must agree with it where this package knows the name.  Without a checkpoint: the synthetic weights of the named config."""
     name = args["backbonename"]
     src = args.get("clip_state_dict")
-    if src is None:
-        if name not in synth.CONFIGS:
-            raise KeyError(name)
-        cfg = synth.CONFIGS[name]
-        return cfg, synth.clip_state_dict(cfg)
-    sd = load_clip_state_dict(src, trusted=bool(args.get("clip_checkpoint_trusted", False)))
-    cfg = infer_config(sd, name)
+    hw = args.get("vision_head_width")      # a state dict does not say its vision heads' width (OpenCLIP ViT-H/14: 80); None: the named config's, else 64
+    if hw is not None and (isinstance(hw, bool) or not isinstance(hw, int)):
+        raise ValueError(f"vision_head_width must be an integer, not {hw!r}")
     known = synth.CONFIGS.get(name)
+    if src is None:
+        if known is None:
+            raise KeyError(name)
+        if hw is not None and hw != known.vision_head_width:
+            raise ValueError(f"vision_head_width holds {hw}, backbonename {name!r} names vision heads of {known.vision_head_width}")
+        return known, synth.clip_state_dict(known)
+    sd = load_clip_state_dict(src, trusted=bool(args.get("clip_checkpoint_trusted", False)))
+    cfg = infer_config(sd, name, vision_head_width=hw)
     if known is not None and not same_architecture(known, cfg):
-        raise ValueError(f"clip_state_dict holds a {cfg.as_clip_args()} CLIP, backbonename {name!r} names {known.as_clip_args()}")
+        raise ValueError(f"clip_state_dict holds a {cfg.as_clip_args()} CLIP with vision heads of {cfg.vision_head_width}, "
+                         f"backbonename {name!r} names {known.as_clip_args()} with vision heads of {known.vision_head_width}")
     return cfg, sd
 
 

@@ -16,7 +16,7 @@ so a real CLIP state dict can be passed to the engine in place of the synthetic 
 from __future__ import annotations
 
 import zlib
-from dataclasses import dataclass, asdict
+from dataclasses import dataclass, asdict, field
 
 import numpy as np
 
@@ -42,22 +42,30 @@ class ClipConfig:
     transformer_width: int
     transformer_heads: int
     transformer_layers: int
+    # not an argument of CLIP.__init__ (model.py:292 computes width // 64): OpenCLIP's ViT-H/14 has vision heads of 80.  A state dict does not say it.
+    vision_head_width: int = field(default=64, kw_only=True)
+
+    def __post_init__(self):
+        if self.vision_head_width <= 0 or self.vision_width % self.vision_head_width:
+            raise ValueError(f"{self.name}: vision width {self.vision_width} is no multiple of the head width {self.vision_head_width}")
 
     @property
     def vision_heads(self) -> int:
-        return self.vision_width // 64
+        return self.vision_width // self.vision_head_width
 
     @property
     def n_patches(self) -> int:
         return (self.image_resolution // self.vision_patch_size) ** 2
 
     def as_clip_args(self):
+        """The ten arguments of the reference's CLIP.__init__ (the head width is not one of them)."""
         d = asdict(self)
         d.pop("name")
+        d.pop("vision_head_width")
         return tuple(d.values())
 
 
-# head_dim is 64 for every CLIP ViT (vision_heads = width // 64, model.py:292)
+# head_dim is 64 for every CLIP ViT of the reference (vision_heads = width // 64, model.py:292)
 VIT_B16 = ClipConfig("ViT-B/16", 512, 224, 12, 768, 16, 77, 49408, 512, 8, 12)
 VIT_L14 = ClipConfig("ViT-L/14", 768, 224, 24, 1024, 14, 77, 49408, 768, 12, 12)
 VIT_L14_336 = ClipConfig("ViT-L/14@336px", 768, 336, 24, 1024, 14, 77, 49408, 768, 12, 12)      # 577 vision tokens: the long-sequence attention kernels
@@ -71,7 +79,14 @@ TINY14 = ClipConfig("tiny14", 128, 28, 2, 256, 14, 77, 49408, 128, 2, 2)   # wid
 # 401 vision tokens (+ prompts) at toy width: the long-sequence attention kernels (csrc/attn_long.hip; ViT-L/14@336px has 577)
 TINY_LONG = ClipConfig("tinyLong", 128, 80, 2, 128, 4, 77, 49408, 128, 2, 2)
 
-CONFIGS = {c.name: c for c in (VIT_B16, VIT_L14, VIT_L14_336, VIT_B32, TINY, TINY14, TINY_LONG)}
+# OpenCLIP ViT-H/14: vision heads of 80 (csrc/attn_hd.hip); the text tower's heads are 64.  The reference cannot build it (model.py:292): the oracle is its yardstick.
+VIT_H14 = ClipConfig("ViT-H/14", 1024, 224, 32, 1280, 14, 77, 49408, 1024, 16, 24, vision_head_width=80)
+# 8 vision heads of 80 at toy size: 640 is the smallest width that is a multiple of both 128 (GEMM tile) and 80; 4 patches + CLS
+TINY_H80 = ClipConfig("tinyH80", 128, 32, 2, 640, 16, 77, 49408, 128, 2, 2, vision_head_width=80)
+# ViT-H/14's widths, patch and resolution with 2 + 2 layers: the real GEMM and row shapes (d = 1280, E = 1024) at a size the CPU oracle runs in seconds
+H14_SHALLOW = ClipConfig("H14-shallow", 1024, 224, 2, 1280, 14, 77, 49408, 1024, 16, 2, vision_head_width=80)
+
+CONFIGS = {c.name: c for c in (VIT_B16, VIT_L14, VIT_L14_336, VIT_B32, TINY, TINY14, TINY_LONG, VIT_H14, TINY_H80, H14_SHALLOW)}
 
 
 def _rng(seed: int, name: str) -> np.random.Generator:
