@@ -262,7 +262,7 @@ int lpi_gather_batch_rows(int dtype, int B, int L, int row0, int P, int cols, co
  * leave rowsum(dctx*ctx) there, the streamed single-pass backward (attention4.hip) keeps it in LDS and does not touch the buffer at L <= 224; at
  * 224 < L <= 288 (two key-window launches) its first launch leaves -rowsum(dctx*ctx)/8 there for the second.  The contents are unspecified after the call.
  * dqkv: [B*L, 3*d] `dtype`.  L <= 288: one workgroup per (sample, head) keeps the head's K and V in LDS (attention.hip, attention4.hip).  Round 6: NON-CAUSAL
- * UNIFORM sequences of 288 < L <= 1024 tokens (ViT-L/14@336px: 577 + prompts) run tiled over the keys with an online softmax (attn_long.hip: forward one
+ * UNIFORM sequences of 288 < L <= 1024 tokens (ViT-L/14@336px: 577 + prompts) run tiled over the keys with an online softmax (attn_long.hip, kernels in attn_walk.h: forward one
  * launch, backward two — dQ + delta, then dK / dV; the backward computes every row, `rows_needed` of the _prefix form is ignored there); causal or ragged
  * sequences of that length are refused with LPI_EINVAL.
  *
@@ -293,7 +293,7 @@ int lpi_attn_bwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, con
 /* ---- Attention for heads that are NOT 64 wide (since 624; lpi_amd/csrc/attn_hd.hip).  replaces: nn.MultiheadAttention of a vision tower with
  * width / heads != 64 (OpenCLIP ViT-H/14: 1280 = 16 heads of 80; the reference's model.py:292 computes width // 64 and cannot build it).  The interleaved
  * layout of lpi_attn_fwd / lpi_attn_bwd with head_dim in place of 64 — qkv, dqkv [B*L, 3*H*head_dim], ctx, dctx [B*L, H*head_dim], lse, delta [B, H, L] f32 —,
- * softmax(q k^T head_dim^-0.5) v, NON-CAUSAL, UNIFORM sequences, at every 1 <= L <= 1024 in the key-walking form of attn_long.hip (forward one launch,
+ * softmax(q k^T head_dim^-0.5) v, NON-CAUSAL, UNIFORM sequences, at every 1 <= L <= 1024 in the key-walking form of attn_walk.h (forward one launch,
  * backward two: dQ + delta, then dK / dV; every row of dqkv is written; deterministic).  dtype as lpi_attn_fwd / lpi_attn_bwd at L > 288: LPI_F32, LPI_BF16,
  * LPI_F16 (backward: saved qkv / ctx fp16, dctx / dqkv bf16).
  * The rule (anything else is LPI_EINVAL before any launch): head_dim == 80 (the one width that is built); B, L, H > 0, L <= 1024, B H <= 65535 (a grid extent);

@@ -1018,7 +1018,7 @@ inline bool bad_attn(int dtype, int B, int L, int H, int ld, int lmax = 288) {
 
 }  // namespace
 
-// attn_long.hip: 288 < L <= 1024, non-causal, uniform sequences — tiled over the keys with an online softmax (ViT-L/14@336px: 577 tokens + prompts)
+// attn_long.hip (the kernels: attn_walk.h at head width 64): 288 < L <= 1024, non-causal, uniform sequences — tiled over the keys with an online softmax (ViT-L/14@336px: 577 tokens + prompts)
 bool lpi_attn_long_ok(int L, int causal, const void* row_start);
 int lpi_attn_long_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, hipStream_t s);
 int lpi_attn_long_bwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx, const float* lse,

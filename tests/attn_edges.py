@@ -9,13 +9,13 @@ P and dq / dk / dv in f64.  Causal, ragged, shared-prefix, rows_needed and poole
 BARS are per element and come from the reference, never from a kernel's output.  u = 2^-9 (bf16), 2^-12 (f16), 2^-24 (f32); one round-to-nearest store into a
 type moves a value by at most 2 u of its magnitude (bf16 keeps 8 significant bits).  Counted roundings (lpi_amd/csrc):
 
-  MFMA kernels (attention.hip attn_fwd_body, attn_long.hip, the 2-byte types):
-    P -> operand type in mma_transposed (pack2_t, attention.hip; attn_long.hip pack2_t<TM>)                              2 u of every addend p_ij v_jc
+  MFMA kernels (attention.hip attn_fwd_body, attn_walk.h, the 2-byte types):
+    P -> operand type in mma_transposed (pack2_t, attention.hip; attn_walk.h pack2_t<TM>)                                2 u of every addend p_ij v_jc
     o * inv -> operand type in store_row16_t / Elem<T>::st4                                                               2 u of |ctx| <= sum_j P_ij |v_jc|
     the row sum lsum adds the UNROUNDED f32 p (attn_softmax.h: ps += s0 + s1 before the pack), 1 / ltot and o * inv are f32: in EPS below
                                                                                                                c_fwd = 4;  f32 operands: nothing is packed,
     the reciprocal and the product are one f32 rounding each: c_fwd = 2 (u = 2^-24)
-  MFMA backwards (attn_bwd_fused_kernel, attn_bwd_dq_kernel / attn_bwd_dkv_kernel, attention4.hip, attn_long.hip; gradients bf16 for both 2-byte modes):
+  MFMA backwards (attn_bwd_fused_kernel, attn_bwd_dq_kernel / attn_bwd_dkv_kernel, attention4.hip, attn_walk.h; gradients bf16 for both 2-byte modes):
     dS = P (dP - delta) / 8 -> bf16, P -> bf16 in mma_transposed                                                          2 u of every addend
     dq / dk / dv -> bf16 in store_row_bf16_t                                                                              2 u of the sum      c_bwd = 4 (f32: 2)
     delta = rowsum(ctx * dctx) reads the STORED ctx (load_row_chunks of ctx in phase A): its error, c_fwd u_ctx sum_c (P |v|)_ic |dctx_ic| =: c_fwd u_ctx D_i,

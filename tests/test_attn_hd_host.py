@@ -104,13 +104,13 @@ def test_supported_agrees_with_the_refusals():
     assert _lib.launch_count() == before
 
 
-def test_attn_hd_kernels_use_no_scratch(tmp_path):
-    """.private_segment_fixed_size == 0 and no VGPR spill for every kernel of attn_hd.hip: nine — forward x (f32, bf16, f16), backward dQ and backward dK / dV x
-    (f32, bf16, fp16-saved with bf16 gradients) — each instantiated at head width 80 only."""
-    src = os.path.join(REPO, "lpi_amd", "csrc", "build", "attn_hd.o")
+def _check_walk_kernels(tmp_path, obj_name, width):
+    """(private segment, VGPR spill) == (0, 0) for the nine kernels of csrc/build/<obj_name>: forward x (f32, bf16, f16), backward dQ and backward dK / dV x (f32,
+    bf16, fp16-saved with bf16 gradients), each an instantiation of attn_walk.h at the one head width `width`."""
+    src = os.path.join(REPO, "lpi_amd", "csrc", "build", obj_name)
     if not os.path.exists(src) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
-        pytest.skip("attn_hd.o not built (run __graft_entry__.build()) or llvm-objdump not available")
-    obj = shutil.copy(src, tmp_path / "attn_hd.o")
+        pytest.skip(obj_name + " not built (run __graft_entry__.build()) or llvm-objdump not available")
+    obj = shutil.copy(src, tmp_path / obj_name)
     subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", str(obj)], check=True, capture_output=True, cwd=tmp_path)
     dev = [p for p in os.listdir(tmp_path) if "amdgcn" in p]
     assert dev
@@ -121,10 +121,20 @@ def test_attn_hd_kernels_use_no_scratch(tmp_path):
         if name and size:
             ks[name.group(1)] = (int(size.group(1)), int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)))
     assert len(ks) == 9, sorted(ks)
-    for kind, n in (("attn_hd_fwd_kernel", 3), ("attn_hd_bwd_dq_kernel", 3), ("attn_hd_bwd_dkv_kernel", 3)):
+    for kind, n in (("attn_walk_fwd_kernel", 3), ("attn_walk_bwd_dq_kernel", 3), ("attn_walk_bwd_dkv_kernel", 3)):
         assert sum(kind in k for k in ks) == n, (kind, sorted(ks))
-    assert all("Li80E" in k for k in ks), sorted(ks)      # the head width is a template argument; 80 is the one instantiation
+    assert all("Li%dE" % width in k for k in ks), sorted(ks)      # the head width is a template argument; one instantiation per object
     assert {k: v for k, v in ks.items() if v != (0, 0)} == {}
+
+
+def test_attn_hd_kernels_use_no_scratch(tmp_path):
+    """.private_segment_fixed_size == 0 and no VGPR spill for every kernel of attn_hd.hip: nine, each instantiated at head width 80 only."""
+    _check_walk_kernels(tmp_path, "attn_hd.o", 80)
+
+
+def test_attn_long_kernels_use_no_scratch(tmp_path):
+    """The same for attn_long.hip, the family's instantiation at head width 64."""
+    _check_walk_kernels(tmp_path, "attn_long.o", 64)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ configuration

@@ -3,10 +3,13 @@
 <build dir>/<name>.o, unbundled as tools/isa_count.py does.)
 
 usage: python3 tools/kernel_diff.py BUILD_DIR_A BUILD_DIR_B [--objects rowops.o,mx8_rows.o,attn_pooled.o] [--json OUT] [--label-a TEXT] [--label-b TEXT]
+                                                         [--rename REGEX=REPL ...]
 
 For the UNION of the listed objects' code objects on each side (a function may move between the objects) it compares, by function name and whatever the order:
 the set of names; each function's disassembly with addresses and raw bytes stripped; each kernel's metadata note (VGPRs, SGPRs, LDS, private segment, kernarg
 size).  Prints every difference and exits 1 if there is any.  It compares text and knows nothing about particular instructions.
+--rename REGEX=REPL (repeatable, applied in order with re.sub) rewrites the function names of BOTH sides and the <name+offset> labels inside the text before
+comparing, so that a kernel whose name changed (a new template argument, another argument struct) meets its predecessor under one key.
 """
 import argparse
 import difflib
@@ -84,6 +87,16 @@ def side(build_dir, objects, tmp):
     return fn, md
 
 
+def renamed(fn, md, rules):
+    def r(name):
+        for pat, repl in rules:
+            name = re.sub(pat, repl, name)
+        return name
+    out = {r(k): re.sub(r"<([^>+]+)", lambda m: "<" + r(m.group(1)), v) for k, v in fn.items()}
+    assert len(out) == len(fn), "--rename maps two functions to one name"
+    return out, {r(k): v for k, v in md.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("a")
@@ -93,7 +106,9 @@ def main():
     ap.add_argument("--show", help="regex: print the text diff of the differing functions it matches")
     ap.add_argument("--label-a", default=None)
     ap.add_argument("--label-b", default=None)
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
     args = ap.parse_args()
+    rules = [r.split("=", 1) for r in args.rename]
     objects = args.objects.split(",")
     tmp = tempfile.mkdtemp()
     try:
@@ -101,6 +116,7 @@ def main():
         fb, mb = side(args.b, objects, tmp)
     finally:
         shutil.rmtree(tmp)
+    (fa, ma), (fb, mb) = renamed(fa, ma, rules), renamed(fb, mb, rules)
     only_a, only_b = sorted(set(fa) - set(fb)), sorted(set(fb) - set(fa))
     differ = []
     for name in sorted(set(fa) & set(fb)):
@@ -120,7 +136,7 @@ def main():
     print(f"{len(fa)} functions in A, {len(fb)} in B, {len(ma)} / {len(mb)} kernels with metadata; {len(only_a)} only in A, {len(only_b)} only in B, {len(differ)} differ")
     if args.json:
         with open(args.json, "w") as f:
-            json.dump({"a": args.label_a or args.a, "b": args.label_b or args.b, "objects": objects, "functions_a": len(fa), "functions_b": len(fb),
+            json.dump({"a": args.label_a or args.a, "b": args.label_b or args.b, "objects": objects, "rename": args.rename, "functions_a": len(fa), "functions_b": len(fb),
                        "only_in_a": only_a, "only_in_b": only_b, "differ": differ}, f, indent=1)
             f.write("\n")
     return 1 if only_a or only_b or differ else 0

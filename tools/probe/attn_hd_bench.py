@@ -1,9 +1,9 @@
-"""The 80-wide-head attention kernels alone (csrc/attn_hd.hip) at ViT-H/14's vision shape — 256 samples x 16 heads, L = 273 (257 tokens + 16 prompts), bf16 —
+"""The 80-wide-head attention kernels alone (csrc/attn_hd.hip: csrc/attn_walk.h at head width 80) at ViT-H/14's vision shape — 256 samples x 16 heads, L = 273 (257 tokens + 16 prompts), bf16 —
 beside the EXISTING 64-wide family at H x 64 and the same L, in the same process: forward and backward TFLOP/s of each, and the ratio.
 
-At L = 273 the existing entry points run the one-workgroup short kernels (L <= 288; attention.hip / attention4.hip), not attn_long.hip — the key-walking family
-the new kernels are modelled on takes 288 < L <= 1024 only.  So a second pair is timed at L = 289, the shortest sequence that reaches attn_long.hip: the new
-family against the form it was written in.  The arms are INTERLEAVED (round by round: hd 80, 64-wide, hd 80, ...), every round on fresh random data, each call
+At L = 273 the existing entry points run the one-workgroup short kernels (L <= 288; attention.hip / attention4.hip), not attn_long.hip — the same key-walking
+family at head width 64 takes 288 < L <= 1024 only.  So a second pair is timed at L = 289, the shortest sequence that reaches attn_long.hip: the two
+instantiations of attn_walk.h side by side.  The arms are INTERLEAVED (round by round: hd 80, 64-wide, hd 80, ...), every round on fresh random data, each call
 timed by HIP events around a few repeats after a warm-up; the median over the rounds is reported and the spread (min .. max) beside it.
 
 usage: python3 tools/probe/attn_hd_bench.py [--json OUT] [--rounds 7] [--batch 256]          (LPI_LIB selects a build)
@@ -76,7 +76,7 @@ def main():
     B, H = a.batch, 16
     out = {"lib": os.environ.get("LPI_LIB", "default build"), "dtype": "bf16", "B": B, "H": H, "rounds": a.rounds, "repeats": a.repeats, "shapes": []}
     for L, what64 in ((273, "short kernels (attention.hip / attention4.hip): what lpi_attn_fwd / _bwd run at L <= 288"),
-                      (289, "key-walking long family (attn_long.hip): what lpi_attn_fwd / _bwd run at 288 < L <= 1024")):
+                      (289, "key-walking family at 64 (attn_long.hip): what lpi_attn_fwd / _bwd run at 288 < L <= 1024")):
         t = {80: ([], []), 64: ([], [])}
         for r in range(a.rounds):
             for hd in (80, 64):      # interleaved, fresh data every round
