@@ -290,17 +290,20 @@ int lpi_attn_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, voi
 int lpi_attn_bwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx,
                  const void* dctx, int lddctx, const float* lse, float* delta, void* dqkv, int lddqkv,
                  int causal, void* stream);
-/* ---- Attention for heads that are NOT 64 wide (since 624; lpi_amd/csrc/attn_hd.hip).  replaces: nn.MultiheadAttention of a vision tower with
- * width / heads != 64 (OpenCLIP ViT-H/14: 1280 = 16 heads of 80; the reference's model.py:292 computes width // 64 and cannot build it).  The interleaved
+/* ---- Attention for heads that are NOT 64 wide (since 624; widths 88 and 104 since 625; lpi_amd/csrc/attn_hd.hip).  replaces: nn.MultiheadAttention of a vision
+ * tower with width / heads != 64 (OpenCLIP ViT-H/14: 1280 = 16 heads of 80, ViT-g/14: 1408 = 16 of 88, ViT-bigG/14: 1664 = 16 of 104; the reference's
+ * model.py:292 computes width // 64 and cannot build them).  The interleaved
  * layout of lpi_attn_fwd / lpi_attn_bwd with head_dim in place of 64 — qkv, dqkv [B*L, 3*H*head_dim], ctx, dctx [B*L, H*head_dim], lse, delta [B, H, L] f32 —,
  * softmax(q k^T head_dim^-0.5) v, NON-CAUSAL, UNIFORM sequences, at every 1 <= L <= 1024 in the key-walking form of attn_walk.h (forward one launch,
  * backward two: dQ + delta, then dK / dV; every row of dqkv is written; deterministic).  dtype as lpi_attn_fwd / lpi_attn_bwd at L > 288: LPI_F32, LPI_BF16,
  * LPI_F16 (backward: saved qkv / ctx fp16, dctx / dqkv bf16).
- * The rule (anything else is LPI_EINVAL before any launch): head_dim == 80 (the one width that is built); B, L, H > 0, L <= 1024, B H <= 65535 (a grid extent);
- *   forward: ldqkv >= 3 H 80 and a whole number of 16-byte units, ldctx >= H 80 and a multiple of 8 ELEMENTS for every dtype; qkv, ctx 16-byte aligned;
- *   backward: ldqkv, lddqkv >= 3 H 80, ldctx, lddctx >= H 80, each a whole number of 16-byte units; qkv, ctx, dctx, dqkv 16-byte aligned;
- *   no pointer NULL (stream excepted).  No load touches an element outside the 80 of its own (row, head) slice or a row >= B L; lse / delta are written one
- *   element at a time inside [B, H, L].  lpi_attn_hd_supported: 1 where (L, H, head_dim) is inside this rule, without a launch. */
+ * The rule (anything else is LPI_EINVAL before any launch): head_dim is 80, 88 or 104 (the widths that are built, by list: 64, 72, 96 are refused); B, L, H > 0,
+ *   L <= 1024, B H <= 65535 (a grid extent);
+ *   forward: ldqkv >= 3 H head_dim and a whole number of 16-byte units, ldctx >= H head_dim and a multiple of 8 ELEMENTS for every dtype; qkv, ctx 16-byte aligned;
+ *   backward: ldqkv, lddqkv >= 3 H head_dim, ldctx, lddctx >= H head_dim, each a whole number of 16-byte units; qkv, ctx, dctx, dqkv 16-byte aligned;
+ *   no pointer NULL (stream excepted).  No load or store touches an element outside the head_dim of its own (row, head) slice or a row >= B L (88 and 104 end in
+ *   half a 16-column tile: the other half exists in registers and LDS only); lse / delta are written one element at a time inside [B, H, L].
+ *   lpi_attn_hd_supported: 1 where (L, H, head_dim) is inside this rule, without a launch. */
 int lpi_attn_hd_supported(int L, int H, int head_dim);
 int lpi_attn_hd_fwd(int dtype, int B, int L, int H, int head_dim, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, void* stream);
 int lpi_attn_hd_bwd(int dtype, int B, int L, int H, int head_dim, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx,

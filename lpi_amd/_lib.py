@@ -68,7 +68,7 @@ SIGNATURES = {
     "lpi_gather_batch_rows": [_I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     "lpi_attn_fwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P],
     "lpi_attn_bwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _P],
-    # heads that are not 64 wide (attn_hd.hip; since 624): head_dim follows H, otherwise the arguments of lpi_attn_fwd / lpi_attn_bwd without `causal`
+    # heads that are not 64 wide (attn_hd.hip; since 624, head_dim 88 / 104 since 625): head_dim follows H, otherwise the arguments of lpi_attn_fwd / lpi_attn_bwd without `causal`
     "lpi_attn_hd_supported": [_I, _I, _I],
     "lpi_attn_hd_fwd": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P],
     "lpi_attn_hd_bwd": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P],
@@ -191,7 +191,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 624
+EXPECTED_ABI = 625
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -79,7 +79,8 @@ def load_clip_state_dict(src, trusted: bool = False) -> dict:
 def infer_config(sd: dict, name: str = "checkpoint", vision_head_width: int | None = None) -> ClipConfig:
     """build_model's shape inference (model.py:419-441).  Raises CheckpointError for ModifiedResNet checkpoints (no ``visual.proj``) and for tensors
     the ViT path needs but the dict lacks.  A state dict does not say how wide its vision heads are: ``vision_head_width`` None takes the width of the
-    known config called ``name``, else 64 (build_model's width // 64); a width that does not divide the vision width is a CheckpointError."""
+    known config called ``name``, else 64 (build_model's width // 64); a width that does not divide the vision width is a CheckpointError.  It does say how
+    wide each tower's MLP is (the first block's c_fc; OpenCLIP ViT-g/14: 6144 at width 1408): 4 x width is recorded as None, the config's default."""
     if "visual.proj" not in sd:
         rn = any(k.startswith("visual.layer1") for k in sd)
         raise CheckpointError(("this is a ModifiedResNet (RN50-style) CLIP checkpoint: only the ViT backbones of the LPI configs are built"
@@ -106,12 +107,21 @@ def infer_config(sd: dict, name: str = "checkpoint", vision_head_width: int | No
         vision_head_width = CONFIGS[name].vision_head_width if name in CONFIGS else 64
     if isinstance(vision_head_width, bool) or not isinstance(vision_head_width, int) or vision_head_width <= 0 or vision_width % vision_head_width:
         raise CheckpointError(f"vision head width {vision_head_width!r} does not divide the checkpoint's vision width {vision_width}")
-    return ClipConfig(name, embed_dim, vision_patch_size * grid, vision_layers, vision_width, vision_patch_size, context_length, vocab_size,
-                      transformer_width, transformer_heads, transformer_layers, vision_head_width=vision_head_width)
+    mlp = {}
+    for field_, key, width in (("vision_mlp_width", "visual.transformer.resblocks.0.mlp.c_fc.weight", vision_width),
+                               ("transformer_mlp_width", "transformer.resblocks.0.mlp.c_fc.weight", transformer_width)):
+        f = shape(key)[0] if key in sd else 4 * width
+        mlp[field_] = None if f == 4 * width else int(f)
+    try:
+        return ClipConfig(name, embed_dim, vision_patch_size * grid, vision_layers, vision_width, vision_patch_size, context_length, vocab_size,
+                          transformer_width, transformer_heads, transformer_layers, vision_head_width=vision_head_width, **mlp)
+    except ValueError as e:
+        raise CheckpointError(str(e)) from None
 
 
 def same_architecture(a: ClipConfig, b: ClipConfig) -> bool:
-    return a.as_clip_args() == b.as_clip_args() and a.vision_head_width == b.vision_head_width
+    return (a.as_clip_args() == b.as_clip_args() and a.vision_head_width == b.vision_head_width and a.vision_mlp == b.vision_mlp
+            and a.transformer_mlp == b.transformer_mlp)
 
 
 class ParamTree(nn.Module):

@@ -1,6 +1,6 @@
 // Key-walking multi-head attention (non-causal, uniform sequences, L <= 1024): forward and backward tiled over the keys with an online softmax, the head width
-// HD a template parameter.  Two instantiations ship: 64 (attn_long.hip: 288 < L <= 1024, ViT-L/14@336px's 577 tokens + prompts) and 80 (attn_hd.hip: 1 <= L,
-// OpenCLIP ViT-H/14's vision tower).
+// HD a template parameter.  Four instantiations ship: 64 (attn_long.hip: 288 < L <= 1024, ViT-L/14@336px's 577 tokens + prompts), 80 (attn_hd.hip: 1 <= L,
+// OpenCLIP ViT-H/14's vision tower), 88 (attn_hd88.hip: ViT-g/14) and 104 (attn_hd104.hip: ViT-bigG/14).
 //
 // The one-workgroup-per-(sample, head) kernels of attention.hip / attention4.hip keep a head's K and V in LDS (L <= 288); here a workgroup owns 128 rows of one
 // (sample, head) — 4 waves of two 16-row tiles — and walks the OTHER index in blocks of 32 (2-byte types) / 16 (f32):
@@ -25,6 +25,14 @@
 //     per thread (HT::NS), each inside [row ld + h HD, row ld + h HD + HD) of a row < L of its own sample;
 //   * the scale HD^-0.5 is folded into the exp2-domain constant C2: exp(s scale - x) = exp2(C2 s - x log2 e), one multiply and v_exp_f32; the 2-byte backward's
 //     initial accumulator is -lse / scale.  80^-0.5 is no power of two, 64^-0.5 = 1 / 8 is.
+//   * HD = 8 (mod 16) — 88, 104 — ends the output side in HALF a tile: HDP = HD rounded up to 16 (96 / 112), NDT = HDP / 16 tiles (6 / 7), of which the last
+//     holds the head-dimension rows HD - 8 .. HD - 1 in the lanes of k-groups 0, 1 and rows HD .. HDP - 1, which do not exist, in k-groups 2, 3.  acc_operand
+//     reads those rows out of LDS: the 2-byte row-major image has HDP columns per row, the f32 transposed image HDP rows; store_block never writes the 8 pad
+//     columns / rows, zero_pad() zeroes them once per kernel before the walk (they feed only accumulator rows >= HD, which are never stored — but no result may
+//     depend on stale LDS).  Every 4-element store of ctx / dq / dk / dv is guarded by 16 dt + 4 g < HD: HD % 8 == 0 puts a store wholly inside or wholly
+//     outside, and a column >= HD is the next head's, or the next of q / k / v.  GLOBAL MEMORY IS STILL NEVER READ OR WRITTEN OUTSIDE THE HD COLUMNS OF A
+//     (row, head) SLICE: the padding exists in registers and LDS only.  The contraction pads as at 80: 88 -> 96 deep (2-byte KSD 3; f32 22 chunks, KSD 6),
+//     104 -> 128 deep (2-byte KSD 4, whose last step is one live chunk and three zero registers — accepted: correctness first; f32 26 chunks, KSD 7).
 // Registers / LDS per kernel are in DESIGN.md section 4 ("Attention for 80-wide heads"), read from the code object's notes.
 #pragma once
 #include "common.h"
@@ -36,25 +44,30 @@ namespace {
 constexpr int NTHR = 256;
 constexpr float LN2_ = 0.69314718055994531f;
 
-// per width: HD^-0.5, HD^0.5, and the pad of a 2-byte row-major image row — both widths get the 160-byte stride (40 dwords: the transposing reads' 8 rows land on
-// 8 distinct bank octets)
+// per width: HD^-0.5, HD^0.5, and the pad of a 2-byte row-major image row — 64 and 80 get the 160-byte stride (40 dwords: the transposing reads' 8 rows land on
+// 8 distinct bank octets), 88 (96 columns) and 104 (112 columns) the 224-byte stride (56 dwords: 56 q mod 64 = 0, 56, 48, .. 8 for the rows q = 0 .. 7, eight
+// distinct octets again — derived, not measured)
 template <int HD> struct HeadScale;
-template <> struct HeadScale<64> { static constexpr float SCALE = 0.125f, RSCALE = 8.f; static constexpr int PAD2 = 32; };
-template <> struct HeadScale<80> { static constexpr float SCALE = 0.11180339887498948f, RSCALE = 8.94427190999915879f; static constexpr int PAD2 = 0; };
+template <> struct HeadScale<64> { static constexpr int NOWN = 2; static constexpr float SCALE = 0.125f, RSCALE = 8.f; static constexpr int PAD2 = 32; };
+template <> struct HeadScale<80> { static constexpr int NOWN = 2; static constexpr float SCALE = 0.11180339887498948f, RSCALE = 8.94427190999915879f; static constexpr int PAD2 = 0; };
+template <> struct HeadScale<88> { static constexpr int NOWN = 1; static constexpr float SCALE = 0.10660035817780522f, RSCALE = 9.38083151964685911f; static constexpr int PAD2 = 32; };
+template <> struct HeadScale<104> { static constexpr int NOWN = 1; static constexpr float SCALE = 0.09805806756909202f, RSCALE = 10.19803902718556966f; static constexpr int PAD2 = 0; };
 
 template <typename TM, int HD>
 struct HT {
-    static_assert(HD % 16 == 0, "the output side is whole 16-column tiles");
+    static_assert(HD % 8 == 0, "a (row, head) slice is whole 8-element groups; the output side may end in half a 16-column tile");
     static constexpr int EPC = Elem<TM>::EPC;             // elements per 16-byte chunk: 4 / 8
     static constexpr int NB = 4 * EPC;                    // walked rows per block = one MFMA k-step of the accumulate products: 16 / 32
     static constexpr int NTB = NB / 16;                   // 16-wide score tiles per block
     static constexpr int NCH = HD / EPC;                  // 16-byte chunks of a row in TM: 20 / 10
     static constexpr int KSD = (NCH + 3) / 4;             // chunk steps over the head dimension: 5 / 3 (the 2-byte types' third step is half zeros)
-    static constexpr int NDT = HD / 16;                   // output tiles: 5
-    static constexpr int RS = HD * (int)sizeof(TM) + (sizeof(TM) == 2 ? HeadScale<HD>::PAD2 : 16);  // row-major image, bytes per row: 160 / 336
+    static constexpr int HDP = (HD + 15) / 16 * 16;       // the output side's extent in whole tiles: HD, or HD + 8 (88 -> 96, 104 -> 112)
+    static constexpr int NDT = HDP / 16;                  // output tiles: 5 (88: 6, 104: 7, the last half live)
+    // row-major image, bytes per row: 160 / 336; the 2-byte image is read by acc_operand and has HDP columns, the f32 one HD
+    static constexpr int RS = sizeof(TM) == 2 ? HDP * 2 + HeadScale<HD>::PAD2 : HD * 4 + 16;
     static constexpr int RST = NB * (int)sizeof(TM) + 16; // transposed image: bytes per row (one head-dimension index)
     static constexpr int IMG = NB * RS;
-    static constexpr int IMGT = HD * RST;
+    static constexpr int IMGT = HDP * RST;
     static constexpr int NG = HD / 8;                     // 8-element groups of a row: 10
     static constexpr int SLOTS = NB * NG;                 // (row, group) pairs of a block: 160 / 320
     static constexpr int NS = (SLOTS + NTHR - 1) / NTHR;  // of which a thread owns 1 / 2
@@ -104,6 +117,25 @@ __device__ __forceinline__ void store_block(const BlockRegs<HT<TM, HD>::NS>& r, 
         }
     }
 }
+
+// The pad of the images that acc_operand reads, zeroed once per kernel before the walk (HD = 8 mod 16 only): columns HD .. HDP - 1 of every row of a 2-byte
+// row-major image (one 16-byte store per row), rows HD .. HDP - 1 of an f32 transposed image.  store_block never writes them.
+template <typename TM, int HD>
+__device__ __forceinline__ void zero_pad(char* img, char* imgt) {
+    typedef HT<TM, HD> C;
+    if constexpr (C::HDP != HD) {
+        static_assert(C::HDP - HD == 8, "half a tile");
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        if constexpr (C::EPC != 4) {
+            if ((int)threadIdx.x < C::NB) *reinterpret_cast<uint4*>(img + threadIdx.x * C::RS + HD * 2) = z;
+        } else {
+            for (int i = threadIdx.x; i < 8 * C::RST / 16; i += NTHR) *reinterpret_cast<uint4*>(imgt + HD * C::RST + i * 16) = z;
+        }
+    }
+}
+// is the 4-column store of output tile dt live in the lanes of k-group g?  (always, where the width is whole tiles)
+template <typename TM, int HD>
+__device__ __forceinline__ bool tile_live(int dt, int g) { return HT<TM, HD>::HDP == HD || 16 * dt + 4 * g < HD; }
 
 // fragment chunk step ks of one of the lane's OWN rows, from global memory (converted to TM): elements (g + 4 ks) EPC ... of the row; a chunk behind the
 // head's width is zero and is not read
@@ -205,13 +237,16 @@ struct WalkArgs {
 // row-major image instead of the transposed image + permlane reductions: 231 / 268; 160-byte image rows: 233 / 274.  About 0.6 of the tuned short-sequence
 // kernels' rate.  Two image sets with ONE barrier per block: 234 / 271 (no gain: not kept) — what remains is the serial S -> softmax -> PV chain of a wave
 // at one or two waves per SIMD (172-260 VGPRs at 64).
-constexpr int NOWN = 2;
+// A per-width constant (HeadScale<HD>::NOWN; the grid follows from it): 2 at 64 and 80.  88 and 104 take 1: with two tiles fourteen of their eighteen kernels need
+// 264-402 registers — more than 256, so ONE wave per SIMD — and with one tile all need 132-244, two waves; measured at the models' shape (64 samples, L = 273, H = 16, bf16;
+// tools/probe/attn_hdx_bench.py), forward / backward us with 2 tiles -> 1 tile: 88: 175 / 754 -> 173 / 583; 104: 314 / 841 -> 239 / 649.
+template <int HD> constexpr int NOWN = HeadScale<HD>::NOWN;
 
 // ---- forward: grid (ceil(L / (64 NOWN)), B H) -----------------------------------------------------------------------------------------------------------
 template <typename T, int HD>
 __global__ __launch_bounds__(NTHR) void attn_walk_fwd_kernel(WalkArgs A) {
     typedef HT<T, HD> C;
-    constexpr int NO = NOWN;
+    constexpr int NO = NOWN<HD>;
     constexpr bool TR = C::EPC != 4;      // 2-byte types: the accumulate products read the row-major images transposed (acc_operand)
     constexpr float C2 = C::C2;
     __shared__ __attribute__((aligned(16))) char kimg[C::IMG];
@@ -233,6 +268,7 @@ __global__ __launch_bounds__(NTHR) void attn_walk_fwd_kernel(WalkArgs A) {
 #pragma unroll
         for (int dt = 0; dt < C::NDT; ++dt) o[j][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    zero_pad<T, HD>(vimg, vimg);
     auto kr = load_block<T, T, HD>(base + H * HD, A.ldqkv, L), vr = load_block<T, T, HD>(base + 2 * H * HD, A.ldqkv, L);
     for (int k0 = 0; k0 < L; k0 += C::NB) {
         __syncthreads();
@@ -294,7 +330,8 @@ __global__ __launch_bounds__(NTHR) void attn_walk_fwd_kernel(WalkArgs A) {
             const float inv = 1.f / ltot;
             T* dst = reinterpret_cast<T*>(const_cast<void*>(A.ctx)) + ((size_t)b * L + q) * A.ldctx + h * HD + 4 * g;
 #pragma unroll
-            for (int dt = 0; dt < C::NDT; ++dt) Elem<T>::st4(dst + 16 * dt, o[j][dt] * inv);
+            for (int dt = 0; dt < C::NDT; ++dt)
+                if (tile_live<T, HD>(dt, g)) Elem<T>::st4(dst + 16 * dt, o[j][dt] * inv);
             if (g == 0) A.lse[((size_t)b * H + h) * L + q] = (m[j] + __log2f(ltot)) * LN2_;
         }
     }
@@ -304,7 +341,7 @@ __global__ __launch_bounds__(NTHR) void attn_walk_fwd_kernel(WalkArgs A) {
 template <typename TS, typename TG, int HD>
 __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dq_kernel(WalkArgs A) {
     typedef HT<TG, HD> C;
-    constexpr int NO = NOWN;
+    constexpr int NO = NOWN<HD>;
     constexpr bool TR = C::EPC != 4;
     constexpr float C2 = C::C2, SCALE = C::SCALE, RSCALE = C::RSCALE;
     __shared__ __attribute__((aligned(16))) char kimg[C::IMG];
@@ -345,6 +382,7 @@ __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dq_kernel(WalkArgs A) {
 #pragma unroll
         for (int dt = 0; dt < C::NDT; ++dt) dq[j][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    zero_pad<TG, HD>(kimg, kimgt);
     auto kr = load_block<TS, TG, HD>(base + H * HD, A.ldqkv, L), vr = load_block<TS, TG, HD>(base + 2 * H * HD, A.ldqkv, L);
     for (int k0 = 0; k0 < L; k0 += C::NB) {
         __syncthreads();
@@ -402,7 +440,8 @@ __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dq_kernel(WalkArgs A) {
         if (q < L) {
             TG* dst = reinterpret_cast<TG*>(A.dqkv) + ((size_t)b * L + q) * A.lddqkv + h * HD + 4 * g;
 #pragma unroll
-            for (int dt = 0; dt < C::NDT; ++dt) Elem<TG>::st4(dst + 16 * dt, dq[j][dt] * SCALE);
+            for (int dt = 0; dt < C::NDT; ++dt)
+                if (tile_live<TG, HD>(dt, g)) Elem<TG>::st4(dst + 16 * dt, dq[j][dt] * SCALE);
         }
     }
 }
@@ -411,7 +450,7 @@ __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dq_kernel(WalkArgs A) {
 template <typename TS, typename TG, int HD>
 __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dkv_kernel(WalkArgs A) {
     typedef HT<TG, HD> C;
-    constexpr int NO = NOWN;
+    constexpr int NO = NOWN<HD>;
     constexpr bool TR = C::EPC != 4;
     constexpr float C2 = C::C2, SCALE = C::SCALE, RSCALE = C::RSCALE;
     __shared__ __attribute__((aligned(16))) char qimg[C::IMG];
@@ -438,6 +477,8 @@ __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dkv_kernel(WalkArgs A) {
 #pragma unroll
         for (int dt = 0; dt < C::NDT; ++dt) dk[j][dt] = dv[j][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    zero_pad<TG, HD>(qimg, qimgt);
+    zero_pad<TG, HD>(dimg, dimgt);
     const size_t s0 = ((size_t)b * H + h) * L;
     auto qr = load_block<TS, TG, HD>(base, A.ldqkv, L);
     auto dr = load_block<TG, TG, HD>(dbase, A.lddctx, L);
@@ -515,6 +556,7 @@ __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dkv_kernel(WalkArgs A) {
             TG* dst = reinterpret_cast<TG*>(A.dqkv) + ((size_t)b * L + k) * A.lddqkv + h * HD + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < C::NDT; ++dt) {
+                if (!tile_live<TG, HD>(dt, g)) continue;
                 Elem<TG>::st4(dst + H * HD + 16 * dt, dk[j][dt] * SCALE);
                 Elem<TG>::st4(dst + 2 * H * HD + 16 * dt, dv[j][dt]);
             }
@@ -523,11 +565,11 @@ __global__ __launch_bounds__(NTHR) void attn_walk_bwd_dkv_kernel(WalkArgs A) {
 }
 
 // ---- launches: the forward one, the backward two; an unknown dtype -> LPI_EINVAL -----------------------------------------------------------------------------
-inline dim3 walk_grid(const WalkArgs& A) { return dim3((A.L + 64 * NOWN - 1) / (64 * NOWN), A.B * A.H); }
+template <int HD> dim3 walk_grid(const WalkArgs& A) { return dim3((A.L + 64 * NOWN<HD> - 1) / (64 * NOWN<HD>), A.B * A.H); }
 
 template <int HD> int walk_fwd(int dtype, const WalkArgs& A, hipStream_t s) {
     if (!dispatch_types(TypeList<Types<float>, Types<bf16_t>, Types<f16_t>>{}, [&](auto t) {
-            LPI_LAUNCH((attn_walk_fwd_kernel<type_of<decltype(t)>, HD>), walk_grid(A), dim3(NTHR), 0, s, A);
+            LPI_LAUNCH((attn_walk_fwd_kernel<type_of<decltype(t)>, HD>), walk_grid<HD>(A), dim3(NTHR), 0, s, A);
         }, dtype)) return LPI_EINVAL;
     LPI_CHECK_LAST();
     return 0;
@@ -538,8 +580,8 @@ template <int HD> int walk_bwd(int dtype, const WalkArgs& A, hipStream_t s) {
     if (!dispatch_types(TypeList<Types<float, float>, Types<bf16_t, bf16_t>, Types<f16_t, bf16_t>>{}, [&](auto ts, auto tg) {
             typedef type_of<decltype(ts)> TS;
             typedef type_of<decltype(tg)> TG;
-            LPI_LAUNCH((attn_walk_bwd_dq_kernel<TS, TG, HD>), walk_grid(A), dim3(NTHR), 0, s, A);
-            LPI_LAUNCH((attn_walk_bwd_dkv_kernel<TS, TG, HD>), walk_grid(A), dim3(NTHR), 0, s, A);
+            LPI_LAUNCH((attn_walk_bwd_dq_kernel<TS, TG, HD>), walk_grid<HD>(A), dim3(NTHR), 0, s, A);
+            LPI_LAUNCH((attn_walk_bwd_dkv_kernel<TS, TG, HD>), walk_grid<HD>(A), dim3(NTHR), 0, s, A);
         }, dtype, dtype == LPI_F16 ? LPI_BF16 : dtype)) return LPI_EINVAL;      // (saved type, gradient type)
     LPI_CHECK_LAST();
     return 0;

@@ -273,14 +273,16 @@ def gemm(dt, a, b, c, M, N, K, bias=None, residual=None, epi=EPI_NONE, aux=None,
 _LN_FOLD_OK = {}
 
 
-def _ln_fold_ok(Mp, d):
-    """True if the persistent 256x256 kernel (the one with the LN-fold epilogues) takes the in_proj / c_fc GEMMs of a [Mp, d] stream."""
-    key = (Mp, d)
+def _ln_fold_ok(Mp, d, f=None):
+    """True if the persistent 256x256 kernel (the one with the LN-fold epilogues) takes the in_proj / c_fc GEMMs of a [Mp, d] stream with an MLP f wide
+    (None: 4 d)."""
+    f = 4 * d if f is None else f
+    key = (Mp, d, f)
     ok = _LN_FOLD_OK.get(key)
     if ok is None:
         lib = _lib.load()
         ok = _LN_FOLD_OK[key] = bool(lib.lpi_gemm_ln_supported(F16, Mp, 2 * d, d) and lib.lpi_gemm_ln_supported(F16, Mp, 3 * d, d)
-                                     and lib.lpi_gemm_ln_supported(F16, Mp, 4 * d, d))
+                                     and lib.lpi_gemm_ln_supported(F16, Mp, f, d))
     return ok
 
 
@@ -587,6 +589,11 @@ class TowerSpec:
     heads: int
     layers: int
     causal: bool
+    mlp_width: int = 0      # the MLP's hidden width f; 0 = 4 x width (OpenCLIP ViT-g/14's vision tower: 6144 at 1408, bigG/14's: 8192 at 1664)
+
+    def __post_init__(self):
+        if not self.mlp_width:
+            self.mlp_width = 4 * self.width
 
 
 class Tower:
@@ -613,7 +620,7 @@ class Tower:
             raise ValueError(f"tower width {spec.width} is no multiple of its {spec.heads} heads")
         self.hd = spec.width // spec.heads
         if self.hd != 64 and (spec.causal or _lib.load().lpi_attn_hd_supported(1, spec.heads, self.hd) != 1):
-            raise ValueError(f"heads of {self.hd}: the attention kernels take 64 (any tower) or 80 (a non-causal tower)")
+            raise ValueError(f"heads of {self.hd}: the attention kernels take 64 (any tower) or 80, 88, 104 (a non-causal tower)")
         if self.hd != 64 and opt.mx8_forward:
             raise ValueError(f"mx8_forward does not combine with heads of {self.hd}: lpi_layernorm_mx8_fwd takes d <= 1024")
         self.pooled_last = bool(opt.pooled_last and self.hd == 64)
@@ -625,6 +632,12 @@ class Tower:
         if mx8 and spec.width % 128:
             raise ValueError(f"mx8_forward: tower width {spec.width} is not a multiple of 128")
         d_, H_ = spec.width, spec.heads
+        # the MLP's width is the tower's own (TowerSpec.mlp_width, from the config) and the weights must agree with it
+        if spec.layers and tuple(f(f"{prefix}resblocks.0.mlp.c_fc.weight").shape) != (spec.mlp_width, d_):
+            raise ValueError(f"{prefix}resblocks.0.mlp.c_fc.weight is {tuple(f(f'{prefix}resblocks.0.mlp.c_fc.weight').shape)}: the config says an MLP of "
+                             f"{spec.mlp_width} at width {d_}")
+        if spec.mlp_width % 128:
+            raise ValueError(f"MLP width {spec.mlp_width} is not a multiple of 128 (GEMM tile)")
         self.qkv_lay = (3 * 64, 64, 64)                                 # (head stride, q -> k -> v stride, ctx head stride) of a grouped block
         perm = torch.arange(3 * d_).view(3, H_, 64).permute(1, 0, 2).reshape(-1) if self.hd == 64 else None      # new feature h*192 + w*64 + c  <-  old w*d + h*64 + c
         for i in range(spec.layers):
@@ -711,7 +724,7 @@ class Tower:
         key = (B, train)
         for k in [k for k in self._ws if k[1] == train]:
             del self._ws[k]
-        d, H, nl = self.spec.width, self.spec.heads, self.spec.layers
+        d, H, nl, f = self.spec.width, self.spec.heads, self.spec.layers, self.spec.mlp_width
         POOLED_LAST = self.pooled_last
         Lreal, L = L, max(L, cap or L)
         Mp = _pad(B * L, 256)      # whole 256x256 GEMM tiles (the 128x128 kernel takes any multiple of 128)
@@ -728,17 +741,17 @@ class Tower:
             "qkv": [z(Mp, 3 * d, dtype=T) for _ in range(keep)],
             "ctx": [z(Mp, d, dtype=T) for _ in range(keep)],
             "lse": [z(B + 1, H, L) for _ in range(keep)],      # + 1: the shared sequence of a shared-prefix batch (sample index B)
-            "u": [z(Mp, 4 * d, dtype=TU) for _ in range(keep)] if train else [None],
+            "u": [z(Mp, f, dtype=TU) for _ in range(keep)] if train else [None],
             # per layer, per LayerNorm: mean[Mp] | rstd[Mp] | c1[<= 4d] (the LN operand block of the LN-fold GEMM epilogues, include/lpi_hip.h)
             # (+ Mp: a row CHUNK of the MLP passes the block shifted by its first row, and reads c1 shifted by as much: a copy of c1 sits there)
-            "lnblk": [z(2, 3 * Mp + 4 * d) for _ in range(nl)],
+            "lnblk": [z(2, 3 * Mp + max(3 * d, f)) for _ in range(nl)],
             "h": z(Mp, d, dtype=T),
-            "g": z(Mp, 4 * d, dtype=T),
+            "g": z(Mp, f, dtype=T),
             # slot sums of the row statistics a residual GEMM's epilogue leaves (LPI_EPI_RES_ROWSTATS): d/128 slots x (sum, sum of squares) x Mp
             "rstat": z(2 * max(d // 128, 1), Mp),
             # the LAST block's MLP runs on the B pooled rows only (exact: the heads read nothing else of its output)
-            "Bp": Bp, "c_xmid": z(Bp, d), "c_h": z(Bp, d, dtype=T), "c_g": z(Bp, 4 * d, dtype=T),
-            "c_u": z(Bp, 4 * d, dtype=TU) if train else None, "c_xout": z(Bp, d), "c_stat": z(2, Bp),
+            "Bp": Bp, "c_xmid": z(Bp, d), "c_h": z(Bp, d, dtype=T), "c_g": z(Bp, f, dtype=T),
+            "c_u": z(Bp, f, dtype=TU) if train else None, "c_xout": z(Bp, d), "c_stat": z(2, Bp),
             # ... and so do its query, attention row and out_proj (K and V still cover every token)
             "c_q": z(Bp, d, dtype=T), "c_ctx": z(Bp, d, dtype=T), "c_lse": z(B * H), "c_xin": z(Bp, d), "c_stat1": z(2, Bp),
             # the last block without K and V (EngineOptions.stream_pool): qt | hbar | dhbar | dqt, f32 [B, H, d] each, and the scores' log-sum-exp
@@ -762,7 +775,7 @@ class Tower:
         if self.mx8 and not train:
             # MX-FP8 operands of the no-grad forward: LN(x) (h), the attention output (ctx) and QuickGELU(c_fc) (g) as e4m3 bytes + E8M0 scales per 32 columns
             u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=dev)  # noqa: E731
-            ws["mx"] = {"h": u8(Mp, d), "hs": u8(Mp, d // 32), "ctx": u8(Mp, d), "ctxs": u8(Mp, d // 32), "g": u8(Mp, 4 * d), "gs": u8(Mp, 4 * d // 32)}
+            ws["mx"] = {"h": u8(Mp, d), "hs": u8(Mp, d // 32), "ctx": u8(Mp, d), "ctxs": u8(Mp, d // 32), "g": u8(Mp, f), "gs": u8(Mp, f // 32)}
         # "stat"[i] = (ln1 mean, ln1 rstd, ln2 mean, ln2 rstd) of layer i: views into the LN blocks
         ws["stat"] = [(b[0, :Mp], b[0, Mp:2 * Mp], b[1, :Mp], b[1, Mp:2 * Mp]) for b in ws["lnblk"]]
         ws["ln_ld"] = Mp
@@ -772,7 +785,7 @@ class Tower:
                 if i == nl - 1 and POOLED_LAST:      # the last block's in_proj GEMM covers K and V only (rows d.. of the weight)
                     c1 = c1[d:]
                 ws["lnblk"][i][0, 2 * Mp:2 * Mp + c1.numel()].copy_(c1)
-                ws["lnblk"][i][1, 2 * Mp:2 * Mp + 4 * d].copy_(blk["fc_ln"].c1)
+                ws["lnblk"][i][1, 2 * Mp:2 * Mp + f].copy_(blk["fc_ln"].c1)
         self._ws[key] = ws
         return bind(ws, Lreal)
 
@@ -780,7 +793,7 @@ class Tower:
     def ln1_stats_out(self, ws):
         """(mean, rstd) of the first block's ln_1 if the front end should leave them there (its rows pass through a wave: lpi_vis_assemble_fwd /
         lpi_txt_embed_fwd take them as out_mean / out_rstd), else (None, None): no statistics pass over x_0 then.  Pass ln1_ready=True to forward_gen."""
-        if self.rowstats >= 2 and self.blocks and "qkv_ln" in self.blocks[0] and _ln_fold_ok(ws["Mp"], self.spec.width):
+        if self.rowstats >= 2 and self.blocks and "qkv_ln" in self.blocks[0] and _ln_fold_ok(ws["Mp"], self.spec.width, self.spec.mlp_width):
             st = ws["stat"][0]
             return st[0], st[1]
         return None, None
@@ -802,7 +815,7 @@ class Tower:
         mdt = _gemm_code(dt, self.opt)      # what the GemmReqs carry: dt, or F32X3 (EngineOptions.gemm_bf16x3)
         POOLED_LAST, LN_FOLD = self.pooled_last, self.opt.ln_fold
         ERF = self.opt.erf_gelu      # c_fc as a plain GEMM + lpi_gelu_erf_fwd behind it (EngineOptions.erf_gelu)
-        d, H = sp.width, sp.heads
+        d, H, f = sp.width, sp.heads, sp.mlp_width
         B, L, Mp, M = ws["B"], ws["L"], ws["Mp"], ws["M"]
         rs = ws["rs"]                                  # ragged batch: row starts (device int32 [B+1]); None = B x L rows
         # kernels that address ONE token per sample: (L, token index) or, ragged, (0, absolute row) — see include/lpi_hip.h
@@ -838,14 +851,14 @@ class Tower:
                 yield Mx8Req(G(d, d), xc, Mp, d, d, m["ctx"], d, m["ctxs"], d // 32, ow.w8, d, ow.w8s, d // 32, xmid, d, None, 0, ow.b, x_in, d, EPI_NONE, 1.0,
                              m_real=M)
                 yield Mx8Req("lpi_layernorm_mx8_fwd", xdt, M, d, xmid, d, blk["ln_2.w"], blk["ln_2.b"], m["h"], d, m["hs"], d // 32, None, None)
-                yield Mx8Req(G(4 * d, d), _lib.MX8, Mp, 4 * d, d, m["h"], d, m["hs"], d // 32, fw.w8, d, fw.w8s, d // 32, m["g"], 4 * d, m["gs"], 4 * d // 32, fw.b,
+                yield Mx8Req(G(f, d), _lib.MX8, Mp, f, d, m["h"], d, m["hs"], d // 32, fw.w8, d, fw.w8s, d // 32, m["g"], f, m["gs"], f // 32, fw.b,
                              None, 0, EPI_QUICKGELU, 1.0, m_real=M)
-                yield Mx8Req(G(d, 4 * d), xc, Mp, d, 4 * d, m["g"], 4 * d, m["gs"], 4 * d // 32, pw.w8, 4 * d, pw.w8s, 4 * d // 32, x_out, d, None, 0, pw.b, xmid, d,
+                yield Mx8Req(G(d, f), xc, Mp, d, f, m["g"], f, m["gs"], f // 32, pw.w8, f, pw.w8s, f // 32, x_out, d, None, 0, pw.b, xmid, d,
                              EPI_NONE, 1.0, m_real=M)
                 have_ln1 = False      # no row-statistics epilogue on this path: the next block (the pooled last one) takes its statistics pass
                 continue
             # LayerNorm folded into the GEMM behind it (LnLinear): a statistics pass over the stream, then the GEMM reads the stream itself
-            fold = "qkv_ln" in blk and _ln_fold_ok(Mp, d)
+            fold = "qkv_ln" in blk and _ln_fold_ok(Mp, d, f)
             lnb, ln_ld = ws["lnblk"][i], ws["ln_ld"]
             rowstats = self.rowstats if (fold and d % 128 == 0) else 0
             if fold and have_ln1:
@@ -881,11 +894,11 @@ class Tower:
                 yield RowReq(f"{lt}.pln2", [_lib.row_job(_lib.ROWOP_POOL_LN_FWD, B=B, L=1, d=d, dt_a=F32, dt_b=dt, a=ws["c_xmid"], gamma=blk["ln_2.w"],
                                                          beta=blk["ln_2.b"], out=ws["c_h"], ld_c=d, mean=cst[0], rstd=cst[1])])
                 if ERF:
-                    yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, m_real=B)
+                    yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, f, d, bias=blk["fc"].b, m_real=B)
                     yield self._erf_act(f"{lt}.cact", ws["c_g"], ws["c_u"], B)
                 else:
-                    yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=ws["c_u"], m_real=B)
-                yield GemmReq(f"{lt}.cproj", mdt, ws["c_g"], blk["proj"].w, ws["c_xout"], Bp, d, 4 * d, bias=blk["proj"].b, residual=ws["c_xmid"], m_real=B)
+                    yield GemmReq(f"{lt}.cfc", mdt, ws["c_h"], blk["fc"].w, ws["c_g"], Bp, f, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=ws["c_u"], m_real=B)
+                yield GemmReq(f"{lt}.cproj", mdt, ws["c_g"], blk["proj"].w, ws["c_xout"], Bp, d, f, bias=blk["proj"].b, residual=ws["c_xmid"], m_real=B)
                 return ws["c_xout"]
             if fold:
                 ql = blk["qkv_ln"]
@@ -915,18 +928,18 @@ class Tower:
                 if not ln2_stats:
                     yield LnReq(f"{lt}.ln2", "fwd", (dt, xdt), M, d, xmid, d, None, None, None, 0, st[2], st[3], optional=True)
                 if ERF:
-                    yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, 4 * d, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN, m_real=M)
+                    yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, f, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN, m_real=M)
                 else:
-                    yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, 4 * d, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN_QUICKGELU, aux=u, m_real=M)
+                    yield GemmReq(f"{lt}.fc", F16, xmid, fl.w, ws["g"], Mp, f, d, bias=fl.c2, residual=lnb[1], ldr=ln_ld, epi=EPI_LN_QUICKGELU, aux=u, m_real=M)
             else:
                 yield LnReq(f"{lt}.ln2", "fwd", (dt, xdt), M, d, xmid, d, blk["ln_2.w"], blk["ln_2.b"], ws["h"], d, st[2], st[3], optional=True)
                 if ERF:
-                    yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, m_real=M)
+                    yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, f, d, bias=blk["fc"].b, m_real=M)
                 else:
-                    yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, 4 * d, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=u, m_real=M)
+                    yield GemmReq(f"{lt}.fc", mdt, ws["h"], blk["fc"].w, ws["g"], Mp, f, d, bias=blk["fc"].b, epi=EPI_QUICKGELU, aux=u, m_real=M)
             if ERF:
                 yield self._erf_act(f"{lt}.act", ws["g"], u, M)
-            yield GemmReq(f"{lt}.proj", mdt, ws["g"], blk["proj"].w, x_out, Mp, d, 4 * d, **proj_kw)
+            yield GemmReq(f"{lt}.proj", mdt, ws["g"], blk["proj"].w, x_out, Mp, d, f, **proj_kw)
             if have_ln1:
                 nst = ws["stat"][nxt]
                 yield StatFinReq(f"{lt}.fin1", M, d, ws["rstat"], ws["rstat"].stride(0), nst[0], nst[1])
@@ -946,7 +959,7 @@ class Tower:
         mdt = _gemm_code(dt, self.opt)
         adt = F16 if self.dt == F16 else dt       # attention backward: F16 = "saved q, k, v, ctx are fp16; gradients and operands bf16"
         POOLED_LAST, L0_PROMPT_ROWS = self.pooled_last, self.opt.l0_prompt_rows
-        d, H = sp.width, sp.heads
+        d, H, f = sp.width, sp.heads, sp.mlp_width
         B, L, Mp, M = ws["B"], ws["L"], ws["Mp"], ws["M"]
         rs = ws["rs"]                                  # ragged batch: row starts (device int32 [B+1]); None = B x L rows
         # kernels that address ONE token per sample: (L, token index) or, ragged, (0, absolute row) — see include/lpi_hip.h
@@ -970,8 +983,8 @@ class Tower:
                 Bp, cst = ws["Bp"], ws["c_stat"]
                 c_dx = ws["c_dx"]
                 c_dxT = ws["c_dxT"] if dt != F32 else c_dx
-                yield GemmReq(f"{lt}.cdproj", mdt, c_dxT, blk["proj"].wt, ws["c_du"], Bp, 4 * d, d, epi=EPI_DQUICKGELU, aux=ws["c_u"], m_real=B)
-                yield GemmReq(f"{lt}.cdfc", mdt, ws["c_du"], blk["fc"].wt, ws["c_dh"], Bp, d, 4 * d, m_real=B)
+                yield GemmReq(f"{lt}.cdproj", mdt, c_dxT, blk["proj"].wt, ws["c_du"], Bp, f, d, epi=EPI_DQUICKGELU, aux=ws["c_u"], m_real=B)
+                yield GemmReq(f"{lt}.cdfc", mdt, ws["c_du"], blk["fc"].wt, ws["c_dh"], Bp, d, f, m_real=B)
                 yield RowReq(f"{lt}.cdln2", [_lib.row_job(_lib.ROWOP_LN_BWD, B=B, d=d, dt_a=dt, dt_b=dt, a=ws["c_dh"], ld_a=d, b=ws["c_xmid"], ld_b=d,
                                                           gamma=blk["ln_2.w"], mean_in=cst[0], rstd_in=cst[1], out=c_dx, out2=None if dt == F32 else c_dxT,
                                                           ld_c=d, flag=1)])
@@ -1001,8 +1014,8 @@ class Tower:
                 continue
             if not (i == len(self.blocks) - 1 and POOLED_LAST):
                 du = ws["du"]
-                yield GemmReq(f"{lt}.dproj", mdt, dxT, blk["proj"].wt, du, Mp, 4 * d, d, epi=EPI_DQUICKGELU, aux=u, m_real=M)          # d c_proj, * gelu'
-                yield GemmReq(f"{lt}.dfc", mdt, du, blk["fc"].wt, dh, Mp, d, 4 * d, m_real=M)                                         # d c_fc
+                yield GemmReq(f"{lt}.dproj", mdt, dxT, blk["proj"].wt, du, Mp, f, d, epi=EPI_DQUICKGELU, aux=u, m_real=M)          # d c_proj, * gelu'
+                yield GemmReq(f"{lt}.dfc", mdt, du, blk["fc"].wt, dh, Mp, d, f, m_real=M)                                         # d c_fc
                 yield LnReq(f"{lt}.dln2", "bwd", (dt, dt, xdt), M, d, dh, d, xmid, d, blk["ln_2.w"], st[2], st[3], dx, d,
                             None if dt == F32 else dxT, d, 1)      # dx is None in bf16 mode: dxT accumulates in place
             yield GemmReq(f"{lt}.dout", mdt, dxT, blk["out"].wt, dctx, Mp, d, d, m_real=M)                                         # d out_proj
@@ -1070,8 +1083,8 @@ class DualEncoder:
         dev, dt = self.device, self.dt
         t = lambda k: (state_dict[k] if torch.is_tensor(state_dict[k]) else torch.as_tensor(np.asarray(state_dict[k]))).to(  # noqa: E731
             device=dev, dtype=torch.float32).contiguous()
-        self.vis = Tower(state_dict, "visual.transformer.", TowerSpec(cfg.vision_width, cfg.vision_heads, cfg.vision_layers, False), dt, dev, self.opt)
-        self.txt = Tower(state_dict, "transformer.", TowerSpec(cfg.transformer_width, cfg.transformer_heads, cfg.transformer_layers, True), dt, dev, self.opt)
+        self.vis = Tower(state_dict, "visual.transformer.", TowerSpec(cfg.vision_width, cfg.vision_heads, cfg.vision_layers, False, cfg.vision_mlp), dt, dev, self.opt)
+        self.txt = Tower(state_dict, "transformer.", TowerSpec(cfg.transformer_width, cfg.transformer_heads, cfg.transformer_layers, True, cfg.transformer_mlp), dt, dev, self.opt)
         ps = cfg.vision_patch_size
         self.kp = _pad(3 * ps * ps, 32 if dt == F32 else 64)
         self.conv = Linear(t("visual.conv1.weight").reshape(cfg.vision_width, -1), None, dt, dev, k_pad=self.kp)

@@ -129,6 +129,9 @@ class SliNet(nn.Module):
         self.clip_cfg, sd = _resolve_weights(args)
         if args["visual_dim"] != self.clip_cfg.vision_width or args["textual_dim"] != self.clip_cfg.transformer_width:
             raise ValueError("visual_dim / textual_dim do not match the backbone")
+        if args.get("eval_scores", "matrix") == "streamed" and self.clip_cfg.embed_dim > 1024:      # lpi_amd.search: E <= 1024 (ViT-bigG/14 has 1280)
+            raise ValueError(f"eval_scores='streamed' takes features up to 1024 wide and {self.clip_cfg.name} has {self.clip_cfg.embed_dim}: "
+                             "use eval_scores='matrix' (the default)")
         self.compute_dtype = args.get("compute_dtype", "f32")
         self.erf_gelu = engine_erf_gelu(args)      # config key `activation`: refused HERE, before anything is built
         self.depth = int(args["prompt_depth"]) if args.get("honor_prompt_depth", False) else 1

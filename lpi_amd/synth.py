@@ -44,10 +44,26 @@ class ClipConfig:
     transformer_layers: int
     # not an argument of CLIP.__init__ (model.py:292 computes width // 64): OpenCLIP's ViT-H/14 has vision heads of 80.  A state dict does not say it.
     vision_head_width: int = field(default=64, kw_only=True)
+    # not arguments either (model.py:171 builds every MLP 4 x width): OpenCLIP's ViT-g/14 and bigG/14 have vision MLPs of 6144 and 8192 at widths 1408 and
+    # 1664.  None = 4 x the tower's width.  A state dict does say these (the c_fc shapes).
+    vision_mlp_width: int | None = field(default=None, kw_only=True)
+    transformer_mlp_width: int | None = field(default=None, kw_only=True)
 
     def __post_init__(self):
         if self.vision_head_width <= 0 or self.vision_width % self.vision_head_width:
             raise ValueError(f"{self.name}: vision width {self.vision_width} is no multiple of the head width {self.vision_head_width}")
+        for what, f in (("vision", self.vision_mlp_width), ("transformer", self.transformer_mlp_width)):
+            if f is not None and (isinstance(f, bool) or not isinstance(f, int) or f <= 0 or f % 128):
+                raise ValueError(f"{self.name}: {what} MLP width {f!r} is no positive multiple of 128 (GEMM tile)")
+
+    @property
+    def vision_mlp(self) -> int:
+        """the vision MLP's hidden width: vision_mlp_width, or 4 x vision_width"""
+        return 4 * self.vision_width if self.vision_mlp_width is None else self.vision_mlp_width
+
+    @property
+    def transformer_mlp(self) -> int:
+        return 4 * self.transformer_width if self.transformer_mlp_width is None else self.transformer_mlp_width
 
     @property
     def vision_heads(self) -> int:
@@ -58,10 +74,12 @@ class ClipConfig:
         return (self.image_resolution // self.vision_patch_size) ** 2
 
     def as_clip_args(self):
-        """The ten arguments of the reference's CLIP.__init__ (the head width is not one of them)."""
+        """The ten arguments of the reference's CLIP.__init__ (the head width and the MLP widths are not among them)."""
         d = asdict(self)
         d.pop("name")
         d.pop("vision_head_width")
+        d.pop("vision_mlp_width")
+        d.pop("transformer_mlp_width")
         return tuple(d.values())
 
 
@@ -85,8 +103,15 @@ VIT_H14 = ClipConfig("ViT-H/14", 1024, 224, 32, 1280, 14, 77, 49408, 1024, 16, 2
 TINY_H80 = ClipConfig("tinyH80", 128, 32, 2, 640, 16, 77, 49408, 128, 2, 2, vision_head_width=80)
 # ViT-H/14's widths, patch and resolution with 2 + 2 layers: the real GEMM and row shapes (d = 1280, E = 1024) at a size the CPU oracle runs in seconds
 H14_SHALLOW = ClipConfig("H14-shallow", 1024, 224, 2, 1280, 14, 77, 49408, 1024, 16, 2, vision_head_width=80)
+# OpenCLIP ViT-g/14 and ViT-bigG/14: vision heads of 88 / 104 (csrc/attn_hd88.hip, attn_hd104.hip) and vision MLPs that are not 4 x width; text heads of 64
+VIT_G14 = ClipConfig("ViT-g/14", 1024, 224, 40, 1408, 14, 77, 49408, 1024, 16, 24, vision_head_width=88, vision_mlp_width=6144)
+VIT_BIGG14 = ClipConfig("ViT-bigG/14", 1280, 224, 48, 1664, 14, 77, 49408, 1280, 20, 32, vision_head_width=104, vision_mlp_width=8192)
+# their widths with 4 patches + CLS and 2 + 2 layers: 1408 and 1664 are the smallest widths that are multiples of both 128 and 88 / 104 — there is no smaller toy
+G14_WIDTHS = ClipConfig("g14-widths", 1024, 28, 2, 1408, 14, 77, 49408, 1024, 16, 2, vision_head_width=88, vision_mlp_width=6144)
+BIGG14_WIDTHS = ClipConfig("bigG14-widths", 1280, 28, 2, 1664, 14, 77, 49408, 1280, 20, 2, vision_head_width=104, vision_mlp_width=8192)
 
-CONFIGS = {c.name: c for c in (VIT_B16, VIT_L14, VIT_L14_336, VIT_B32, TINY, TINY14, TINY_LONG, VIT_H14, TINY_H80, H14_SHALLOW)}
+CONFIGS = {c.name: c for c in (VIT_B16, VIT_L14, VIT_L14_336, VIT_B32, TINY, TINY14, TINY_LONG, VIT_H14, TINY_H80, H14_SHALLOW, VIT_G14, VIT_BIGG14, G14_WIDTHS,
+                               BIGG14_WIDTHS)}
 
 
 def _rng(seed: int, name: str) -> np.random.Generator:
@@ -102,7 +127,7 @@ def normal(seed: int, name: str, shape, std: float = 1.0, mean: float = 0.0) -> 
     return x
 
 
-def _block(sd, seed, prefix, width, layers):
+def _block(sd, seed, prefix, width, layers, mlp):
     attn_std = width ** -0.5
     proj_std = (width ** -0.5) * ((2 * layers) ** -0.5)
     fc_std = (2 * width) ** -0.5
@@ -115,9 +140,9 @@ def _block(sd, seed, prefix, width, layers):
             ("attn.out_proj.bias", (width,), 0.02, 0.0),
             ("ln_1.weight", (width,), 0.1, 1.0),
             ("ln_1.bias", (width,), 0.05, 0.0),
-            ("mlp.c_fc.weight", (4 * width, width), fc_std, 0.0),
-            ("mlp.c_fc.bias", (4 * width,), 0.02, 0.0),
-            ("mlp.c_proj.weight", (width, 4 * width), proj_std, 0.0),
+            ("mlp.c_fc.weight", (mlp, width), fc_std, 0.0),
+            ("mlp.c_fc.bias", (mlp,), 0.02, 0.0),
+            ("mlp.c_proj.weight", (width, mlp), proj_std, 0.0),
             ("mlp.c_proj.bias", (width,), 0.02, 0.0),
             ("ln_2.weight", (width,), 0.1, 1.0),
             ("ln_2.bias", (width,), 0.05, 0.0),
@@ -166,8 +191,8 @@ def _clip_state_dict(cfg: ClipConfig, seed: int) -> dict:
     for nm in ("ln_pre", "ln_post"):
         sd[f"visual.{nm}.weight"] = normal(seed, f"visual.{nm}.weight", (vw,), 0.1, 1.0)
         sd[f"visual.{nm}.bias"] = normal(seed, f"visual.{nm}.bias", (vw,), 0.05)
-    _block(sd, seed, "visual.transformer.", vw, cfg.vision_layers)
-    _block(sd, seed, "transformer.", tw, cfg.transformer_layers)
+    _block(sd, seed, "visual.transformer.", vw, cfg.vision_layers, cfg.vision_mlp)
+    _block(sd, seed, "transformer.", tw, cfg.transformer_layers, cfg.transformer_mlp)
     sd["token_embedding.weight"] = normal(seed, "token_embedding.weight", (cfg.vocab_size, tw), 0.02)
     sd["positional_embedding"] = normal(seed, "positional_embedding", (cfg.context_length, tw), 0.01)
     sd["ln_final.weight"] = normal(seed, "ln_final.weight", (tw,), 0.1, 1.0)
