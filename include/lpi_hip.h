@@ -476,13 +476,25 @@ int lpi_patchify(int dtype, int B, int R, int ps, const float* image, void* cols
 /* The same im2col from UINT8 pixels [B,3,R,R] (what the decoder produces: PIL -> HWC bytes -> CHW) with the loader's ToTensor + Normalize
  * (utils/data.py:201-204: x / 255, (x - mean) / std) folded in through `lut` (f32 [3][256], DEVICE: lut[c][v] = the f32 value the host pipeline gives byte v
  * in channel c — filled by the caller with those very operations, so the columns equal lpi_patchify's on the normalised f32 image bit for bit).  A quarter
- * of the host-to-device bytes of the f32 batch (38.5 MB instead of 154 MB per 256 images).  ps and R multiples of 4, image 4-byte aligned. */
+ * of the host-to-device bytes of the f32 batch (38.5 MB instead of 154 MB per 256 images).  Every geometry with R % ps == 0 (since 626; before, only ps and R multiples of 4): with ps and R multiples of 4 a kernel that reads four
+ * pixels as one dword runs, and `image` must be 4-byte aligned (LPI_EINVAL otherwise, as before); every other geometry (ps = 14, 7, 6, ...) runs a kernel of
+ * byte loads, which takes any image pointer.  Same columns, same zero padding of columns 3*ps*ps .. Kp, in f32, bf16 and f16. */
 int lpi_patchify_u8(int dtype, int B, int R, int ps, const uint8_t* image, const float* lut, void* cols, int ldcols, void* stream);
 int lpi_vis_assemble_fwd(int x_dtype, int B, int G2, int P, int d, const float* patch_emb, int ldpe, const float* cls,
                          const float* pos, const float* prompt0, long prompt_bstride,
                          const float* gamma, const float* beta, void* x0, float* mean, float* rstd, float* out_mean, float* out_rstd, void* stream);
 int lpi_vis_assemble_bwd(int dtype, int B, int G2, int P, int d, void* dx0, const float* prompt0, long prompt_bstride,
                          const float* gamma, const float* mean, const float* rstd, float* dprompt, void* stream);
+/* The position table at another patch grid (since 626; lpi_amd/csrc/posembed.hip): what a ViT library does when a checkpoint runs at a resolution other than
+ * the one it was trained at.  src [1 + g_in*g_in, d] f32 (row 0 the class row, then the grid row-major; row stride lds), dst [1 + g_out*g_out, d] (stride ldd).
+ * Row 0 is copied; the grid is resampled as torch.nn.functional.interpolate(x.reshape(1,g,g,d).permute(0,3,1,2), size=(g',g'), mode, align_corners=False,
+ * antialias) does (OpenCLIP and timm use bicubic with antialias): separably, with float64 weights and sums and one rounding to f32.  g_out == g_in is a
+ * bitwise copy in every mode, as in torch.  One launch; meant to be called once per engine.
+ * 1 <= g_in, g_out <= 64; d a positive multiple of 4; lds, ldd >= d and multiples of 4; src, dst 16-byte aligned and not overlapping; filter one of the two
+ * below, antialias 0 or 1: LPI_EINVAL before any launch otherwise.  Columns d .. ldd of dst are not written. */
+#define LPI_POS_BICUBIC 0
+#define LPI_POS_BILINEAR 1
+int lpi_pos_embed_resample(int g_in, int g_out, int d, const float* src, long lds, float* dst, long ldd, int filter, int antialias, void* stream);
 
 /* ---- a6/a7: text front end          replaces: models/clip/prompt_learner.py:52-53,128-163 --------------
  * x0[b,l] = (l in 1..P ? ctx[b,l-1] : tok_emb[ids[b,l]]) + pos[l]      (CLASS_TOKEN_POSITION == "end")

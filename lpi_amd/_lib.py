@@ -100,6 +100,8 @@ SIGNATURES = {
     "lpi_patchify_u8": [_I, _I, _I, _I, _P, _P, _P, _I, _P],
     "lpi_vis_assemble_fwd": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P],
     "lpi_vis_assemble_bwd": [_I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P],
+    # the position table at another patch grid (posembed.hip; since 626): torch's interpolate, bicubic / bilinear, with or without antialias
+    "lpi_pos_embed_resample": [_I, _I, _I, _P, _L, _P, _L, _I, _I, _P],
     "lpi_txt_embed_fwd": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P],
     "lpi_rows_sum_over_batch": [_I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "lpi_prompt_add": [_I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _P],
@@ -191,7 +193,7 @@ _RESTYPES = {"lpi_launch_count": c_uint64, "lpi_search_workspace": c_long, "lpi_
 
 # The C ABI this binding was written against (lpi_version()).  Bumped with every change of a signature or of an argument's meaning: a stale
 # liblpi_hip.so (or an LPI_LIB variant of another commit) would otherwise take shifted arguments silently.
-EXPECTED_ABI = 625
+EXPECTED_ABI = 626
 VARIANT_OFFSET = 1000000      # lpi_version() of a tools/build_variant.sh build = EXPECTED_ABI + this
 
 _lib = None

@@ -397,7 +397,8 @@ __global__ __launch_bounds__(256) void patchify_kernel(int B, int R, int ps, int
 
 // The same im2col from UINT8 pixels [B, 3, R, R] with ToTensor + Normalize folded in (utils/data.py:201-204: x / 255, then (x - mean) / std per channel):
 // lut[c][v] holds that f32 value for channel c and byte v, computed by the HOST with the very torch operations the f32 pipeline applies, so the columns are
-// bit for bit those of patchify_kernel on the normalised f32 image — at a quarter of the host-to-device bytes.  ps and R multiples of 4.
+// bit for bit those of patchify_kernel on the normalised f32 image — at a quarter of the host-to-device bytes.  Every R % ps == 0 geometry: this kernel (four
+// pixels as one dword, so a 4-byte image pointer) when ps and R are multiples of 4, patchify_u8_any_kernel (byte loads, any image pointer) for the rest, e.g. ps = 14.
 template <typename T>
 __global__ __launch_bounds__(256) void patchify_u8_kernel(int B, int R, int ps, int G, int Kp, const uint8_t* __restrict__ img, const float* __restrict__ lut,
                                                          T* __restrict__ cols, int ldcols) {
@@ -417,6 +418,32 @@ __global__ __launch_bounds__(256) void patchify_u8_kernel(int B, int R, int ps, 
         const uint32_t px = *reinterpret_cast<const uint32_t*>(img + (((size_t)b * 3 + c) * R + gy * ps + dy) * R + gx * ps + dx);
         const float* l = s_lut + c * 256;
         v = f32x4{l[px & 255u], l[(px >> 8) & 255u], l[(px >> 16) & 255u], l[px >> 24]};
+    }
+    Elem<T>::st4(cols + (size_t)patch * ldcols + k4, v);
+}
+
+// any ps and R, any image alignment: as patchify_kernel's non-VEC4 arm, the four k of a thread split one by one (they may cross a patch row or a channel)
+template <typename T>
+__global__ __launch_bounds__(256) void patchify_u8_any_kernel(int B, int R, int ps, int G, int Kp, const uint8_t* __restrict__ img, const float* __restrict__ lut,
+                                                             T* __restrict__ cols, int ldcols) {
+    __shared__ float s_lut[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) s_lut[i] = lut[i];
+    __syncthreads();
+    const int K = 3 * ps * ps;
+    const long total = (long)B * G * G * (Kp >> 2);
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int k4 = (int)(t % (Kp >> 2)) << 2;
+    const long patch = t / (Kp >> 2);
+    const int b = (int)(patch / (G * G)), gy = (int)(patch % (G * G)) / G, gx = (int)(patch % G);
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = k4 + j;
+        if (k < K) {
+            const int c = k / (ps * ps), rem = k % (ps * ps), dy = rem / ps, dx = rem % ps;
+            v[j] = s_lut[c * 256 + img[(((size_t)b * 3 + c) * R + gy * ps + dy) * R + gx * ps + dx]];
+        }
     }
     Elem<T>::st4(cols + (size_t)patch * ldcols + k4, v);
 }
@@ -1155,11 +1182,14 @@ extern "C" int lpi_patchify(int dtype, int B, int R, int ps, const float* image,
 extern "C" int lpi_patchify_u8(int dtype, int B, int R, int ps, const uint8_t* image, const float* lut, void* cols, int ldcols, void* stream) {
     int G, Kp;
     dim3 g;
-    if (!image || !lut || !cols || B <= 0 || ps <= 0 || R % ps || (ps & 3) || (R & 3) || ((uintptr_t)image & 3) || !patchify_shape(dtype, B, R, ps, cols, ldcols, G, Kp, g))
+    // ps and R multiples of 4: the dword kernel and its rule on the image pointer, as on record (tests/rowop_args_expected.json); every other geometry: byte loads
+    const bool dword = (ps & 3) == 0 && (R & 3) == 0;
+    if (!image || !lut || !cols || B <= 0 || ps <= 0 || R % ps || (dword && ((uintptr_t)image & 3)) || !patchify_shape(dtype, B, R, ps, cols, ldcols, G, Kp, g))
         return LPI_EINVAL;
     dispatch_types(AnyElem{}, [&](auto t) {
         typedef type_of<decltype(t)> T;
-        LPI_LAUNCH(patchify_u8_kernel<T>, g, dim3(256), 0, S(stream), B, R, ps, G, Kp, image, lut, (T*)cols, ldcols);
+        if (dword) LPI_LAUNCH(patchify_u8_kernel<T>, g, dim3(256), 0, S(stream), B, R, ps, G, Kp, image, lut, (T*)cols, ldcols);
+        else LPI_LAUNCH(patchify_u8_any_kernel<T>, g, dim3(256), 0, S(stream), B, R, ps, G, Kp, image, lut, (T*)cols, ldcols);
     }, dtype);
     LPI_CHECK_LAST();
     return 0;

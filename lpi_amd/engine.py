@@ -46,6 +46,10 @@ PIXEL_NORMS = {"imagenet": (None, None),
                "clip": ((0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711))}
 
 
+# EngineOptions.pos_embed by name: (filter, antialias) of lpi_pos_embed_resample (LPI_POS_BICUBIC 0 / LPI_POS_BILINEAR 1)
+POS_EMBED_MODES = {"bicubic": (0, 0), "bicubic_aa": (0, 1), "bilinear": (1, 0)}
+
+
 @dataclass(frozen=True)
 class EngineOptions:
     """Everything that selects a code path of the engine, as ONE typed per-engine object (round 6; it replaced sixteen module globals read from the
@@ -99,7 +103,12 @@ class EngineOptions:
         with the fold) and lpi_gelu_erf_fwd (csrc/act.hip) rewrites its output in place and, in a training forward, saves gelu'(u) in the buffer the QuickGELU
         epilogue fills: the backward is unchanged, its d c_proj epilogue multiplies by whatever derivative the forward saved.  One more launch per tower and block
         in the forward and one more pass over the [M, 4 d] tile; every mode and both forwards (train=True / False).  Not with mx8_forward (ValueError: that path's
-        c_fc writes MX-FP8 straight from its QuickGELU epilogue)."""
+        c_fc writes MX-FP8 straight from its QuickGELU epilogue).
+    pos_embed (constructor only): what to do when the checkpoint's position table was trained on another patch grid than cfg's (a checkpoint run at another
+        resolution, ClipConfig.at_resolution).  None: refuse (ValueError naming both grids, before anything touches the GPU).  'bicubic_aa' (OpenCLIP's and
+        timm's recipe), 'bicubic' or 'bilinear': resample the grid rows of the table as torch.nn.functional.interpolate(..., align_corners=False) does, with
+        antialias for 'bicubic_aa' — one lpi_pos_embed_resample launch (csrc/posembed.hip) at construction; DualEncoder.vpos holds the result and the state
+        dict is not touched.  Equal grids: nothing happens with any value, no launch, the same tensor."""
     residual_f16: bool = True
     ln_fold: int = 2
     rowstats: int = 2
@@ -113,8 +122,11 @@ class EngineOptions:
     mx8_tile256: bool = True
     gemm_bf16x3: bool = False
     erf_gelu: bool = False
+    pos_embed: Optional[str] = None
 
     def __post_init__(self):
+        if self.pos_embed is not None and (not isinstance(self.pos_embed, str) or self.pos_embed not in POS_EMBED_MODES):
+            raise ValueError(f"pos_embed is None, {', '.join(repr(m) for m in POS_EMBED_MODES)}, not {self.pos_embed!r}")
         if self.ln_fold not in (0, 1, 2) or self.rowstats not in (0, 1, 2):
             raise ValueError("ln_fold and rowstats are 0, 1 or 2")
         if self.erf_gelu and self.mx8_forward:
@@ -1073,6 +1085,18 @@ class DualEncoder:
         self.opt.check_dtype(dtype)
         if self.opt.mx8_forward and cfg.vision_width // cfg.vision_heads != 64:      # (before anything touches the GPU; Tower.__init__ says it again)
             raise ValueError(f"mx8_forward does not combine with vision heads of {cfg.vision_width // cfg.vision_heads}: lpi_layernorm_mx8_fwd takes d <= 1024")
+        # the position table against cfg's patch grid (before anything touches the GPU): equal -> used as it is; another grid -> resampled below, once, when
+        # EngineOptions.pos_embed names a mode, refused otherwise (lpi_vis_assemble_fwd reads 1 + n_patches rows of whatever it is handed)
+        g_cfg, rows = cfg.image_resolution // cfg.vision_patch_size, int(np.shape(state_dict["visual.positional_embedding"])[0])
+        g_tab = math.isqrt(max(rows - 1, 0))
+        if rows != 1 + g_tab * g_tab or g_tab < 1:
+            raise ValueError(f"visual.positional_embedding has {rows} rows: not 1 + g * g for a patch grid g x g")
+        if g_tab != g_cfg and self.opt.pos_embed is None:
+            raise ValueError(f"visual.positional_embedding was trained on a {g_tab} x {g_tab} patch grid and the config asks for {g_cfg} x {g_cfg} "
+                             f"({cfg.image_resolution} px at patch size {cfg.vision_patch_size}): set EngineOptions.pos_embed ('bicubic_aa', 'bicubic' or "
+                             "'bilinear') to resample the table")
+        if g_tab != g_cfg and not (1 <= g_cfg <= 64 and g_tab <= 64):
+            raise ValueError(f"pos_embed: lpi_pos_embed_resample takes patch grids up to 64 x 64, not {g_tab} x {g_tab} -> {g_cfg} x {g_cfg}")
         self.device = torch.device(device)
         _require_gpu(self.device)
         _lib.load()
@@ -1090,6 +1114,11 @@ class DualEncoder:
         self.conv = Linear(t("visual.conv1.weight").reshape(cfg.vision_width, -1), None, dt, dev, k_pad=self.kp)
         self.cls = t("visual.class_embedding")
         self.vpos = t("visual.positional_embedding")
+        if g_tab != g_cfg:      # the engine's copy only: the state dict, and with it every prompt checkpoint, keeps the table it came with
+            table, self.vpos = self.vpos, torch.empty(1 + g_cfg * g_cfg, cfg.vision_width, dtype=torch.float32, device=dev)
+            filt, aa = POS_EMBED_MODES[self.opt.pos_embed]
+            with torch.cuda.device(dev):
+                call("lpi_pos_embed_resample", g_tab, g_cfg, cfg.vision_width, table, table.stride(0), self.vpos, self.vpos.stride(0), filt, aa, _stream())
         self.ln_pre = (t("visual.ln_pre.weight"), t("visual.ln_pre.bias"))
         self.ln_post = (t("visual.ln_post.weight"), t("visual.ln_post.bias"))
         self.vproj = Linear(t("visual.proj").t().contiguous(), None, dt, dev)        # Linear weight [E, d]

@@ -165,7 +165,7 @@ class SPrompts(BaseLearner):
             # loader's — the filter travels with the items, 'f32' items are normalised here and the engine gets the same statistics for the
             # other formats (models/slinet.py: EngineOptions.pixel_norm).  Without those keys the datasets are built as ever.
             from lpi_amd.retrieval.utils.data import preprocess_options
-            pre = preprocess_options(self.args, self._network.clip_cfg.image_resolution if 'preprocess' in self.args else None)
+            pre = preprocess_options(self.args, self._network.clip_cfg.image_resolution if ('preprocess' in self.args or 'image_resolution' in self.args) else None)
             kw, ekw = {}, {}
             if pre is not None:
                 kw = dict(size=pre['size'], interpolation=pre['interpolation'], normalize=pre['normalize'])

@@ -18,7 +18,8 @@ Differences that are deliberate:
   * ``text`` may be a list of captions (tokenised on the host like PromptLearner.forward) or a LongTensor [B,77] of ids;
   * extra keys: ``compute_dtype`` ('f32' parity mode | 'bf16' throughput mode), ``honor_prompt_depth`` (default False: the
     shipped reference never reads ``prompt_depth`` and behaves as depth 1 — SURVEY.md F1), ``r`` (default 4), ``activation`` ('quick_gelu', the
-    default | 'gelu': nn.GELU's erf form for checkpoints trained with it, e.g. OpenCLIP's — EngineOptions.erf_gelu; see engine_erf_gelu).
+    default | 'gelu': nn.GELU's erf form for checkpoints trained with it, e.g. OpenCLIP's — EngineOptions.erf_gelu; see engine_erf_gelu),
+    ``image_resolution`` / ``pos_embed_interpolation`` (the checkpoint at another input resolution, its position table resampled: see model_resolution).
 """
 import copy
 import os
@@ -82,6 +83,37 @@ def engine_erf_gelu(args):
     return want
 
 
+POS_EMBED_INTERPOLATIONS = ("bicubic_aa", "bicubic", "bilinear")      # config key `pos_embed_interpolation` -> EngineOptions.pos_embed
+MAX_VISION_TOKENS = 1024      # the attention kernels' longest sequence (csrc/attn_long.hip, attn_walk.h): class token + prompts + patches
+
+
+def model_resolution(args, cfg):
+    """-> (ClipConfig, EngineOptions.pos_embed or None) for the config keys `image_resolution` (an integer; absent: the checkpoint's or named config's own)
+    and `pos_embed_interpolation` ('bicubic_aa', the default: OpenCLIP's and timm's recipe | 'bicubic' | 'bilinear'; means something only when the resolution
+    differs from cfg's, and the mode is None when it does not).  The position table is resampled inside the engine only (DualEncoder.vpos): clip_model, its
+    state dict and every prompt checkpoint keep the table they came with.  ValueError, before anything is built: a key of the wrong type, a resolution that is
+    no positive multiple of the patch size, a sequence of 1 + prompt_length + patches over MAX_VISION_TOKENS, an interpolation outside the three names, or
+    engine_options whose pos_embed says otherwise than the key."""
+    mode = args.get("pos_embed_interpolation")
+    if mode is not None and (not isinstance(mode, str) or mode not in POS_EMBED_INTERPOLATIONS):
+        raise ValueError(f"pos_embed_interpolation must be one of {', '.join(repr(m) for m in POS_EMBED_INTERPOLATIONS)}, not {mode!r}")
+    eo = args.get("engine_options")
+    given = eo.get("pos_embed") if isinstance(eo, dict) else getattr(eo, "pos_embed", None)
+    if given is not None and mode is not None and given != mode:
+        raise ValueError(f"pos_embed_interpolation is {mode!r} but engine_options.pos_embed is {given!r}: the two must agree")
+    if "image_resolution" not in args:
+        return cfg, None
+    r = args["image_resolution"]
+    if isinstance(r, bool) or not isinstance(r, int):
+        raise ValueError(f"image_resolution must be an integer, not {r!r}")
+    new = cfg.at_resolution(r)      # ValueError: no positive multiple of the patch size
+    tokens = 1 + int(args["prompt_length"]) + new.n_patches
+    if tokens > MAX_VISION_TOKENS:
+        raise ValueError(f"image_resolution {r} at patch size {cfg.vision_patch_size} gives 1 + {args['prompt_length']} + {new.n_patches} = {tokens} vision tokens: "
+                         f"the limit is {MAX_VISION_TOKENS}")
+    return new, (None if r == cfg.image_resolution else (mode or given or "bicubic_aa"))
+
+
 class _TaskTerm:
     """The task loss of a continual session (slinet.py:160-162, 167-183) inside the fused step: 0.1 * (nt_bxent(V) + nt_bxent(T)) / 2 over the stacked,
     flattened prompt stacks of tasks 0..t.  Rows 0..t-1 (the finished tasks, frozen: sprompt.py:230-237) are reconstructed ONCE; row t is copied from the
@@ -127,6 +159,7 @@ class SliNet(nn.Module):
         if args["prompt_type"] != "lpi":
             raise ValueError("lpi_amd builds prompt_type 'lpi' only (the hot path); got {}".format(args["prompt_type"]))
         self.clip_cfg, sd = _resolve_weights(args)
+        self.clip_cfg, self.pos_embed = model_resolution(args, self.clip_cfg)      # config keys `image_resolution` / `pos_embed_interpolation`: refused HERE
         if args["visual_dim"] != self.clip_cfg.vision_width or args["textual_dim"] != self.clip_cfg.transformer_width:
             raise ValueError("visual_dim / textual_dim do not match the backbone")
         if args.get("eval_scores", "matrix") == "streamed" and self.clip_cfg.embed_dim > 1024:      # lpi_amd.search: E <= 1024 (ViT-bigG/14 has 1280)
@@ -168,6 +201,9 @@ class SliNet(nn.Module):
                 eo = dict(eo or {}, pixel_norm=norm)
             if self.erf_gelu and not isinstance(eo, EngineOptions):      # `activation`: 'gelu' (an EngineOptions object agrees already: engine_erf_gelu)
                 eo = dict(eo or {}, erf_gelu=True)
+            if self.pos_embed is not None:      # `image_resolution` differs from the checkpoint's: the engine resamples its copy of the position table
+                import dataclasses
+                eo = dataclasses.replace(eo, pos_embed=self.pos_embed) if isinstance(eo, EngineOptions) else dict(eo or {}, pos_embed=self.pos_embed)
             if isinstance(eo, dict):
                 eo = EngineOptions.from_env(**eo)
             self.engine = DualEncoder(self.clip_cfg, self.clip_model.state_dict(), dtype=self.compute_dtype, device=dev, n_ctx=self.cfg.NCTX, options=eo)

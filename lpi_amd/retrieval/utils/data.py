@@ -517,9 +517,12 @@ def preprocess_options(args, resolution=None):
     the datasets and the engine are then built exactly as without them).  Config keys: `preprocess` = 'reference' (default: the reference's retrieval
     loader — bilinear, ImageNet statistics, Resize(256) for evaluation, 224 x 224 items) or 'clip' (CLIP's own, models/clip/clip.py:71-78 of the
     reference: bicubic, CLIP's statistics, Resize(n_px) + CenterCrop(n_px) for evaluation, n_px = `resolution`, the model's); `interpolation`
-    ('bilinear' | 'bicubic' | 'box'), `normalize` ('imagenet' | 'clip' | a (mean, std) pair) and `eval_resize` override single parts of it."""
+    ('bilinear' | 'bicubic' | 'box'), `normalize` ('imagenet' | 'clip' | a (mean, std) pair) and `eval_resize` override single parts of it.
+    `image_resolution` (the model run at another input resolution than its checkpoint's, models/slinet.py model_resolution) counts as one of the keys, and only
+    with it does 'reference' leave its 224 / 256: the items are image_resolution x image_resolution and evaluation resizes to
+    round(image_resolution * 256 / 224) first — the loader's own ratio — unless `eval_resize` says otherwise.  'clip' follows `resolution` as ever."""
     keys = ("preprocess", "interpolation", "normalize", "eval_resize")
-    if not any(k in args for k in keys):
+    if not any(k in args for k in keys + ("image_resolution",)):
         return None
     pre = args.get("preprocess", "reference")
     if pre not in PREPROCESS:
@@ -530,6 +533,11 @@ def preprocess_options(args, resolution=None):
         out = {"interpolation": "bicubic", "normalize": "clip", "eval_resize": int(resolution), "size": int(resolution)}
     else:
         out = {"interpolation": "bilinear", "normalize": "imagenet", "eval_resize": 256, "size": 224}
+        if "image_resolution" in args:
+            r = args["image_resolution"]
+            if isinstance(r, bool) or not isinstance(r, int) or r <= 0:
+                raise ValueError(f"image_resolution must be a positive integer, not {r!r}")
+            out.update(size=r, eval_resize=int(round(r * 256 / 224)))
     for k in keys[1:]:
         if k in args:
             out[k] = args[k]

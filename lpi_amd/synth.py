@@ -16,7 +16,7 @@ so a real CLIP state dict can be passed to the engine in place of the synthetic 
 from __future__ import annotations
 
 import zlib
-from dataclasses import dataclass, asdict, field
+from dataclasses import dataclass, asdict, field, replace
 
 import numpy as np
 
@@ -72,6 +72,14 @@ class ClipConfig:
     @property
     def n_patches(self) -> int:
         return (self.image_resolution // self.vision_patch_size) ** 2
+
+    def at_resolution(self, r: int) -> "ClipConfig":
+        """The same architecture at input resolution r (a positive integer multiple of the patch size): what a checkpoint run above or below its training
+        resolution needs, together with EngineOptions.pos_embed for its position table."""
+        ps = self.vision_patch_size
+        if isinstance(r, bool) or not isinstance(r, int) or r <= 0 or r % ps:
+            raise ValueError(f"{self.name}: resolution {r!r} is no positive integer multiple of the patch size {ps}")
+        return replace(self, image_resolution=r)
 
     def as_clip_args(self):
         """The ten arguments of the reference's CLIP.__init__ (the head width and the MLP widths are not among them)."""
