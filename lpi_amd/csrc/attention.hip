@@ -21,11 +21,27 @@
 //   pass B (a wave owns 2x16 keys)   : dV = P^T dO;           dK = scale * dS^T Q
 // Fragment conventions (cdna_hip_programming.md section 3): 16x16 MFMA tiles, lane l supplies row (l & 15) and
 // k-group g = l >> 4 of each operand as one 16-byte chunk; it receives column (l & 15), rows 4g..4g+3.
+//
+// The host layer is at the end of the file: one call struct (AttnCall), one predicate per argument rule, one typed dispatch per form (dispatch.h); every
+// kernel instantiation that needs more than 64 KiB of LDS has its own LdsOnce beside its launch.
+#include <algorithm>
+#include <initializer_list>
 #include <type_traits>
-#include "common.h"
+#include "dispatch.h"
 #include "attn_softmax.h"
 
 extern int g_lpi_tuning[16];
+
+// attn_long.hip (the kernels: attn_walk.h at head width 64): 288 < L <= 1024, non-causal, uniform sequences — tiled over the keys with an online softmax (ViT-L/14@336px: 577 tokens + prompts)
+bool lpi_attn_long_ok(int L, int causal, const void* row_start);
+int lpi_attn_long_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, hipStream_t s);
+int lpi_attn_long_bwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx, const float* lse,
+                      float* delta, void* dqkv, int lddqkv, hipStream_t s);
+// attention4.hip: the backward as ONE pass, 8 waves owning 16-32 keys each, query slices streamed through an LDS ring; non-causal, L <= 288 (more than 224
+// tokens: two key windows); which calls it takes: streamed_bwd_takes below
+bool lpi_attn4_bwd_ok(int L, int causal);
+int lpi_attn4_bwd(int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx, const float* lse,
+                  float* delta, void* dqkv, int lddqkv, hipStream_t s, int saved_f16, int rows_hi, const int* lay = nullptr);
 
 namespace {
 
@@ -913,211 +929,7 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(int Lmax, int Lpmax
     }
 }
 
-// waves per workgroup: each wave owns NB 16-row blocks per round; balance the rounds
-inline int pick_waves(int L) {
-    const int nqb = (L + 16 * NB - 1) / (16 * NB);
-    const int rounds = (nqb + 7) / 8;
-    return (nqb + rounds - 1) / rounds;
-}
-// ragged batches (the text tower: 2 000 workgroups of a few dozen rows, latency-bound): tuning key 9 = minimum number of waves per workgroup — the waves
-// beyond the row blocks take part in the staging only (more loads in flight per workgroup)
-inline int pick_waves_ragged(int L) {
-    const int w = pick_waves(L), lo = g_lpi_tuning[9];
-    return lo > w ? (lo < 8 ? lo : 8) : w;
-}
-
-// allow the full 160 KiB of a CU's LDS for a kernel: once per (kernel function, device), safe from any host thread
-int set_lds(const void* kern, size_t bytes) {
-    if (bytes > 160 * 1024) return LPI_EINVAL;
-    static const void* fn[32];
-    static LdsOnce once[32];
-    static std::atomic<int> nfn{0};
-    static std::atomic_flag lock = ATOMIC_FLAG_INIT;
-    int slot = -1;
-    const int n = nfn.load(std::memory_order_acquire);
-    for (int i = 0; i < n; ++i)
-        if (fn[i] == kern) { slot = i; break; }
-    if (slot < 0) {
-        while (lock.test_and_set(std::memory_order_acquire)) {}
-        const int m = nfn.load(std::memory_order_relaxed);
-        for (int i = 0; i < m; ++i)
-            if (fn[i] == kern) { slot = i; break; }
-        if (slot < 0 && m < 32) { fn[m] = kern; slot = m; nfn.store(m + 1, std::memory_order_release); }
-        lock.clear(std::memory_order_release);
-    }
-    if (slot < 0) return (int)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return lpi_ensure_lds(once[slot], kern, 160 * 1024);
-}
-
-// the padded images of two workgroups do not fit a CU's 160 KiB but the unpadded ones do (tuning key 13 = 1: never; A/B switch)
-static bool fwd_swizzled(int Lp) { return g_lpi_tuning[13] != 1 && (size_t)2 * 2 * Lp * 160 > (size_t)160 * 1024 && (size_t)2 * 2 * Lp * 128 <= (size_t)160 * 1024; }
-
-template <typename T, bool CAUSAL>
-int fwd_launch(int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, hipStream_t s, const int* rs = nullptr, int pre = 0,
-               int hs = 0, int vs = 0, int chs = 0) {
-    // pre > 0 (causal ragged batches): B tail samples + the shared sequence as sample B (attn_fwd_body)
-    const int nbh = (B + (pre > 0 ? 1 : 0)) * H, bsh = pre > 0 ? B : -1;
-    const int Lp = (L + 31) / 32 * 32;
-    const size_t lds = (size_t)2 * Lp * AT<T>::RS;
-    const int thr = 64 * (rs ? pick_waves_ragged(L) : pick_waves(L));
-    if constexpr (sizeof(T) == 2 && !CAUSAL) {
-        if (fwd_swizzled(Lp) && !rs) {      // 257 .. 288 tokens: unpadded swizzled images, two workgroups per CU (stage_rows2)
-            const size_t lsw = (size_t)2 * Lp * 128;
-            if (int e = set_lds((const void*)attn_fwd_kernel<T, CAUSAL, true>, lsw)) return e;
-            LPI_LAUNCH((attn_fwd_kernel<T, CAUSAL, true>), dim3(nbh), dim3(thr), lsw, s, L, Lp, rs, H, (const T*)qkv, ldqkv, (T*)ctx, ldctx, lse, pre, bsh, hs, vs, chs);
-            LPI_CHECK_LAST();
-            return 0;
-        }
-    }
-    int e = set_lds((const void*)attn_fwd_kernel<T, CAUSAL>, lds);
-    if (e) return e;
-    LPI_LAUNCH((attn_fwd_kernel<T, CAUSAL>), dim3(nbh), dim3(thr), lds, s, L, Lp, rs, H, (const T*)qkv, ldqkv, (T*)ctx, ldctx, lse, pre, bsh, hs, vs, chs);
-    LPI_CHECK_LAST();
-    return 0;
-}
-
-template <typename T, bool CAUSAL, bool SV16 = false>
-int bwd_launch(int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx,
-               const float* lse, float* delta, void* dqkv, int lddqkv, hipStream_t s, const int* rs = nullptr, int rows_hi = 1 << 30, int pre = 0,
-               float* shared_dkv = nullptr, const int* lay = nullptr) {
-    // lay: NULL = interleaved, else {qkv_hs, qkv_vs, dqkv_hs, dqkv_vs, ...} (lpi_attn_bwd_layout; ctx / dctx keep their 64-element head stride here)
-    const int l0 = lay ? lay[0] : 0, l1 = lay ? lay[1] : 0, l2 = lay ? lay[2] : 0, l3 = lay ? lay[3] : 0;
-    const int Lp = (L + 31) / 32 * 32;
-    const size_t ldsA = (size_t)2 * Lp * AT<T>::RS;
-    const size_t ldsB = ldsA + (size_t)2 * Lp * sizeof(float);
-    const int thr = 64 * (rs ? pick_waves_ragged(L) : pick_waves(L));
-    const size_t ldsF = (size_t)4 * Lp * AT<T>::RS + (size_t)2 * Lp * sizeof(float);
-    // fused single pass for 2-byte operands (HBM bound: -7 % at L = 213, -23 % at L = 77); f32 is compute bound and faster with the
-    // two-pass kernels at two workgroups per CU.  Tuning key 3 != 0 forces the two-pass kernels.
-    if (sizeof(T) == 2 && ldsF <= 160 * 1024 && g_lpi_tuning[3] == 0) {
-        int ef = set_lds((const void*)attn_bwd_fused_kernel<T, CAUSAL, SV16>, ldsF);
-        if (ef) return ef;
-        LPI_LAUNCH((attn_bwd_fused_kernel<T, CAUSAL, SV16>), dim3((B + (pre > 0 ? 1 : 0)) * H), dim3(thr), ldsF, s, L, Lp, rs, H, (const T*)qkv, ldqkv,
-                   (const T*)ctx, ldctx, (const T*)dctx, lddctx, lse, delta, (T*)dqkv, lddqkv, rows_hi, pre, pre > 0 ? B : -1, shared_dkv, l0, l1, l2, l3);
-        LPI_CHECK_LAST();
-        return 0;
-    }
-    int e = set_lds((const void*)attn_bwd_dq_kernel<T, CAUSAL, SV16>, ldsA);
-    if (e) return e;
-    e = set_lds((const void*)attn_bwd_dkv_kernel<T, CAUSAL, SV16>, ldsB);
-    if (e) return e;
-    const int nbh = (B + (pre > 0 ? 1 : 0)) * H, bsh = pre > 0 ? B : -1;
-    LPI_LAUNCH((attn_bwd_dq_kernel<T, CAUSAL, SV16>), dim3(nbh), dim3(thr), ldsA, s, L, Lp, rs, H, (const T*)qkv, ldqkv, (const T*)ctx, ldctx,
-               (const T*)dctx, lddctx, lse, delta, (T*)dqkv, lddqkv, pre, bsh, l0, l1, l2, l3);
-    LPI_CHECK_LAST();
-    LPI_LAUNCH((attn_bwd_dkv_kernel<T, CAUSAL, SV16>), dim3(nbh), dim3(thr), ldsB, s, L, Lp, rs, H, (const T*)qkv, ldqkv, (const T*)dctx, lddctx,
-               lse, delta, (T*)dqkv, lddqkv, pre, bsh, shared_dkv, l0, l1, l2, l3);
-    LPI_CHECK_LAST();
-    return 0;
-}
-
-inline bool bad_attn(int dtype, int B, int L, int H, int ld, int lmax = 288) {
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    return B <= 0 || H <= 0 || L <= 0 || L > lmax || ld < 3 * H * HD || (ld * esz) % 16;
-}
-
 }  // namespace
-
-// attn_long.hip (the kernels: attn_walk.h at head width 64): 288 < L <= 1024, non-causal, uniform sequences — tiled over the keys with an online softmax (ViT-L/14@336px: 577 tokens + prompts)
-bool lpi_attn_long_ok(int L, int causal, const void* row_start);
-int lpi_attn_long_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, hipStream_t s);
-int lpi_attn_long_bwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx, const float* lse,
-                      float* delta, void* dqkv, int lddqkv, hipStream_t s);
-
-// attention4.hip: the backward as ONE pass, 8 waves owning 16-32 keys each, query slices streamed through an LDS ring; non-causal, L <= 224;
-// the default for L > 160 (tuning key 7 = 0), forced at every L it takes by key 7 = 5, never with key 7 = 1
-bool lpi_attn4_bwd_ok(int L, int causal);
-int lpi_attn4_bwd(int B, int L, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx, int lddctx, const float* lse,
-                  float* delta, void* dqkv, int lddqkv, hipStream_t s, int saved_f16, int rows_hi, const int* lay = nullptr);
-extern "C" int lpi_attn_fwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* qkv, int ldqkv, void* ctx, int ldctx,
-                                   float* lse, int causal, void* stream) {
-    const int* rs = row_start;      // ragged batch: the one-head-per-workgroup kernels take a per-sample length
-    const bool lng = lpi_attn_long_ok(L, causal, row_start);
-    if (!qkv || !ctx || !lse || bad_attn(dtype, B, L, H, ldqkv, lng ? 1024 : 288) || ldctx < H * HD || (ldctx & 7)) return LPI_EINVAL;
-    if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (lng) return lpi_attn_long_fwd(dtype, B, L, H, qkv, ldqkv, ctx, ldctx, lse, s);
-    if (dtype == LPI_F32)
-        return causal ? fwd_launch<float, true>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, rs) : fwd_launch<float, false>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, rs);
-    if (dtype == LPI_F16)       // f16 operand mode: q, k, v and ctx are fp16 (the reference's own arithmetic type)
-        return causal ? fwd_launch<f16_t, true>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, rs) : fwd_launch<f16_t, false>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, rs);
-    if (dtype == LPI_BF16) {
-        // (a persistent forward with K / V double-buffered by LDS-DMA measured SLOWER than two one-head workgroups per CU — 112.7 vs
-        // 102.5 us at L = 213 —: tools/probe/attention2.hip, profiles/r02_gemm_experiments.md)
-        return causal ? fwd_launch<bf16_t, true>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, rs) : fwd_launch<bf16_t, false>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, rs);
-    }
-    return LPI_EINVAL;
-}
-
-extern "C" int lpi_attn_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, int causal,
-                            void* stream) {
-    return lpi_attn_fwd_varlen(dtype, B, L, nullptr, H, qkv, ldqkv, ctx, ldctx, lse, causal, stream);
-}
-
-// two forwards (2-byte operand types) in one launch; any other case runs as two launches
-template <typename T>
-static int fwd_pair_launch(const lpi_attn_fwd_desc* d, hipStream_t s) {
-    AttnFwdP<T> p[2];
-    size_t lds = 0;
-    int thr = 0;
-    for (int i = 0; i < 2; ++i) {
-        const int Lp = (d[i].L + 31) / 32 * 32;
-        const int pre = d[i].shared_rows;
-        if (pre < 0 || (pre > 0 && (!d[i].causal || !d[i].row_start || pre >= d[i].L))) return LPI_EINVAL;
-        p[i] = AttnFwdP<T>{d[i].L, Lp, d[i].H, d[i].ldqkv, d[i].ldctx, d[i].row_start, (const T*)d[i].qkv, (T*)d[i].ctx, d[i].lse, pre, pre > 0 ? d[i].B : -1,
-                           d[i].qkv_hs, d[i].qkv_vs, d[i].ctx_hs};
-        lds = std::max(lds, (size_t)2 * Lp * AT<T>::RS);
-        thr = std::max(thr, 64 * (d[i].row_start ? pick_waves_ragged(d[i].L) : pick_waves(d[i].L)));
-    }
-    const int nb0 = (d[0].B + (d[0].shared_rows > 0)) * d[0].H, nb1 = (d[1].B + (d[1].shared_rows > 0)) * d[1].H;
-    if (!d[0].causal && d[1].causal && !d[0].row_start && fwd_swizzled(p[0].Lp)) {      // a long vision sequence beside the text tower: problem 0 on the swizzled images
-        const size_t lsw = std::max((size_t)2 * p[0].Lp * 128, (size_t)2 * p[1].Lp * AT<T>::RS);
-        if (int e = set_lds((const void*)attn_fwd_pair_kernel<T, false, true, true>, lsw)) return e;
-        LPI_LAUNCH((attn_fwd_pair_kernel<T, false, true, true>), dim3(nb0 + nb1), dim3(thr), lsw, s, p[0], p[1], nb0);
-        LPI_CHECK_LAST();
-        return 0;
-    }
-#define FP(C0, C1)                                                                                                              \
-    do {                                                                                                                        \
-        if (int e = set_lds((const void*)attn_fwd_pair_kernel<T, C0, C1>, lds)) return e;                                       \
-        LPI_LAUNCH((attn_fwd_pair_kernel<T, C0, C1>), dim3(nb0 + nb1), dim3(thr), lds, s, p[0], p[1], nb0);                     \
-    } while (0)
-    if (d[0].causal && d[1].causal) FP(true, true);
-    else if (d[0].causal) FP(true, false);
-    else if (d[1].causal) FP(false, true);
-    else FP(false, false);
-#undef FP
-    LPI_CHECK_LAST();
-    return 0;
-}
-extern "C" int lpi_attn_fwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* qkv, int ldqkv, void* ctx, int ldctx,
-                                   float* lse, int causal, void* stream);
-extern "C" int lpi_attn_fwd_pair(int dtype, const lpi_attn_fwd_desc* d, void* stream) {
-    if (!d) return LPI_EINVAL;
-    bool any_long = false;
-    for (int i = 0; i < 2; ++i) {
-        const bool lay = d[i].qkv_hs || d[i].qkv_vs || d[i].ctx_hs;      // an explicit layout: the strides are the caller's statement, only their alignment is checked
-        if (lay && (dtype == LPI_F32 || d[i].row_start || d[i].shared_rows || !d[i].qkv_hs || !d[i].qkv_vs || !d[i].ctx_hs ||
-                    ((d[i].qkv_hs | d[i].qkv_vs | d[i].ctx_hs | d[i].ldqkv | d[i].ldctx) & 7) || d[i].ldqkv < HD || d[i].ldctx < HD)) return LPI_EINVAL;
-        const bool lng = !lay && !d[i].shared_rows && lpi_attn_long_ok(d[i].L, d[i].causal, d[i].row_start);      // a long sequence: its own launch (attn_long.hip)
-        any_long |= lng;
-        if (!d[i].qkv || !d[i].ctx || !d[i].lse || (!lay && (bad_attn(dtype, d[i].B, d[i].L, d[i].H, d[i].ldqkv, lng ? 1024 : 288) || d[i].ldctx < d[i].H * HD)) || (d[i].ldctx & 7))
-            return LPI_EINVAL;
-        if (lay && (d[i].B <= 0 || d[i].H <= 0 || d[i].L <= 0 || d[i].L > 288)) return LPI_EINVAL;
-        if (((uintptr_t)d[i].qkv | (uintptr_t)d[i].ctx) & 15) return LPI_EINVAL;
-    }
-    if (dtype == LPI_BF16 && !any_long) return fwd_pair_launch<bf16_t>(d, (hipStream_t)stream);
-    if (dtype == LPI_F16 && !any_long) return fwd_pair_launch<f16_t>(d, (hipStream_t)stream);
-    for (int i = 0; i < 2; ++i) {
-        if (d[i].shared_rows) {
-            if (int e = lpi_attn_fwd_shared(dtype, d[i].B, d[i].L, d[i].row_start, d[i].shared_rows, d[i].H, d[i].qkv, d[i].ldqkv, d[i].ctx, d[i].ldctx, d[i].lse, stream)) return e;
-            continue;
-        }
-        if (int e = lpi_attn_fwd_varlen(dtype, d[i].B, d[i].L, d[i].row_start, d[i].H, d[i].qkv, d[i].ldqkv, d[i].ctx, d[i].ldctx, d[i].lse, d[i].causal, stream))
-            return e;
-    }
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------------------ shared prefix (see attn_fwd_body)
 namespace {
@@ -1158,48 +970,301 @@ __global__ __launch_bounds__(256) void shared_kv_reduce_kernel(int B, int pre, i
 }
 }  // namespace
 
-extern "C" int lpi_shared_kv_reduce(int dtype, int B, int shared_rows, int H, const float* partial, void* dqkv, int lddqkv, int accumulate, void* stream) {
-    if (!partial || !dqkv || B <= 0 || shared_rows <= 0 || H <= 0 || lddqkv < 3 * H * HD || (lddqkv & 3) || ((uintptr_t)partial & 15) || ((uintptr_t)dqkv & (dtype == LPI_F32 ? 15 : 7))) return LPI_EINVAL;
-    const int dm = H * HD, n = shared_rows * (2 * dm / 4);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LPI_BF16 || dtype == LPI_F16)      // F16: "saved activations fp16, gradients bf16" (lpi_attn_bwd_prefix)
-        LPI_LAUNCH((shared_kv_reduce_kernel<bf16_t>), dim3((n + 15) / 16), dim3(256), 0, s, B, shared_rows, dm, partial, (bf16_t*)dqkv, lddqkv, accumulate);
-    else if (dtype == LPI_F32)
-        LPI_LAUNCH((shared_kv_reduce_kernel<float>), dim3((n + 15) / 16), dim3(256), 0, s, B, shared_rows, dm, partial, (float*)dqkv, lddqkv, accumulate);
-    else
-        return LPI_ENOSYS;
+// ------------------------------------------------------------------------------------------------ the host layer
+// Every entry point fills ONE AttnCall, asks the predicates below (each argument rule is written once; what an entry point adds to the common rule is one
+// explicit line at its call site) and hands the struct to fwd_run / bwd_run / fwd_pair_launch, which choose the template arguments by list (dispatch.h).
+namespace {
+
+// the arguments of one call of the one-head family; a field an entry point does not have keeps its default
+struct AttnCall {
+    int dtype = -1, B = 0, L = 0;
+    const int* row_start = nullptr;      // ragged batch: the one-head-per-workgroup kernels take a per-sample length
+    int H = 0;
+    const void* qkv = nullptr; int ldqkv = 0;
+    void* ctx = nullptr; int ldctx = 0;      // read-only in the backward
+    const void* dctx = nullptr; int lddctx = 0;
+    float* lse = nullptr;                    // read-only in the backward
+    float* delta = nullptr;
+    void* dqkv = nullptr; int lddqkv = 0;
+    int causal = 0;
+    int shared_rows = 0;                 // > 0 (causal ragged batches): B tail samples + the shared sequence as sample B (attn_fwd_body)
+    int rows_hi = 1 << 30;               // only dQ / dK / dV of token rows < rows_hi are wanted (the 2-byte kernels skip the 32-row blocks behind it; f32 computes all)
+    float* shared_dkv = nullptr;
+    int qkv_hs = 0, qkv_vs = 0, ctx_hs = 0;      // the forward's layout strides (lpi_attn_fwd_desc; all 0 = interleaved)
+    const int* lay = nullptr;            // the backward's: NULL = interleaved, else {qkv_hs, qkv_vs, dqkv_hs, dqkv_vs, ctx_hs, dctx_hs} (lpi_attn_bwd_layout)
+};
+
+// ---- the argument rules (host predicates: no HIP call)
+// counts, and one interleaved [rows, 3 H 64] leading dimension in whole 16-byte units
+inline bool bad_attn(int dtype, int B, int L, int H, int ld, int lmax) {
+    const int esz = dtype == LPI_F32 ? 4 : 2;
+    return B <= 0 || H <= 0 || L <= 0 || L > lmax || ld < 3 * H * HD || (ld * esz) % 16;
+}
+inline bool fwd_ptrs_ok(const AttnCall& c) { return c.qkv && c.ctx && c.lse && !(((uintptr_t)c.qkv | (uintptr_t)c.ctx) & 15); }
+inline bool bwd_ptrs_ok(const AttnCall& c) {
+    return c.qkv && c.ctx && c.dctx && c.lse && c.delta && c.dqkv && !(((uintptr_t)c.qkv | (uintptr_t)c.ctx | (uintptr_t)c.dctx | (uintptr_t)c.dqkv) & 15);
+}
+// the forward's interleaved operands: ctx is stored 8 elements at a time, so ldctx counts in 8 ELEMENTS whatever the type
+inline bool fwd_ok(const AttnCall& c, int lmax) { return fwd_ptrs_ok(c) && !bad_attn(c.dtype, c.B, c.L, c.H, c.ldqkv, lmax) && c.ldctx >= c.H * HD && !(c.ldctx & 7); }
+// the backward's: all four leading dimensions in whole 16-byte units
+inline bool bwd_ok(const AttnCall& c, int lmax) {
+    const int esz = c.dtype == LPI_F32 ? 4 : 2;
+    return bwd_ptrs_ok(c) && !bad_attn(c.dtype, c.B, c.L, c.H, c.ldqkv, lmax) && !bad_attn(c.dtype, c.B, c.L, c.H, c.lddqkv, lmax) && c.ldctx >= c.H * HD &&
+           c.lddctx >= c.H * HD && !((c.ldctx * esz) % 16) && !((c.lddctx * esz) % 16);
+}
+// an explicit layout: the strides are the caller's statement — non-zero, and with the leading dimensions (each >= 64) multiples of 8 elements; uniform sequences
+// of the one-workgroup-per-head lengths only
+inline bool layout_ok(const AttnCall& c, std::initializer_list<int> strides, std::initializer_list<int> lds) {
+    if (c.B <= 0 || c.H <= 0 || c.L <= 0 || c.L > 288 || c.row_start || c.shared_rows) return false;
+    int bits = 0;
+    for (int v : strides) { if (!v) return false; bits |= v; }
+    for (int v : lds) { if (v < HD) return false; bits |= v; }
+    return !(bits & 7);
+}
+inline bool fwd_layout_ok(const AttnCall& c) { return fwd_ptrs_ok(c) && layout_ok(c, {c.qkv_hs, c.qkv_vs, c.ctx_hs}, {c.ldqkv, c.ldctx}); }
+inline bool has_layout(const AttnCall& c) { return c.qkv_hs || c.qkv_vs || c.ctx_hs; }
+// a shared prefix: ragged, and shorter than the longest sequence
+inline bool shared_ok(const AttnCall& c) { return c.row_start && c.shared_rows > 0 && c.shared_rows < c.L; }
+// the streamed single-pass backward (attention4.hip) takes this call: 2-byte operands, uniform, a shape it was built for; the default for L > 160 (tuning
+// key 7 = 0), forced at every L it takes by key 7 = 5, never with key 7 = 1 or with the two-pass kernels forced (key 3)
+inline bool streamed_bwd_takes(const AttnCall& c) {
+    return (c.dtype == LPI_BF16 || c.dtype == LPI_F16) && !c.row_start && g_lpi_tuning[3] == 0 && lpi_attn4_bwd_ok(c.L, c.causal) &&
+           (g_lpi_tuning[7] == 5 || (g_lpi_tuning[7] == 0 && c.L > 160));
+}
+inline int lmax_of(bool lng) { return lng ? 1024 : 288; }
+
+// ---- the launches
+// waves per workgroup: each wave owns NB 16-row blocks per round; balance the rounds
+inline int pick_waves(int L) {
+    const int nqb = (L + 16 * NB - 1) / (16 * NB);
+    const int rounds = (nqb + 7) / 8;
+    return (nqb + rounds - 1) / rounds;
+}
+// ragged batches (the text tower: 2 000 workgroups of a few dozen rows, latency-bound): tuning key 9 = minimum number of waves per workgroup — the waves
+// beyond the row blocks take part in the staging only (more loads in flight per workgroup)
+inline int pick_waves_ragged(int L) {
+    const int w = pick_waves(L), lo = g_lpi_tuning[9];
+    return lo > w ? (lo < 8 ? lo : 8) : w;
+}
+inline int threads_of(const AttnCall& c) { return 64 * (c.row_start ? pick_waves_ragged(c.L) : pick_waves(c.L)); }
+inline int heads_of(const AttnCall& c) { return (c.B + (c.shared_rows > 0 ? 1 : 0)) * c.H; }      // a shared prefix is one more sample
+inline int bshared_of(const AttnCall& c) { return c.shared_rows > 0 ? c.B : -1; }
+
+// allow the full 160 KiB of a CU's LDS for a kernel: once per (kernel instantiation, device) — `once` is a function-local static beside that kernel's launch
+inline int set_lds(LdsOnce& once, const void* kern, size_t bytes) {
+    if (bytes > 160 * 1024) return LPI_EINVAL;
+    return lpi_ensure_lds(once, kern, 160 * 1024);
+}
+
+// the padded images of two workgroups do not fit a CU's 160 KiB but the unpadded ones do (tuning key 13 = 1: never; A/B switch)
+inline bool fwd_swizzled(int Lp) { return g_lpi_tuning[13] != 1 && (size_t)2 * 2 * Lp * 160 > (size_t)160 * 1024 && (size_t)2 * 2 * Lp * 128 <= (size_t)160 * 1024; }
+
+template <typename T, bool CAUSAL>
+int fwd_launch(const AttnCall& c, hipStream_t s) {
+    const int L = c.L, Lp = (L + 31) / 32 * 32, nbh = heads_of(c), thr = threads_of(c);
+    if constexpr (sizeof(T) == 2 && !CAUSAL) {
+        if (fwd_swizzled(Lp) && !c.row_start) {      // 257 .. 288 tokens: unpadded swizzled images, two workgroups per CU (stage_rows2)
+            static LdsOnce once;
+            const size_t lsw = (size_t)2 * Lp * 128;
+            if (int e = set_lds(once, (const void*)attn_fwd_kernel<T, CAUSAL, true>, lsw)) return e;
+            LPI_LAUNCH((attn_fwd_kernel<T, CAUSAL, true>), dim3(nbh), dim3(thr), lsw, s, L, Lp, c.row_start, c.H, (const T*)c.qkv, c.ldqkv, (T*)c.ctx, c.ldctx, c.lse,
+                       c.shared_rows, bshared_of(c), c.qkv_hs, c.qkv_vs, c.ctx_hs);
+            LPI_CHECK_LAST();
+            return 0;
+        }
+    }
+    static LdsOnce once;
+    const size_t lds = (size_t)2 * Lp * AT<T>::RS;
+    if (int e = set_lds(once, (const void*)attn_fwd_kernel<T, CAUSAL>, lds)) return e;
+    LPI_LAUNCH((attn_fwd_kernel<T, CAUSAL>), dim3(nbh), dim3(thr), lds, s, L, Lp, c.row_start, c.H, (const T*)c.qkv, c.ldqkv, (T*)c.ctx, c.ldctx, c.lse, c.shared_rows,
+               bshared_of(c), c.qkv_hs, c.qkv_vs, c.ctx_hs);
     LPI_CHECK_LAST();
     return 0;
 }
 
+// T: the gradients' type (dctx, dqkv) and the MFMA operands'; SV16: the saved qkv / ctx are fp16 and are converted on their way into LDS / registers
+template <typename T, bool CAUSAL, bool SV16>
+int bwd_launch(const AttnCall& c, hipStream_t s) {
+    // ctx / dctx keep their 64-element head stride here (lay[4], lay[5]: lpi_attn_bwd_layout checks them)
+    const int l0 = c.lay ? c.lay[0] : 0, l1 = c.lay ? c.lay[1] : 0, l2 = c.lay ? c.lay[2] : 0, l3 = c.lay ? c.lay[3] : 0;
+    const int L = c.L, Lp = (L + 31) / 32 * 32, nbh = heads_of(c), bsh = bshared_of(c), thr = threads_of(c);
+    const size_t ldsA = (size_t)2 * Lp * AT<T>::RS;
+    const size_t ldsB = ldsA + (size_t)2 * Lp * sizeof(float);
+    // fused single pass for 2-byte operands (HBM bound: -7 % at L = 213, -23 % at L = 77); f32 is compute bound and faster with the
+    // two-pass kernels at two workgroups per CU.  Tuning key 3 != 0 forces the two-pass kernels.
+    if constexpr (sizeof(T) == 2) {
+        const size_t ldsF = (size_t)4 * Lp * AT<T>::RS + (size_t)2 * Lp * sizeof(float);
+        if (ldsF <= 160 * 1024 && g_lpi_tuning[3] == 0) {
+            static LdsOnce once;
+            if (int e = set_lds(once, (const void*)attn_bwd_fused_kernel<T, CAUSAL, SV16>, ldsF)) return e;
+            LPI_LAUNCH((attn_bwd_fused_kernel<T, CAUSAL, SV16>), dim3(nbh), dim3(thr), ldsF, s, L, Lp, c.row_start, c.H, (const T*)c.qkv, c.ldqkv, (const T*)c.ctx, c.ldctx,
+                       (const T*)c.dctx, c.lddctx, c.lse, c.delta, (T*)c.dqkv, c.lddqkv, c.rows_hi, c.shared_rows, bsh, c.shared_dkv, l0, l1, l2, l3);
+            LPI_CHECK_LAST();
+            return 0;
+        }
+    }
+    static LdsOnce once_dq, once_dkv;
+    if (int e = set_lds(once_dq, (const void*)attn_bwd_dq_kernel<T, CAUSAL, SV16>, ldsA)) return e;
+    if (int e = set_lds(once_dkv, (const void*)attn_bwd_dkv_kernel<T, CAUSAL, SV16>, ldsB)) return e;
+    LPI_LAUNCH((attn_bwd_dq_kernel<T, CAUSAL, SV16>), dim3(nbh), dim3(thr), ldsA, s, L, Lp, c.row_start, c.H, (const T*)c.qkv, c.ldqkv, (const T*)c.ctx, c.ldctx,
+               (const T*)c.dctx, c.lddctx, c.lse, c.delta, (T*)c.dqkv, c.lddqkv, c.shared_rows, bsh, l0, l1, l2, l3);
+    LPI_CHECK_LAST();
+    LPI_LAUNCH((attn_bwd_dkv_kernel<T, CAUSAL, SV16>), dim3(nbh), dim3(thr), ldsB, s, L, Lp, c.row_start, c.H, (const T*)c.qkv, c.ldqkv, (const T*)c.dctx, c.lddctx,
+               c.lse, c.delta, (T*)c.dqkv, c.lddqkv, c.shared_rows, bsh, c.shared_dkv, l0, l1, l2, l3);
+    LPI_CHECK_LAST();
+    return 0;
+}
+
+// the combinations that are built.  Forward: q, k, v and ctx of one type (f16: the reference's own arithmetic type).  Backward: (gradients, saved activations) —
+// gradients do not fit fp16's range, so an f16-mode forward's backward has bf16 gradients; the call's dtype names the SAVED type.
+typedef TypeList<Types<float>, Types<f16_t>, Types<bf16_t>> FwdTypes;
+typedef TypeList<Types<float, float>, Types<bf16_t, bf16_t>, Types<bf16_t, f16_t>> BwdTypes;
+
+// the one-head kernels on call c; `unknown`: the code for a dtype outside the list
+// (a persistent forward with K / V double-buffered by LDS-DMA measured SLOWER than two one-head workgroups per CU — 112.7 vs 102.5 us at L = 213 —:
+// tools/probe/attention2.hip, profiles/r02_gemm_experiments.md)
+int fwd_run(const AttnCall& c, hipStream_t s, int unknown) {
+    int e = unknown;
+    dispatch_types(FwdTypes{}, [&](auto t) {
+        e = dispatch_bool([&](auto causal) { return fwd_launch<type_of<decltype(t)>, decltype(causal)::value>(c, s); }, c.causal != 0);
+    }, c.dtype);
+    return e;
+}
+int bwd_run(const AttnCall& c, hipStream_t s, int unknown) {
+    int e = unknown;
+    dispatch_types(BwdTypes{}, [&](auto t, auto ts) {
+        typedef type_of<decltype(t)> T;
+        e = dispatch_bool([&](auto causal) { return bwd_launch<T, decltype(causal)::value, !std::is_same<T, type_of<decltype(ts)>>::value>(c, s); }, c.causal != 0);
+    }, c.dtype == LPI_F16 ? LPI_BF16 : c.dtype, c.dtype);
+    return e;
+}
+
+// two forwards (2-byte operand types) in one launch; any other case runs as two launches
+template <typename T>
+int fwd_pair_launch(const AttnCall* c, hipStream_t s) {
+    AttnFwdP<T> p[2];
+    size_t lds = 0;
+    int thr = 0;
+    for (int i = 0; i < 2; ++i) {
+        const int Lp = (c[i].L + 31) / 32 * 32;
+        if (c[i].shared_rows != 0 && !(c[i].causal && shared_ok(c[i]))) return LPI_EINVAL;      // the fused launch adds: a shared prefix is causal
+        p[i] = AttnFwdP<T>{c[i].L, Lp, c[i].H, c[i].ldqkv, c[i].ldctx, c[i].row_start, (const T*)c[i].qkv, (T*)c[i].ctx, c[i].lse, c[i].shared_rows, bshared_of(c[i]),
+                           c[i].qkv_hs, c[i].qkv_vs, c[i].ctx_hs};
+        lds = std::max(lds, (size_t)2 * Lp * AT<T>::RS);
+        thr = std::max(thr, threads_of(c[i]));
+    }
+    const int nb0 = heads_of(c[0]), nb1 = heads_of(c[1]);
+    if (!c[0].causal && c[1].causal && !c[0].row_start && fwd_swizzled(p[0].Lp)) {      // a long vision sequence beside the text tower: problem 0 on the swizzled images
+        static LdsOnce once;
+        const size_t lsw = std::max((size_t)2 * p[0].Lp * 128, (size_t)2 * p[1].Lp * AT<T>::RS);
+        if (int e = set_lds(once, (const void*)attn_fwd_pair_kernel<T, false, true, true>, lsw)) return e;
+        LPI_LAUNCH((attn_fwd_pair_kernel<T, false, true, true>), dim3(nb0 + nb1), dim3(thr), lsw, s, p[0], p[1], nb0);
+        LPI_CHECK_LAST();
+        return 0;
+    }
+    return dispatch_bool([&](auto c0, auto c1) -> int {
+        static LdsOnce once;
+        if (int e = set_lds(once, (const void*)attn_fwd_pair_kernel<T, decltype(c0)::value, decltype(c1)::value>, lds)) return e;
+        LPI_LAUNCH((attn_fwd_pair_kernel<T, decltype(c0)::value, decltype(c1)::value>), dim3(nb0 + nb1), dim3(thr), lds, s, p[0], p[1], nb0);
+        LPI_CHECK_LAST();
+        return 0;
+    }, c[0].causal != 0, c[1].causal != 0);
+}
+
+// ---- the forms, on the struct (the extern "C" functions below only fill it)
+int fwd_varlen(const AttnCall& c, hipStream_t s) {
+    const bool lng = lpi_attn_long_ok(c.L, c.causal, c.row_start);
+    if (!fwd_ok(c, lmax_of(lng))) return LPI_EINVAL;
+    if (lng) return lpi_attn_long_fwd(c.dtype, c.B, c.L, c.H, c.qkv, c.ldqkv, c.ctx, c.ldctx, c.lse, s);
+    return fwd_run(c, s, LPI_EINVAL);
+}
+int fwd_shared(AttnCall c, hipStream_t s) {
+    if (!shared_ok(c) || !fwd_ok(c, 288)) return LPI_EINVAL;
+    c.causal = 1;
+    return fwd_run(c, s, LPI_ENOSYS);      // (lpi_attn_fwd_varlen answers an unknown dtype with LPI_EINVAL)
+}
+int fwd_plain(const AttnCall& c, hipStream_t s) { return c.shared_rows ? fwd_shared(c, s) : fwd_varlen(c, s); }
+
+AttnCall call_of(int dtype, const lpi_attn_fwd_desc& d) {
+    return AttnCall{.dtype = dtype, .B = d.B, .L = d.L, .row_start = d.row_start, .H = d.H, .qkv = d.qkv, .ldqkv = d.ldqkv, .ctx = d.ctx, .ldctx = d.ldctx, .lse = d.lse,
+                    .causal = d.causal, .shared_rows = d.shared_rows, .qkv_hs = d.qkv_hs, .qkv_vs = d.qkv_vs, .ctx_hs = d.ctx_hs};
+}
+
+}  // namespace
+
+extern "C" int lpi_attn_fwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* qkv, int ldqkv, void* ctx, int ldctx,
+                                   float* lse, int causal, void* stream) {
+    return fwd_varlen(AttnCall{.dtype = dtype, .B = B, .L = L, .row_start = row_start, .H = H, .qkv = qkv, .ldqkv = ldqkv, .ctx = ctx, .ldctx = ldctx, .lse = lse, .causal = causal},
+                      (hipStream_t)stream);
+}
+
+extern "C" int lpi_attn_fwd(int dtype, int B, int L, int H, const void* qkv, int ldqkv, void* ctx, int ldctx, float* lse, int causal,
+                            void* stream) {
+    return lpi_attn_fwd_varlen(dtype, B, L, nullptr, H, qkv, ldqkv, ctx, ldctx, lse, causal, stream);
+}
+
 extern "C" int lpi_attn_fwd_shared(int dtype, int B, int L, const int32_t* row_start, int shared_rows, int H, const void* qkv, int ldqkv, void* ctx, int ldctx,
                                    float* lse, void* stream) {
-    if (!qkv || !ctx || !lse || !row_start || shared_rows <= 0 || shared_rows >= L || bad_attn(dtype, B, L, H, ldqkv) || ldctx < H * HD || (ldctx & 7)) return LPI_EINVAL;
-    if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return LPI_EINVAL;
+    return fwd_shared(AttnCall{.dtype = dtype, .B = B, .L = L, .row_start = row_start, .H = H, .qkv = qkv, .ldqkv = ldqkv, .ctx = ctx, .ldctx = ldctx, .lse = lse,
+                               .shared_rows = shared_rows}, (hipStream_t)stream);
+}
+
+extern "C" int lpi_attn_fwd_pair(int dtype, const lpi_attn_fwd_desc* d, void* stream) {
+    if (!d) return LPI_EINVAL;
+    const AttnCall c[2] = {call_of(dtype, d[0]), call_of(dtype, d[1])};
+    bool any_long = false;
+    for (int i = 0; i < 2; ++i) {
+        if (has_layout(c[i])) {
+            if (dtype == LPI_F32 || !fwd_layout_ok(c[i])) return LPI_EINVAL;      // (any other unknown dtype is refused by the launches below)
+            continue;
+        }
+        const bool lng = !c[i].shared_rows && lpi_attn_long_ok(c[i].L, c[i].causal, c[i].row_start);      // a long sequence: its own launch (attn_long.hip)
+        any_long |= lng;
+        if (!fwd_ok(c[i], lmax_of(lng))) return LPI_EINVAL;      // a shared prefix is checked by the launch that takes it
+    }
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == LPI_F16) return fwd_launch<f16_t, true>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, row_start, shared_rows);
-    if (dtype == LPI_BF16) return fwd_launch<bf16_t, true>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, row_start, shared_rows);
-    if (dtype == LPI_F32) return fwd_launch<float, true>(B, L, H, qkv, ldqkv, ctx, ldctx, lse, s, row_start, shared_rows);
-    return LPI_ENOSYS;
+    if (dtype == LPI_BF16 && !any_long) return fwd_pair_launch<bf16_t>(c, s);
+    if (dtype == LPI_F16 && !any_long) return fwd_pair_launch<f16_t>(c, s);
+    for (int i = 0; i < 2; ++i) {
+        AttnCall ci = c[i];
+        ci.qkv_hs = ci.qkv_vs = ci.ctx_hs = 0;      // the single launches here take the interleaved rule only: a layout beside a long sequence is held to it
+        if (int e = fwd_plain(ci, s)) return e;
+    }
+    return 0;
+}
+
+// ONE forward in descriptor form (the only single-problem form that takes the layout strides of lpi_attn_fwd_desc)
+extern "C" int lpi_attn_fwd_one(int dtype, const lpi_attn_fwd_desc* d, void* stream) {
+    if (!d) return LPI_EINVAL;
+    const AttnCall c = call_of(dtype, *d);
+    if (!has_layout(c)) return fwd_plain(c, (hipStream_t)stream);
+    if ((dtype != LPI_BF16 && dtype != LPI_F16) || c.causal || !fwd_layout_ok(c)) return LPI_EINVAL;      // this form adds: non-causal (the pair takes a causal layout)
+    return fwd_run(c, (hipStream_t)stream, LPI_EINVAL);
+}
+
+extern "C" int lpi_shared_kv_reduce(int dtype, int B, int shared_rows, int H, const float* partial, void* dqkv, int lddqkv, int accumulate, void* stream) {
+    if (!partial || !dqkv || B <= 0 || shared_rows <= 0 || H <= 0 || lddqkv < 3 * H * HD || (lddqkv & 3) || ((uintptr_t)partial & 15) || ((uintptr_t)dqkv & (dtype == LPI_F32 ? 15 : 7))) return LPI_EINVAL;
+    const int dm = H * HD, n = shared_rows * (2 * dm / 4);
+    hipStream_t s = (hipStream_t)stream;
+    // the gradients' type: F16 is "saved activations fp16, gradients bf16" (lpi_attn_bwd_prefix)
+    if (!dispatch_types(TypeList<Types<bf16_t>, Types<float>>{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH((shared_kv_reduce_kernel<T>), dim3((n + 15) / 16), dim3(256), 0, s, B, shared_rows, dm, partial, (T*)dqkv, lddqkv, accumulate);
+        }, dtype == LPI_F16 ? LPI_BF16 : dtype)) return LPI_ENOSYS;
+    LPI_CHECK_LAST();
+    return 0;
 }
 
 extern "C" int lpi_attn_bwd_shared(int dtype, int B, int L, const int32_t* row_start, int shared_rows, int rows_needed, int H, const void* qkv, int ldqkv,
                                    const void* ctx, int ldctx, const void* dctx, int lddctx, const float* lse, float* delta, void* dqkv, int lddqkv,
                                    float* shared_dkv, void* stream) {
-    if (!row_start || !shared_dkv || shared_rows <= 0 || shared_rows >= L || rows_needed < shared_rows) return LPI_EINVAL;
-    const int rows_hi = rows_needed >= L ? (1 << 30) : rows_needed;
-    if (!qkv || !ctx || !dctx || !lse || !delta || !dqkv || bad_attn(dtype, B, L, H, ldqkv) || bad_attn(dtype, B, L, H, lddqkv)) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if (ldctx < H * HD || lddctx < H * HD || (ldctx * esz) % 16 || (lddctx * esz) % 16) return LPI_EINVAL;
-    if (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dqkv | (uintptr_t)shared_dkv) & 15) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    int e;
-    if (dtype == LPI_F32)      // the two-pass kernels (f32 is compute-bound); rows_needed is not used: everything is computed
-        e = bwd_launch<float, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, row_start, rows_hi, shared_rows, shared_dkv);
-    else if (dtype == LPI_F16) e = bwd_launch<bf16_t, true, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, row_start, rows_hi, shared_rows, shared_dkv);
-    else if (dtype == LPI_BF16) e = bwd_launch<bf16_t, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, row_start, rows_hi, shared_rows, shared_dkv);
-    else return LPI_ENOSYS;
-    if (e) return e;
+    // rows_hi: f32 (the two-pass kernels: compute-bound) does not use it: everything is computed
+    const AttnCall c{.dtype = dtype, .B = B, .L = L, .row_start = row_start, .H = H, .qkv = qkv, .ldqkv = ldqkv, .ctx = const_cast<void*>(ctx), .ldctx = ldctx, .dctx = dctx,
+                     .lddctx = lddctx, .lse = const_cast<float*>(lse), .delta = delta, .dqkv = dqkv, .lddqkv = lddqkv, .causal = 1, .shared_rows = shared_rows,
+                     .rows_hi = rows_needed >= L ? (1 << 30) : rows_needed, .shared_dkv = shared_dkv};
+    if (!shared_ok(c) || !bwd_ok(c, 288)) return LPI_EINVAL;
+    if (!shared_dkv || ((uintptr_t)shared_dkv & 15) || rows_needed < shared_rows) return LPI_EINVAL;      // this form adds: the f32 partials, and every shared row is needed
+    if (int e = bwd_run(c, (hipStream_t)stream, LPI_ENOSYS)) return e;
     // the shared sequence's own workgroups wrote dK / dV of the shared rows; the tail samples' partial sums are added on top
     return lpi_shared_kv_reduce(dtype, B, shared_rows, H, shared_dkv, dqkv, lddqkv, 1, stream);
 }
@@ -1207,37 +1272,17 @@ extern "C" int lpi_attn_bwd_shared(int dtype, int B, int L, const int32_t* row_s
 extern "C" int lpi_attn_bwd_prefix(int dtype, int B, int L, const int32_t* row_start, int rows_needed, int H, const void* qkv, int ldqkv, const void* ctx,
                                    int ldctx, const void* dctx, int lddctx, const float* lse, float* delta, void* dqkv, int lddqkv, int causal,
                                    void* stream) {
-    const int* rs = row_start;
-    if (rows_needed <= 0) return LPI_EINVAL;
-    const int rows_hi = rows_needed >= L ? (1 << 30) : rows_needed;      // the 2-byte kernels skip the 32-row blocks behind it; f32 computes all
+    const AttnCall c{.dtype = dtype, .B = B, .L = L, .row_start = row_start, .H = H, .qkv = qkv, .ldqkv = ldqkv, .ctx = const_cast<void*>(ctx), .ldctx = ldctx, .dctx = dctx,
+                     .lddctx = lddctx, .lse = const_cast<float*>(lse), .delta = delta, .dqkv = dqkv, .lddqkv = lddqkv, .causal = causal,
+                     .rows_hi = rows_needed >= L ? (1 << 30) : rows_needed};
     const bool lng = lpi_attn_long_ok(L, causal, row_start);
-    const int lmax = lng ? 1024 : 288;
-    if (!qkv || !ctx || !dctx || !lse || !delta || !dqkv || bad_attn(dtype, B, L, H, ldqkv, lmax) || bad_attn(dtype, B, L, H, lddqkv, lmax)) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if (ldctx < H * HD || lddctx < H * HD || (ldctx * esz) % 16 || (lddctx * esz) % 16) return LPI_EINVAL;
-    if (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dqkv) & 15) return LPI_EINVAL;
+    if (rows_needed <= 0 || !bwd_ok(c, lmax_of(lng))) return LPI_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (lng) return lpi_attn_long_bwd(dtype, B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s);      // every row (rows_needed is a saving, not a contract)
-    if (dtype == LPI_F32)
-        return causal ? bwd_launch<float, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, rs, rows_hi)
-                      : bwd_launch<float, false>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, rs, rows_hi);
-    if (dtype == LPI_F16) {     // saved qkv / ctx are fp16 (f16-mode forward); dctx and dqkv are bf16, and so are the MFMA operands:
-                                // q, k, v are converted on their way into LDS / registers (attention4.hip: in registers after the LDS read)
-        if (!rs && g_lpi_tuning[3] == 0 && lpi_attn4_bwd_ok(L, causal) && (g_lpi_tuning[7] == 5 || (g_lpi_tuning[7] == 0 && L > 160)))
-            return lpi_attn4_bwd(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, 1, rows_hi);
-        return causal ? bwd_launch<bf16_t, true, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, rs, rows_hi)
-                      : bwd_launch<bf16_t, false, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, rs, rows_hi);
-    }
-    if (dtype == LPI_BF16) {
-        // the streamed single-pass backward where a head's matrices would fill a CU's LDS (L = 213: 165-175 us against 271 us for the fused
-        // kernel below and 228 us for the two-phase persistent one, tools/probe/attention2.hip); at short L several one-head workgroups
-        // per CU are faster
-        if (!rs && g_lpi_tuning[3] == 0 && lpi_attn4_bwd_ok(L, causal) && (g_lpi_tuning[7] == 5 || (g_lpi_tuning[7] == 0 && L > 160)))
-            return lpi_attn4_bwd(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, 0, rows_hi);
-        return causal ? bwd_launch<bf16_t, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, rs, rows_hi)
-                      : bwd_launch<bf16_t, false>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, rs, rows_hi);
-    }
-    return LPI_EINVAL;
+    // the streamed single-pass backward where a head's matrices would fill a CU's LDS (L = 213: 165-175 us against 271 us for the fused kernel of this file
+    // and 228 us for the two-phase persistent one, tools/probe/attention2.hip); at short L several one-head workgroups per CU are faster
+    if (streamed_bwd_takes(c)) return lpi_attn4_bwd(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, dtype == LPI_F16, c.rows_hi);
+    return bwd_run(c, s, LPI_EINVAL);
 }
 
 extern "C" int lpi_attn_bwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx,
@@ -1250,39 +1295,19 @@ extern "C" int lpi_attn_bwd(int dtype, int B, int L, int H, const void* qkv, int
     return lpi_attn_bwd_varlen(dtype, B, L, nullptr, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, causal, stream);
 }
 
-// The backward on an explicit LAYOUT (round 6; see lpi_attn_fwd_desc): lay = {qkv_hs, qkv_vs, dqkv_hs, dqkv_vs, ctx_hs, dctx_hs}, element strides, multiples
-// of 8.  2-byte operand types, non-causal, uniform sequences.  Dispatch as lpi_attn_bwd_prefix: the streamed single-pass kernel (attention4.hip) where it is
-// the default, else the one-head-per-workgroup kernels of this file — those keep ctx / dctx at their interleaved head stride (ctx_hs = dctx_hs = 64).
+// The backward on an explicit LAYOUT (see lpi_attn_fwd_desc): lay = {qkv_hs, qkv_vs, dqkv_hs, dqkv_vs, ctx_hs, dctx_hs}, element strides, multiples of 8.
+// 2-byte operand types, non-causal, uniform sequences.  Dispatch as lpi_attn_bwd_prefix: the streamed single-pass kernel (attention4.hip) where it is the
+// default, else the one-head-per-workgroup kernels of this file — those keep ctx / dctx at their interleaved head stride (ctx_hs = dctx_hs = 64).
 extern "C" int lpi_attn_bwd_layout(int dtype, int B, int L, int rows_needed, int H, const void* qkv, int ldqkv, const void* ctx, int ldctx, const void* dctx,
                                    int lddctx, const float* lse, float* delta, void* dqkv, int lddqkv, const int32_t* lay, void* stream) {
-    if (!qkv || !ctx || !dctx || !lse || !delta || !dqkv || !lay || B <= 0 || H <= 0 || L <= 0 || L > 288) return LPI_EINVAL;
-    if (dtype != LPI_BF16 && dtype != LPI_F16) return LPI_EINVAL;
-    int bits = ldqkv | ldctx | lddctx | lddqkv;
-    for (int i = 0; i < 6; ++i) { if (lay[i] <= 0) return LPI_EINVAL; bits |= lay[i]; }
-    if ((bits & 7) || ldqkv < HD || ldctx < HD || lddctx < HD || lddqkv < HD) return LPI_EINVAL;
-    if (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dqkv) & 15) return LPI_EINVAL;
+    if (!lay || (dtype != LPI_BF16 && dtype != LPI_F16)) return LPI_EINVAL;
+    const AttnCall c{.dtype = dtype, .B = B, .L = L, .H = H, .qkv = qkv, .ldqkv = ldqkv, .ctx = const_cast<void*>(ctx), .ldctx = ldctx, .dctx = dctx, .lddctx = lddctx,
+                     .lse = const_cast<float*>(lse), .delta = delta, .dqkv = dqkv, .lddqkv = lddqkv, .rows_hi = rows_needed > 0 && rows_needed < L ? rows_needed : L, .lay = lay};
+    if (!bwd_ptrs_ok(c) || !layout_ok(c, {lay[0], lay[1], lay[2], lay[3], lay[4], lay[5]}, {ldqkv, ldctx, lddctx, lddqkv})) return LPI_EINVAL;
+    for (int i = 0; i < 6; ++i)
+        if (lay[i] < 0) return LPI_EINVAL;      // this form adds: no negative stride (the forward's layout forms take one)
     hipStream_t s = (hipStream_t)stream;
-    const int rows_hi = rows_needed > 0 && rows_needed < L ? rows_needed : L;
-    const int sv16 = dtype == LPI_F16 ? 1 : 0;
-    if (g_lpi_tuning[3] == 0 && lpi_attn4_bwd_ok(L, 0) && (g_lpi_tuning[7] == 5 || (g_lpi_tuning[7] == 0 && L > 160)))
-        return lpi_attn4_bwd(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, sv16, rows_hi, lay);
+    if (streamed_bwd_takes(c)) return lpi_attn4_bwd(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, dtype == LPI_F16, c.rows_hi, lay);
     if (lay[4] != HD || lay[5] != HD) return LPI_EINVAL;
-    return sv16 ? bwd_launch<bf16_t, false, true>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, nullptr, rows_hi, 0, nullptr, lay)
-                : bwd_launch<bf16_t, false>(B, L, H, qkv, ldqkv, ctx, ldctx, dctx, lddctx, lse, delta, dqkv, lddqkv, s, nullptr, rows_hi, 0, nullptr, lay);
-}
-
-// ONE forward in descriptor form (the only single-problem form that takes the layout strides of lpi_attn_fwd_desc)
-extern "C" int lpi_attn_fwd_one(int dtype, const lpi_attn_fwd_desc* d, void* stream) {
-    if (!d) return LPI_EINVAL;
-    const bool lay = d->qkv_hs || d->qkv_vs || d->ctx_hs;
-    if (!lay) {
-        if (d->shared_rows) return lpi_attn_fwd_shared(dtype, d->B, d->L, d->row_start, d->shared_rows, d->H, d->qkv, d->ldqkv, d->ctx, d->ldctx, d->lse, stream);
-        return lpi_attn_fwd_varlen(dtype, d->B, d->L, d->row_start, d->H, d->qkv, d->ldqkv, d->ctx, d->ldctx, d->lse, d->causal, stream);
-    }
-    if ((dtype != LPI_BF16 && dtype != LPI_F16) || d->row_start || d->shared_rows || d->causal || !d->qkv_hs || !d->qkv_vs || !d->ctx_hs) return LPI_EINVAL;
-    if (((d->qkv_hs | d->qkv_vs | d->ctx_hs | d->ldqkv | d->ldctx) & 7) || d->ldqkv < HD || d->ldctx < HD) return LPI_EINVAL;
-    if (!d->qkv || !d->ctx || !d->lse || d->B <= 0 || d->H <= 0 || d->L <= 0 || d->L > 288 || (((uintptr_t)d->qkv | (uintptr_t)d->ctx) & 15)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LPI_F16) return fwd_launch<f16_t, false>(d->B, d->L, d->H, d->qkv, d->ldqkv, d->ctx, d->ldctx, d->lse, s, nullptr, 0, d->qkv_hs, d->qkv_vs, d->ctx_hs);
-    return fwd_launch<bf16_t, false>(d->B, d->L, d->H, d->qkv, d->ldqkv, d->ctx, d->ldctx, d->lse, s, nullptr, 0, d->qkv_hs, d->qkv_vs, d->ctx_hs);
+    return bwd_run(c, s, LPI_EINVAL);
 }

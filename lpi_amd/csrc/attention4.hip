@@ -27,7 +27,7 @@
 // the stored one — the stored dQ rows of a slice arrive by LDS-DMA as a fourth piece of the slice's ring slot.  lse and delta are per query, so the
 // two windows are independent; dK / dV of a window are complete; two addends per dQ element in a fixed order: still bitwise reproducible.
 #include <type_traits>
-#include "common.h"
+#include "dispatch.h"
 
 extern int g_lpi_tuning[16];
 
@@ -698,6 +698,15 @@ size_t lds_bytes4(int Lkp, int Lqp, int win = 0) {
 }
 constexpr int WIN0 = 224;      // keys of the first window of a long sequence: the Lp = 224 configuration (14 key units over 8 waves)
 
+// one launch; the kernel instantiation's own LdsOnce sits beside it
+template <bool SV16, int NKB, int WIN>
+int launch4(int grid, size_t lds, hipStream_t s, const Args4& A) {
+    static LdsOnce once;
+    if (int e = lpi_ensure_lds(once, (const void*)attn_bwd4_kernel<SV16, NKB, WIN>, 160 * 1024)) return e;
+    LPI_LAUNCH((attn_bwd4_kernel<SV16, NKB, WIN>), dim3(grid), dim3(64 * NWV), lds, s, A);
+    return 0;
+}
+
 }  // namespace
 
 // true if the fourth-generation backward takes this shape (bf16 operands, non-causal, at most 8 x 2 key units)
@@ -717,42 +726,25 @@ int lpi_attn4_bwd(int B, int L, int H, const void* qkv, int ldqkv, const void* c
     const int total = B * H;
     int grid = std::min(total, cu_count4());
     if (g_lpi_tuning[11] > 0) grid = std::min(grid, g_lpi_tuning[11]);      // tests: several heads per workgroup at small B H
-    static LdsOnce o0, o1, o2, o3, w0, w1, w2, w3;
-    if (Lp > 32 * MAXKB) {
-        // a sequence of more than 224 tokens (ViT-L/14: 273) as TWO launches over all queries: keys 0 .. 223 (the Lp = 224 configuration), then keys
-        // 224 .. L - 1 (generic configuration, 4 units at most) whose dQ share is added to the first launch's.  lse and delta are per query, so the two
-        // key windows are independent; dK / dV of a window are complete.  Every query slice streams through twice (the price of not fitting 18 key
-        // units on 8 waves: three units per wave spill).
-#define BWD4W(S, K, W, O, ARGS, LDS)                                                                       \
-    do {                                                                                                   \
-        if (int e = lpi_ensure_lds(O, (const void*)attn_bwd4_kernel<S, K, W>, 160 * 1024)) return e;       \
-        LPI_LAUNCH((attn_bwd4_kernel<S, K, W>), dim3(grid), dim3(64 * NWV), LDS, s, ARGS);                 \
-    } while (0)
-        const int Lk1 = L - WIN0, Lkp1 = (Lk1 + 31) / 32 * 32;
-        const Args4 A0{L, Lp, H, total, (const T*)qkv, ldqkv, (const T*)ctx, ldctx, (const T*)dctx, lddctx, lse, delta, (T*)dqkv, lddqkv, rows_hi, g_lpi_tuning[12],
-                       0, WIN0, WIN0, 0, l_qh, l_qv, l_dh, l_dv, l_ch, l_dch};
-        const Args4 A1{L, Lp, H, total, (const T*)qkv, ldqkv, (const T*)ctx, ldctx, (const T*)dctx, lddctx, lse, delta, (T*)dqkv, lddqkv, rows_hi, g_lpi_tuning[12],
-                       WIN0, Lk1, Lkp1, 1, l_qh, l_qv, l_dh, l_dv, l_ch, l_dch};
-        if (saved_f16) { BWD4W(true, 7, 1, w0, A0, lds_bytes4(WIN0, Lp)); BWD4W(true, 0, 2, w1, A1, lds_bytes4(Lkp1, Lp, 2)); }
-        else { BWD4W(false, 7, 1, w2, A0, lds_bytes4(WIN0, Lp)); BWD4W(false, 0, 2, w3, A1, lds_bytes4(Lkp1, Lp, 2)); }
-#undef BWD4W
+    // the key window as written is the whole sequence; a windowed launch sets its own
+    Args4 A{L, Lp, H, total, (const T*)qkv, ldqkv, (const T*)ctx, ldctx, (const T*)dctx, lddctx, lse, delta, (T*)dqkv, lddqkv, rows_hi, g_lpi_tuning[12],
+            0, L, Lp, 0, l_qh, l_qv, l_dh, l_dv, l_ch, l_dch};
+    return dispatch_bool([&](auto sv16) -> int {
+        constexpr bool S = decltype(sv16)::value;
+        if (Lp > 32 * MAXKB) {
+            // a sequence of more than 224 tokens (ViT-L/14: 273) as TWO launches over all queries: keys 0 .. 223 (the Lp = 224 configuration), then keys
+            // 224 .. L - 1 (generic configuration, 4 units at most) whose dQ share is added to the first launch's.  lse and delta are per query, so the two
+            // key windows are independent; dK / dV of a window are complete.  Every query slice streams through twice (the price of not fitting 18 key
+            // units on 8 waves: three units per wave spill).
+            const int Lk1 = L - WIN0, Lkp1 = (Lk1 + 31) / 32 * 32;
+            A.kw0 = 0, A.Lk = WIN0, A.Lkp = WIN0, A.acc_dq = 0;
+            if (int e = launch4<S, 7, 1>(grid, lds_bytes4(WIN0, Lp), s, A)) return e;
+            A.kw0 = WIN0, A.Lk = Lk1, A.Lkp = Lkp1, A.acc_dq = 1;
+            if (int e = launch4<S, 0, 2>(grid, lds_bytes4(Lkp1, Lp, 2), s, A)) return e;
+        } else if (int e = dispatch_bool([&](auto tuned) { return launch4<S, decltype(tuned)::value ? 7 : 0, 0>(grid, lds_bytes4(Lp, Lp), s, A); }, Lp == 224)) {
+            return e;      // (tuned: the Lp = 224 configuration, NKB = 7)
+        }
         LPI_CHECK_LAST();
         return 0;
-    }
-    const size_t lds = lds_bytes4(Lp, Lp);
-    const Args4 A{L, Lp, H, total, (const T*)qkv, ldqkv, (const T*)ctx, ldctx, (const T*)dctx, lddctx, lse, delta, (T*)dqkv, lddqkv, rows_hi, g_lpi_tuning[12],
-                  0, L, Lp, 0, l_qh, l_qv, l_dh, l_dv, l_ch, l_dch};
-#define BWD4(S, K, O)                                                                               \
-    do {                                                                                            \
-        if (int e = lpi_ensure_lds(O, (const void*)attn_bwd4_kernel<S, K>, 160 * 1024)) return e;   \
-        LPI_LAUNCH((attn_bwd4_kernel<S, K>), dim3(grid), dim3(64 * NWV), lds, s, A);                \
-    } while (0)
-    if (Lp == 224) {
-        if (saved_f16) BWD4(true, 7, o0);
-        else BWD4(false, 7, o1);
-    } else if (saved_f16) BWD4(true, 0, o2);
-    else BWD4(false, 0, o3);
-#undef BWD4
-    LPI_CHECK_LAST();
-    return 0;
+    }, saved_f16 != 0);
 }

@@ -7,7 +7,8 @@
 // instruction (each key row is one contiguous 128 B / 256 B read), 4-step xor reduction.  Softmax row in LDS; every wave reduces
 // it for itself.  Context / dQ / dK / dV: lane = head dim, loop over keys, so every row access is one whole head row; the four
 // partial context / dQ rows are summed through LDS in a fixed order.  No atomics: bitwise reproducible.
-#include "common.h"
+#include <algorithm>
+#include "dispatch.h"
 
 namespace {
 
@@ -198,192 +199,121 @@ __global__ __launch_bounds__(WAVE * WPB) void attn_pooled_bwd_pair_kernel(PoolBw
                                 p.ldo, p.lse, (T*)p.dq, p.lddq, (T*)p.dqkv, p.ldg, p.causal, p.pre, p.part);
 }
 
+// ---- the host layer: every form fills a lpi_attn_pooled_desc (one problem; the _pair forms bring two); one predicate and one launch per direction
+typedef TypeList<Types<float>, Types<bf16_t>, Types<f16_t>> PooledFwdTypes;
+// (gradients in and out, saved q / qkv): an f16-mode forward saved fp16, its gradients are bf16; the call's dtype names the SAVED type
+typedef TypeList<Types<float, float>, Types<bf16_t, bf16_t>, Types<bf16_t, f16_t>> PooledBwdTypes;
+inline int grad_dtype(int dtype) { return dtype == LPI_F16 ? LPI_BF16 : dtype; }
+
+// LDS of a workgroup: `rows` score-sized rows of L rounded up to 64 floats + the waves' partial head rows
+inline int pooled_lp(int L) { return (L + 63) / 64 * 64; }
+inline size_t pooled_lds(int L, int rows) { return (size_t)(rows * pooled_lp(L) + WPB * DH) * sizeof(float); }
+// the shared-prefix fields: none, or a causal ragged batch with its queries' positions, the prefix shorter than the longest sequence
+inline bool pooled_shared_ok(const lpi_attn_pooled_desc& d) { return d.shared_rows == 0 || (d.shared_rows > 0 && d.causal && d.row_start && d.idx && d.shared_rows < d.L); }
+
+// q and qkv are read four elements at a time (whole 16-byte units, 16-byte aligned); ctx is written one element per lane
+bool pooled_fwd_ok(int dtype, const lpi_attn_pooled_desc& d) {
+    const int esz = dtype == LPI_F32 ? 4 : 2;
+    if (!d.q || !d.qkv || !d.ctx || !d.lse || d.B <= 0 || d.L <= 0 || d.H <= 0) return false;
+    if (d.ldqkv < 3 * d.H * DH || d.ldq < d.H * DH || d.ldctx < d.H * DH || (d.ldqkv * esz) % 16 || (d.ldq * esz) % 16) return false;
+    if (((uintptr_t)d.q | (uintptr_t)d.qkv) & 15) return false;
+    return pooled_lds(d.L, 2) <= 64 * 1024 && pooled_shared_ok(d);
+}
+// the same for q, qkv and dctx; dq and dqkv are written one element per lane.  On a shared prefix dqkv and shared_dkv go through lpi_shared_kv_reduce after
+// the launch (four elements per lane): its conditions are refused here, before any launch
+bool pooled_bwd_ok(int dtype, const lpi_attn_pooled_desc& d) {
+    const int esz = dtype == LPI_F32 ? 4 : 2;
+    if (!d.q || !d.qkv || !d.dctx || !d.lse || !d.dq || !d.dqkv || d.B <= 0 || d.L <= 0 || d.H <= 0) return false;
+    if (d.ldqkv < 3 * d.H * DH || d.lddqkv < 3 * d.H * DH || d.ldq < d.H * DH || d.lddctx < d.H * DH || d.lddq < d.H * DH) return false;
+    if ((d.ldqkv * esz) % 16 || (d.ldq * esz) % 16 || (d.lddctx * esz) % 16) return false;
+    if (((uintptr_t)d.q | (uintptr_t)d.qkv | (uintptr_t)d.dctx) & 15) return false;
+    if (pooled_lds(d.L, 3) > 64 * 1024 || !pooled_shared_ok(d)) return false;
+    return d.shared_rows == 0 || (d.shared_dkv && !(d.lddqkv & 3) && !((uintptr_t)d.shared_dkv & 15) && !((uintptr_t)d.dqkv & (dtype == LPI_F32 ? 15 : 7)));
+}
+
+// a single problem on a shared prefix is causal by rule: the kernel is handed 1, whatever non-zero value the descriptor holds
+inline int causal_of(const lpi_attn_pooled_desc& d) { return d.shared_rows ? 1 : d.causal; }
+
+int pooled_fwd(int dtype, const lpi_attn_pooled_desc& d, void* stream) {
+    if (!pooled_fwd_ok(dtype, d)) return LPI_EINVAL;
+    if (!dispatch_types(PooledFwdTypes{}, [&](auto t) {
+            typedef type_of<decltype(t)> T;
+            LPI_LAUNCH((attn_pooled_fwd_kernel<T>), dim3(d.B * d.H), dim3(WAVE * WPB), pooled_lds(d.L, 2), (hipStream_t)stream, d.B, d.L, d.row_start, d.H, pooled_lp(d.L),
+                       (const T*)d.q, d.ldq, (const T*)d.qkv, d.ldqkv, d.idx, (T*)d.ctx, d.ldctx, d.lse, causal_of(d), d.shared_rows);
+        }, dtype)) return LPI_ENOSYS;
+    LPI_CHECK_LAST();
+    return 0;
+}
+
+int pooled_bwd(int dtype, const lpi_attn_pooled_desc& d, void* stream) {
+    if (!pooled_bwd_ok(dtype, d)) return LPI_EINVAL;
+    if (!dispatch_types(PooledBwdTypes{}, [&](auto t, auto ts) {
+            typedef type_of<decltype(t)> T;
+            typedef type_of<decltype(ts)> TS;
+            LPI_LAUNCH((attn_pooled_bwd_kernel<T, TS>), dim3(d.B * d.H), dim3(WAVE * WPB), pooled_lds(d.L, 3), (hipStream_t)stream, d.B, d.L, d.row_start, d.H, pooled_lp(d.L),
+                       (const TS*)d.q, d.ldq, (const TS*)d.qkv, d.ldqkv, d.idx, (const T*)d.dctx, d.lddctx, d.lse, (T*)d.dq, d.lddq, (T*)d.dqkv, d.lddqkv, causal_of(d),
+                       d.shared_rows, d.shared_rows ? d.shared_dkv : nullptr);
+        }, grad_dtype(dtype), dtype)) return LPI_ENOSYS;
+    LPI_CHECK_LAST();
+    // shared prefix: no query sits on the shared rows here, so their dK / dV are the samples' sum alone (written, not added)
+    return d.shared_rows ? lpi_shared_kv_reduce(dtype, d.B, d.shared_rows, d.H, d.shared_dkv, d.dqkv, d.lddqkv, 0, stream) : 0;
+}
+
 }  // namespace
 
 extern "C" int lpi_attn_pooled_fwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* q, int ldq, const void* qkv, int ld,
                                           const int* idx, void* ctx, int ldo, float* lse, int causal, void* stream)
 {
-    const int* rs = row_start;
-    if (!q || !qkv || !ctx || !lse || B <= 0 || L <= 0 || H <= 0) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if (ld < 3 * H * DH || ldq < H * DH || ldo < H * DH || (ld * esz) % 16 || (ldq * esz) % 16) return LPI_EINVAL;
-    if (((uintptr_t)q | (uintptr_t)qkv) & 15) return LPI_EINVAL;
-    const int Lp = (L + 63) / 64 * 64;
-    const size_t lds = (size_t)(2 * Lp + WPB * DH) * sizeof(float);
-    if (lds > 64 * 1024) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(B * H), block(WAVE * WPB);
-    if (dtype == LPI_F32)
-        LPI_LAUNCH((attn_pooled_fwd_kernel<float>), grid, block, lds, s, B, L, rs, H, Lp, (const float*)q, ldq, (const float*)qkv, ld, idx,
-                   (float*)ctx, ldo, lse, causal, 0);
-    else if (dtype == LPI_BF16)
-        LPI_LAUNCH((attn_pooled_fwd_kernel<bf16_t>), grid, block, lds, s, B, L, rs, H, Lp, (const bf16_t*)q, ldq, (const bf16_t*)qkv, ld, idx,
-                   (bf16_t*)ctx, ldo, lse, causal, 0);
-    else if (dtype == LPI_F16)
-        LPI_LAUNCH((attn_pooled_fwd_kernel<f16_t>), grid, block, lds, s, B, L, rs, H, Lp, (const f16_t*)q, ldq, (const f16_t*)qkv, ld, idx,
-                   (f16_t*)ctx, ldo, lse, causal, 0);
-    else
-        return LPI_ENOSYS;
-    LPI_CHECK_LAST();
-    return 0;
+    return pooled_fwd(dtype, lpi_attn_pooled_desc{.B = B, .L = L, .H = H, .row_start = row_start, .q = q, .ldq = ldq, .qkv = qkv, .ldqkv = ld, .idx = idx, .ctx = ctx,
+                                                  .ldctx = ldo, .lse = lse, .causal = causal}, stream);
 }
 
 extern "C" int lpi_attn_pooled_bwd_varlen(int dtype, int B, int L, const int32_t* row_start, int H, const void* q, int ldq, const void* qkv, int ld,
                                           const int* idx, const void* dctx, int ldo, const float* lse, void* dq, int lddq, void* dqkv, int ldg,
                                           int causal, void* stream)
 {
-    const int* rs = row_start;
-    if (!q || !qkv || !dctx || !lse || !dq || !dqkv || B <= 0 || L <= 0 || H <= 0) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if (ld < 3 * H * DH || ldg < 3 * H * DH || ldq < H * DH || ldo < H * DH || lddq < H * DH) return LPI_EINVAL;
-    if ((ld * esz) % 16 || (ldq * esz) % 16 || (ldo * esz) % 16) return LPI_EINVAL;
-    if (((uintptr_t)q | (uintptr_t)qkv | (uintptr_t)dctx) & 15) return LPI_EINVAL;
-    const int Lp = (L + 63) / 64 * 64;
-    const size_t lds = (size_t)(3 * Lp + WPB * DH) * sizeof(float);
-    if (lds > 64 * 1024) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(B * H), block(WAVE * WPB);
-    if (dtype == LPI_F32)
-        LPI_LAUNCH((attn_pooled_bwd_kernel<float>), grid, block, lds, s, B, L, rs, H, Lp, (const float*)q, ldq, (const float*)qkv, ld, idx,
-                   (const float*)dctx, ldo, lse, (float*)dq, lddq, (float*)dqkv, ldg, causal, 0, nullptr);
-    else if (dtype == LPI_BF16)
-        LPI_LAUNCH((attn_pooled_bwd_kernel<bf16_t>), grid, block, lds, s, B, L, rs, H, Lp, (const bf16_t*)q, ldq, (const bf16_t*)qkv, ld, idx,
-                   (const bf16_t*)dctx, ldo, lse, (bf16_t*)dq, lddq, (bf16_t*)dqkv, ldg, causal, 0, nullptr);
-    else if (dtype == LPI_F16)      // saved q / qkv are fp16 (f16-mode forward); the gradients in and out are bf16
-        LPI_LAUNCH((attn_pooled_bwd_kernel<bf16_t, f16_t>), grid, block, lds, s, B, L, rs, H, Lp, (const f16_t*)q, ldq, (const f16_t*)qkv, ld, idx,
-                   (const bf16_t*)dctx, ldo, lse, (bf16_t*)dq, lddq, (bf16_t*)dqkv, ldg, causal, 0, nullptr);
-    else
-        return LPI_ENOSYS;
-    LPI_CHECK_LAST();
-    return 0;
+    return pooled_bwd(dtype, lpi_attn_pooled_desc{.B = B, .L = L, .H = H, .row_start = row_start, .q = q, .ldq = ldq, .qkv = qkv, .ldqkv = ld, .idx = idx,
+                                                  .lse = const_cast<float*>(lse), .dctx = dctx, .lddctx = ldo, .dq = dq, .lddq = lddq, .dqkv = dqkv, .lddqkv = ldg,
+                                                  .causal = causal}, stream);
 }
+
+// one problem through the descriptor form (the shared-prefix fields exist there only).  Without a shared prefix this is the _varlen form: shared_dkv is not looked at
+extern "C" int lpi_attn_pooled_fwd_desc(int dtype, const lpi_attn_pooled_desc* d, void* stream) { return d ? pooled_fwd(dtype, *d, stream) : LPI_EINVAL; }
+extern "C" int lpi_attn_pooled_bwd_desc(int dtype, const lpi_attn_pooled_desc* d, void* stream) { return d ? pooled_bwd(dtype, *d, stream) : LPI_EINVAL; }
 
 // ---- the two towers' pooled attention in one launch (same kernels' bodies, bit for bit); desc[i]: the arguments of the _varlen entry points
 extern "C" int lpi_attn_pooled_fwd_pair(int dtype, const lpi_attn_pooled_desc* d, void* stream)
 {
-    if (!d) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
+    if (!d || !pooled_fwd_ok(dtype, d[0]) || !pooled_fwd_ok(dtype, d[1])) return LPI_EINVAL;
     PoolFwdP p[2];
-    size_t lds = 0;
-    for (int i = 0; i < 2; ++i) {
-        const lpi_attn_pooled_desc& q = d[i];
-        if (!q.q || !q.qkv || !q.ctx || !q.lse || q.B <= 0 || q.L <= 0 || q.H <= 0) return LPI_EINVAL;
-        if (q.ldqkv < 3 * q.H * DH || q.ldq < q.H * DH || q.ldctx < q.H * DH || (q.ldqkv * esz) % 16 || (q.ldq * esz) % 16) return LPI_EINVAL;
-        if (((uintptr_t)q.q | (uintptr_t)q.qkv) & 15) return LPI_EINVAL;
-        const int Lp = (q.L + 63) / 64 * 64;
-        lds = std::max(lds, (size_t)(2 * Lp + WPB * DH) * sizeof(float));
-        if (q.shared_rows < 0 || (q.shared_rows > 0 && (!q.causal || !q.row_start || !q.idx || q.shared_rows >= q.L))) return LPI_EINVAL;
-        p[i] = PoolFwdP{q.B, q.L, q.H, Lp, q.ldq, q.ldqkv, q.ldctx, q.causal, q.row_start, q.q, q.qkv, q.idx, q.ctx, q.lse, q.shared_rows};
-    }
-    if (lds > 64 * 1024) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < 2; ++i)
+        p[i] = PoolFwdP{d[i].B, d[i].L, d[i].H, pooled_lp(d[i].L), d[i].ldq, d[i].ldqkv, d[i].ldctx, d[i].causal, d[i].row_start, d[i].q, d[i].qkv, d[i].idx, d[i].ctx, d[i].lse,
+                        d[i].shared_rows};
     const int nb0 = p[0].B * p[0].H;
-    const dim3 grid(nb0 + p[1].B * p[1].H), block(WAVE * WPB);
-    if (dtype == LPI_F32) LPI_LAUNCH((attn_pooled_fwd_pair_kernel<float>), grid, block, lds, s, p[0], p[1], nb0);
-    else if (dtype == LPI_BF16) LPI_LAUNCH((attn_pooled_fwd_pair_kernel<bf16_t>), grid, block, lds, s, p[0], p[1], nb0);
-    else if (dtype == LPI_F16) LPI_LAUNCH((attn_pooled_fwd_pair_kernel<f16_t>), grid, block, lds, s, p[0], p[1], nb0);
-    else return LPI_ENOSYS;
+    const size_t lds = pooled_lds(std::max(d[0].L, d[1].L), 2);
+    if (!dispatch_types(PooledFwdTypes{}, [&](auto t) {
+            LPI_LAUNCH((attn_pooled_fwd_pair_kernel<type_of<decltype(t)>>), dim3(nb0 + p[1].B * p[1].H), dim3(WAVE * WPB), lds, (hipStream_t)stream, p[0], p[1], nb0);
+        }, dtype)) return LPI_ENOSYS;
     LPI_CHECK_LAST();
     return 0;
 }
 extern "C" int lpi_attn_pooled_bwd_pair(int dtype, const lpi_attn_pooled_desc* d, void* stream)
 {
-    if (!d) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
+    if (!d || !pooled_bwd_ok(dtype, d[0]) || !pooled_bwd_ok(dtype, d[1])) return LPI_EINVAL;
     PoolBwdP p[2];
-    size_t lds = 0;
-    for (int i = 0; i < 2; ++i) {
-        const lpi_attn_pooled_desc& q = d[i];
-        if (!q.q || !q.qkv || !q.dctx || !q.lse || !q.dq || !q.dqkv || q.B <= 0 || q.L <= 0 || q.H <= 0) return LPI_EINVAL;
-        if (q.ldqkv < 3 * q.H * DH || q.lddqkv < 3 * q.H * DH || q.ldq < q.H * DH || q.lddctx < q.H * DH || q.lddq < q.H * DH) return LPI_EINVAL;
-        if ((q.ldqkv * esz) % 16 || (q.ldq * esz) % 16 || (q.lddctx * esz) % 16) return LPI_EINVAL;
-        if (((uintptr_t)q.q | (uintptr_t)q.qkv | (uintptr_t)q.dctx) & 15) return LPI_EINVAL;
-        const int Lp = (q.L + 63) / 64 * 64;
-        lds = std::max(lds, (size_t)(3 * Lp + WPB * DH) * sizeof(float));
-        if (q.shared_rows < 0 || (q.shared_rows > 0 && (!q.causal || !q.row_start || !q.idx || q.shared_rows >= q.L || !q.shared_dkv))) return LPI_EINVAL;
-        // shared prefix: dqkv and shared_dkv go through lpi_shared_kv_reduce after the launch (four elements per lane): its conditions are refused here, before it
-        if (q.shared_rows > 0 && ((q.lddqkv & 3) || ((uintptr_t)q.shared_dkv & 15) || ((uintptr_t)q.dqkv & (dtype == LPI_F32 ? 15 : 7)))) return LPI_EINVAL;
-        p[i] = PoolBwdP{q.B, q.L, q.H, Lp, q.ldq, q.ldqkv, q.lddctx, q.lddq, q.lddqkv, q.causal, q.row_start, q.q, q.qkv, q.idx, q.dctx, q.lse, q.dq, q.dqkv, q.shared_rows,
-                        q.shared_dkv};
-    }
-    if (lds > 64 * 1024) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < 2; ++i)
+        p[i] = PoolBwdP{d[i].B, d[i].L, d[i].H, pooled_lp(d[i].L), d[i].ldq, d[i].ldqkv, d[i].lddctx, d[i].lddq, d[i].lddqkv, d[i].causal, d[i].row_start, d[i].q, d[i].qkv, d[i].idx,
+                        d[i].dctx, d[i].lse, d[i].dq, d[i].dqkv, d[i].shared_rows, d[i].shared_dkv};
     const int nb0 = p[0].B * p[0].H;
-    const dim3 grid(nb0 + p[1].B * p[1].H), block(WAVE * WPB);
-    if (dtype == LPI_F32) LPI_LAUNCH((attn_pooled_bwd_pair_kernel<float>), grid, block, lds, s, p[0], p[1], nb0);
-    else if (dtype == LPI_BF16) LPI_LAUNCH((attn_pooled_bwd_pair_kernel<bf16_t>), grid, block, lds, s, p[0], p[1], nb0);
-    else if (dtype == LPI_F16) LPI_LAUNCH((attn_pooled_bwd_pair_kernel<bf16_t, f16_t>), grid, block, lds, s, p[0], p[1], nb0);
-    else return LPI_ENOSYS;
+    const size_t lds = pooled_lds(std::max(d[0].L, d[1].L), 3);
+    if (!dispatch_types(PooledBwdTypes{}, [&](auto t, auto ts) {
+            LPI_LAUNCH((attn_pooled_bwd_pair_kernel<type_of<decltype(t)>, type_of<decltype(ts)>>), dim3(nb0 + p[1].B * p[1].H), dim3(WAVE * WPB), lds, (hipStream_t)stream, p[0], p[1], nb0);
+        }, grad_dtype(dtype), dtype)) return LPI_ENOSYS;
     LPI_CHECK_LAST();
-    for (int i = 0; i < 2; ++i)      // shared prefix: no query sits on the shared rows here, so their dK / dV are the samples' sum alone (written, not added)
+    for (int i = 0; i < 2; ++i)      // shared prefix: as pooled_bwd
         if (d[i].shared_rows > 0)
             if (int e = lpi_shared_kv_reduce(dtype, d[i].B, d[i].shared_rows, d[i].H, d[i].shared_dkv, d[i].dqkv, d[i].lddqkv, 0, stream)) return e;
     return 0;
-}
-
-// one problem through the descriptor form (the shared-prefix fields exist there only); a second, empty problem rides along
-extern "C" int lpi_attn_pooled_fwd_desc(int dtype, const lpi_attn_pooled_desc* d, void* stream)
-{
-    if (!d) return LPI_EINVAL;
-    if (!d->shared_rows)
-        return lpi_attn_pooled_fwd_varlen(dtype, d->B, d->L, d->row_start, d->H, d->q, d->ldq, d->qkv, d->ldqkv, d->idx, d->ctx, d->ldctx, d->lse, d->causal, stream);
-    if (!d->q || !d->qkv || !d->ctx || !d->lse || !d->row_start || !d->idx || !d->causal || d->B <= 0 || d->L <= 0 || d->H <= 0 || d->shared_rows < 0 || d->shared_rows >= d->L)
-        return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if (d->ldqkv < 3 * d->H * DH || d->ldq < d->H * DH || d->ldctx < d->H * DH || (d->ldqkv * esz) % 16 || (d->ldq * esz) % 16) return LPI_EINVAL;
-    if (((uintptr_t)d->q | (uintptr_t)d->qkv) & 15) return LPI_EINVAL;
-    const int Lp = (d->L + 63) / 64 * 64;
-    const size_t lds = (size_t)(2 * Lp + WPB * DH) * sizeof(float);
-    if (lds > 64 * 1024) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(d->B * d->H), block(WAVE * WPB);
-    if (dtype == LPI_F32)
-        LPI_LAUNCH((attn_pooled_fwd_kernel<float>), grid, block, lds, s, d->B, d->L, d->row_start, d->H, Lp, (const float*)d->q, d->ldq, (const float*)d->qkv, d->ldqkv, d->idx,
-                   (float*)d->ctx, d->ldctx, d->lse, 1, d->shared_rows);
-    else if (dtype == LPI_BF16)
-        LPI_LAUNCH((attn_pooled_fwd_kernel<bf16_t>), grid, block, lds, s, d->B, d->L, d->row_start, d->H, Lp, (const bf16_t*)d->q, d->ldq, (const bf16_t*)d->qkv, d->ldqkv, d->idx,
-                   (bf16_t*)d->ctx, d->ldctx, d->lse, 1, d->shared_rows);
-    else if (dtype == LPI_F16)
-        LPI_LAUNCH((attn_pooled_fwd_kernel<f16_t>), grid, block, lds, s, d->B, d->L, d->row_start, d->H, Lp, (const f16_t*)d->q, d->ldq, (const f16_t*)d->qkv, d->ldqkv, d->idx,
-                   (f16_t*)d->ctx, d->ldctx, d->lse, 1, d->shared_rows);
-    else
-        return LPI_ENOSYS;
-    LPI_CHECK_LAST();
-    return 0;
-}
-extern "C" int lpi_attn_pooled_bwd_desc(int dtype, const lpi_attn_pooled_desc* d, void* stream)
-{
-    if (!d) return LPI_EINVAL;
-    if (!d->shared_rows)
-        return lpi_attn_pooled_bwd_varlen(dtype, d->B, d->L, d->row_start, d->H, d->q, d->ldq, d->qkv, d->ldqkv, d->idx, d->dctx, d->lddctx, d->lse, d->dq, d->lddq, d->dqkv,
-                                          d->lddqkv, d->causal, stream);
-    if (!d->q || !d->qkv || !d->dctx || !d->lse || !d->dq || !d->dqkv || !d->shared_dkv || !d->row_start || !d->idx || !d->causal || d->B <= 0 || d->L <= 0 || d->H <= 0 ||
-        d->shared_rows < 0 || d->shared_rows >= d->L)
-        return LPI_EINVAL;
-    if (d->ldqkv < 3 * d->H * DH || d->lddqkv < 3 * d->H * DH || d->ldq < d->H * DH || d->lddctx < d->H * DH || d->lddq < d->H * DH) return LPI_EINVAL;
-    const int esz = dtype == LPI_F32 ? 4 : 2;
-    if ((d->ldqkv * esz) % 16 || (d->ldq * esz) % 16 || (d->lddctx * esz) % 16) return LPI_EINVAL;
-    if (((uintptr_t)d->q | (uintptr_t)d->qkv | (uintptr_t)d->dctx) & 15) return LPI_EINVAL;
-    // dqkv and shared_dkv go through lpi_shared_kv_reduce after the launch (four elements per lane): its conditions are refused here, before any launch
-    if ((d->lddqkv & 3) || ((uintptr_t)d->shared_dkv & 15) || ((uintptr_t)d->dqkv & (dtype == LPI_F32 ? 15 : 7))) return LPI_EINVAL;
-    const int Lp = (d->L + 63) / 64 * 64;
-    const size_t lds = (size_t)(3 * Lp + WPB * DH) * sizeof(float);
-    if (lds > 64 * 1024) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(d->B * d->H), block(WAVE * WPB);
-    if (dtype == LPI_F32)
-        LPI_LAUNCH((attn_pooled_bwd_kernel<float>), grid, block, lds, s, d->B, d->L, d->row_start, d->H, Lp, (const float*)d->q, d->ldq, (const float*)d->qkv, d->ldqkv, d->idx,
-                   (const float*)d->dctx, d->lddctx, d->lse, (float*)d->dq, d->lddq, (float*)d->dqkv, d->lddqkv, 1, d->shared_rows, d->shared_dkv);
-    else if (dtype == LPI_BF16)
-        LPI_LAUNCH((attn_pooled_bwd_kernel<bf16_t>), grid, block, lds, s, d->B, d->L, d->row_start, d->H, Lp, (const bf16_t*)d->q, d->ldq, (const bf16_t*)d->qkv, d->ldqkv, d->idx,
-                   (const bf16_t*)d->dctx, d->lddctx, d->lse, (bf16_t*)d->dq, d->lddq, (bf16_t*)d->dqkv, d->lddqkv, 1, d->shared_rows, d->shared_dkv);
-    else if (dtype == LPI_F16)
-        LPI_LAUNCH((attn_pooled_bwd_kernel<bf16_t, f16_t>), grid, block, lds, s, d->B, d->L, d->row_start, d->H, Lp, (const f16_t*)d->q, d->ldq, (const f16_t*)d->qkv, d->ldqkv, d->idx,
-                   (const bf16_t*)d->dctx, d->lddctx, d->lse, (bf16_t*)d->dq, d->lddq, (bf16_t*)d->dqkv, d->lddqkv, 1, d->shared_rows, d->shared_dkv);
-    else
-        return LPI_ENOSYS;
-    LPI_CHECK_LAST();
-    return lpi_shared_kv_reduce(dtype, d->B, d->shared_rows, d->H, d->shared_dkv, d->dqkv, d->lddqkv, 0, stream);
 }
 
 extern "C" int lpi_attn_pooled_fwd(int dtype, int B, int L, int H, const void* q, int ldq, const void* qkv, int ld, const int* idx,

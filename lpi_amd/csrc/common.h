@@ -38,7 +38,7 @@ struct LdsOnce {
 };
 inline int lpi_ensure_lds(LdsOnce& once, const void* kern, int bytes) {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return LPI_EINVAL;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)e;      // the runtime's code (no device: 100), never a refused argument list's
     const uint64_t bit = 1ull << (dev & 63);
     if (once.devices.load(std::memory_order_acquire) & bit) return 0;
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);

@@ -1,4 +1,4 @@
-// Run-time dtype codes and row widths -> compile-time template arguments, for the host entry points and the row-job kernel.  A call site lists the
+// Run-time dtype codes, flags and row widths -> compile-time template arguments, for the host entry points and the row-job kernel.  A call site lists the
 // combinations it instantiates and writes its launch ONCE, in a generic lambda; any other code returns false and calls nothing:
 //     if (!dispatch_types(TypeList<Types<float, float>, Types<f16_t, bf16_t>>{}, [&](auto tx, auto ty) { typedef type_of<decltype(tx)> TX; ... }, x_dtype, y_dtype)) return LPI_EINVAL;
 #pragma once
@@ -20,6 +20,12 @@ template <typename... C, typename F, typename... DT> __host__ __device__ __force
 }
 // is (dt...) a listed combination?  (for the callers that check every problem before the first launch)
 template <typename L, typename... DT> inline bool types_listed(L, DT... dt) { return dispatch_types(L{}, [](auto...) {}, dt...); }
+
+// run-time flags -> compile-time ones: returns f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...); every combination is instantiated
+template <typename F> inline auto dispatch_bool(F f) { return f(); }
+template <typename F, typename... B> inline auto dispatch_bool(F f, bool b0, B... rest) {
+    return b0 ? dispatch_bool([&](auto... r) { return f(std::true_type{}, r...); }, rest...) : dispatch_bool([&](auto... r) { return f(std::false_type{}, r...); }, rest...);
+}
 
 // f(integral_constant<NC>) with the smallest listed chunk bound NC (ascending list) that covers d: ceil(d / 256) <= NC; false if none does
 template <int... NC, typename F> __host__ __device__ __forceinline__ bool dispatch_nc(int d, F f) {

@@ -702,3 +702,40 @@ def test_strides_and_pointers_the_kernels_cannot_take_are_refused_before_any_lau
             yes(1 + extra, lambda *a: _lib.attn_pooled_one(*a, backward=True), BF16, t, st)
             yes(1 + extra, lambda *a: _lib.attn_pooled_pair(*a, backward=True), BF16, pooled(), t, st)
     torch.cuda.synchronize()
+
+
+# ---- the LDS set-up of every kernel instantiation ---------------------------------------------------------------------------------------------------------------------
+def test_every_large_lds_kernel_launches_in_one_process():
+    """Every kernel of attention.hip and attention4.hip that asks for more than the default 64 KiB of LDS is launched here, in one process, at a length whose image
+    exceeds 64 KiB: the permission is set once per (kernel instantiation, device) by an LdsOnce beside each launch, and a kernel whose set-up were skipped (or
+    taken for a neighbour's) fails its launch.  Outputs per element against the f64 reference and bars of tests/attn_edges.py, launch counts as the dispatch implies
+    (the batches, bars and checks of tests/test_attn_edges_gpu.py, imported here at call time: that module imports this one).
+      forward <T, causal> (+ swizzled <2-byte, non-causal>), two-pass backward (f32; key 3 = 1), streamed backward in two windows: L = 288, each dtype, causal and not
+      fused backward <bf16 | f16-saved, causal and not>: L = 224 (causal; non-causal with key 7 = 1), where four images take 145 KiB
+      streamed backward <bf16 | f16-saved>, tuned (L = 224) and generic in two windows (L = 273)
+      ragged causal: L = 288 among shorter samples
+      pair forward <T, C0, C1>: (288 non-causal, 77 causal) on the swizzled images, (77 causal, 77 causal)."""
+    import test_attn_edges_gpu as E
+    for dt in ALL:
+        for causal in (0, 1):
+            pb = E.batch(dt, "random", "uniform", (288, 288), causal)
+            for keys in ({}, {3: 1}) if dt != F32 else ({},):
+                E.check_full(pb, keys, arm="random")
+        E.check_full(E.batch(dt, "match", "ragged", E.RAGGED["long"], 1), {}, arm="match")
+    for dt in TWO:
+        td = TD[dt]
+        E.check_full(E.batch(dt, "random", "uniform", (224, 224), 1), {}, arm="random")          # fused, causal
+        pb = E.batch(dt, "random", "uniform", (224, 224), 0)
+        E.check_full(pb, {7: 1}, arm="random")                                                     # fused, non-causal
+        E.check_full(pb, {}, arm="random")                                                         # streamed, the Lp = 224 configuration
+        E.check_full(E.batch(dt, "random", "uniform", (273, 273), 0), {}, arm="random")           # streamed, two key windows
+        vis, txt = E.batch(dt, "random", "uniform", (288, 288), 0), E.batch(dt, "random", "uniform", (77, 77), 1)
+        for first in (vis, txt):
+            a = [(pb, E.nan(pb["M"], D, td=td), E.nan(2, H, pb["Lmax"])) for pb in (first, txt)]
+            label = f"random pair {NAME[dt]} L={first['Lmax']} + 77"
+            with tuning(DEFAULT_KEYS):
+                launches(lambda: _lib.attn_fwd_pair(dt, *[(2, pb["Lmax"], None, H, pb["qkv"], 3 * D, ctx, D, lse, pb["causal"], 0) for pb, ctx, lse in a], E.stream()), 1, label)
+            torch.cuda.synchronize()
+            for pb, ctx, lse in a:
+                E.hold(label, f"attention fwd pair {NAME[dt]}", "ctx", ctx.cpu(), pb["ref"]["ctx"], pb["bar"]["ctx"], E.AE.OLD_CTX[td])
+                E.hold(label, f"attention fwd pair {NAME[dt]}", "lse", lse.cpu(), pb["ref"]["lse"], pb["bar"]["lse"], E.AE.OLD_LSE[td])
