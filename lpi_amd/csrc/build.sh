@@ -7,7 +7,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wn
 mkdir -p build
 pids=()
 for f in api gemm gemm256 gemm256p gemm256x128 gemm_rows gemm_mx8 mx8_rows mx4_rows attention attention4 attn_pooled attn_stream attn_long attn_hd attn_hd88 attn_hd104 rowops posembed act loss interact bpe host imageops jpeg search search16 search_mx8 search_mx4 search_wide search_rerank; do
-  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ dispatch.h -nt build/$f.o ] ||[ gemm_epilogue.h -nt build/$f.o ] || [ attn_softmax.h -nt build/$f.o ] || [ attn_walk.h -nt build/$f.o ] || [ attn_hd_widths.h -nt build/$f.o ] || [ unicode_ln.h -nt build/$f.o ] || [ gemm256_tile.h -nt build/$f.o ] || [ gemm256x128_tile.h -nt build/$f.o ] || [ mx8.h -nt build/$f.o ] || [ mx4.h -nt build/$f.o ] || [ search_tile.h -nt build/$f.o ] || [ ../../include/lpi_hip.h -nt build/$f.o ]; then
+  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ dispatch.h -nt build/$f.o ] || [ gemm_host.h -nt build/$f.o ] || [ gemm_epilogue.h -nt build/$f.o ] || [ attn_softmax.h -nt build/$f.o ] || [ attn_walk.h -nt build/$f.o ] || [ attn_hd_widths.h -nt build/$f.o ] || [ unicode_ln.h -nt build/$f.o ] || [ gemm256_tile.h -nt build/$f.o ] || [ gemm256x128_tile.h -nt build/$f.o ] || [ mx8.h -nt build/$f.o ] || [ mx4.h -nt build/$f.o ] || [ search_tile.h -nt build/$f.o ] || [ ../../include/lpi_hip.h -nt build/$f.o ]; then
     extra=""
     case $f in attention|attention4) extra="-fno-honor-nans";; esac      # see attn_softmax.h (attn_max3)
     $HIPCC $FLAGS $extra -c $f.hip -o build/$f.o &

@@ -17,7 +17,7 @@
 //    CONSECUTIVE columns of one output row: the epilogue (bias, QuickGELU, gelu', residual) runs on float4s and
 //    stores 16 B (f32) / 8 B (bf16) per lane;
 //  * blockIdx is remapped so that the blocks sharing one XCD's L2 walk neighbouring M tiles of the same N panel.
-#include "common.h"
+#include "gemm_host.h"
 #include "gemm_epilogue.h"
 
 namespace {
@@ -175,190 +175,134 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_kernel(
 }
 
 template <typename T, typename TC, int EPI, bool RES, bool SAVE_U>
-int launch_impl(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-           const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s)
+int launch(const GemmCall& c, Tag<T>, Tag<TC>, Int<EPI>, Bool<RES>, Bool<SAVE_U>)
 {
-    const int tm = M / BM, tn = N / BN;
+    const lpi_gemm_desc& d = c.p;
+    const int tm = d.M / BM, tn = d.N / BN;
     auto kern = gemm_nt_kernel<T, TC, EPI, RES, SAVE_U>;
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES)) return e;
     lpi_note_gemm_kernel(kIsX3<T> ? LPI_GEMM_K_X3 : LPI_GEMM_K_128);
-    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHREADS), 2 * STAGE_BYTES, s, M, N, K, (const T*)A, lda, (const T*)B, ldb,
-                       (TC*)C, ldc, bias, residual, ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn);
+    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES)) return e;
+    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHREADS), 2 * STAGE_BYTES, c.s, d.M, d.N, d.K, (const T*)d.A, d.lda, (const T*)d.B, d.ldb, (TC*)d.C, d.ldc, d.bias,
+               (const float*)d.residual, d.ldr, (typename AuxT<T>::type*)d.aux, d.ldaux, c.alpha, tm, tn);
     LPI_CHECK_LAST();
     return 0;
 }
 
-// run-time pointer presence -> compile-time epilogue flags (residual only with EPI_NONE, save-u only with QUICKGELU)
-template <typename T, typename TC, int EPI>
-int launch(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-           const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s)
-{
-    if constexpr (EPI == LPI_EPI_NONE) {
-        if (residual) return launch_impl<T, TC, EPI, true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-        return launch_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    } else {
-        if (residual) return LPI_ENOSYS;
-        if constexpr (EPI == LPI_EPI_QUICKGELU) {
-            if (aux) return launch_impl<T, TC, EPI, false, true>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-            return launch_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-        } else {
-            if (!aux) return LPI_EINVAL;
-            return launch_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-        }
-    }
-}
-
-template <typename T, typename TC>
-int dispatch_epi(int epi, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                 const float* bias, const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s)
-{
-    switch (epi) {
-    case LPI_EPI_NONE: return launch<T, TC, LPI_EPI_NONE>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    case LPI_EPI_QUICKGELU: return launch<T, TC, LPI_EPI_QUICKGELU>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    case LPI_EPI_DQUICKGELU:
-        if (!aux) return LPI_EINVAL;
-        return launch<T, TC, LPI_EPI_DQUICKGELU>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    }
-    return LPI_EINVAL;
-}
+// the (T, TC) pairs of the 128x128 kernel; bf16 -> f16 is the fp16 residual stream: x_out = x_in + (A.B^T + bias), both fp16
+typedef TypeList<Types<float, float>, Types<f32x3_t, float>, Types<bf16_t, bf16_t>, Types<bf16_t, float>, Types<bf16_t, f16_t, ResidualOnly>, Types<f16_t, f16_t>,
+                 Types<f16_t, float>> Built;
 
 }  // namespace
 
-bool lpi_gemm256_eligible(int dtype, int M, int N, int K);
-int lpi_gemm256p_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                        const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s);
-int lpi_gemm256_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                       const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s);
-bool lpi_gemm256x128_eligible(int dtype, int M, int N, int K);
-int lpi_gemm256x128_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                           const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s,
-                           int group_m);
-extern int g_lpi_tuning[16];
-
 // argument checks shared by lpi_gemm_nt and lpi_gemm_nt_grouped
-static int gemm_nt_check(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                         const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux)
+static int gemm_nt_check(const GemmCall& c, const lpi_gemm_desc& d)
 {
-
+    const int dtype = c.dtype, c_dtype = c.c_dtype, epilogue = c.epilogue;
+    const void* aux = d.aux;
     if (dtype == LPI_F32X3) {      // bf16x3: everything in memory is f32; the epilogues of the f32 mode
         if (c_dtype != LPI_F32) return LPI_ENOSYS;
         if (epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_QUICKGELU && epilogue != LPI_EPI_DQUICKGELU) return LPI_ENOSYS;
     }
-    const int esz = dtype == LPI_F32 || dtype == LPI_F32X3 ? 4 : 2;
+    const int esz = gemm_rows4(dtype) ? 4 : 2;
     const int csz = c_dtype == LPI_F32 ? 4 : 2;
     if (epilogue == LPI_EPI_RES_ROWSTATS) {      // the fp16 residual epilogue + the row statistics of its output: aux = f32 slots, N/128 x 2 x ldaux
         if (c_dtype != LPI_F16 || dtype == LPI_F32) return LPI_ENOSYS;
-        if (!residual || !aux || ldaux < M || (ldaux & 3) || ((uintptr_t)aux & 15)) return LPI_EINVAL;
+        if (!d.residual || !aux || d.ldaux < d.M || (d.ldaux & 3) || ((uintptr_t)aux & 15)) return LPI_EINVAL;
         aux = nullptr;      // the checks below are for an operand-typed [M, N] aux tile
     }
-    if (c_dtype == LPI_F16 && dtype == LPI_BF16 && ((epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_RES_ROWSTATS) || !residual)) return LPI_ENOSYS;
+    if (c_dtype == LPI_F16 && dtype == LPI_BF16 && ((epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_RES_ROWSTATS) || !d.residual)) return LPI_ENOSYS;
     if (c_dtype == LPI_F16 && dtype == LPI_F32) return LPI_ENOSYS;
-    const bool ln = epilogue == LPI_EPI_LN || epilogue == LPI_EPI_LN_QUICKGELU;
+    const bool ln = gemm_epi_ln(epilogue);
     if (c_dtype == LPI_BF16 && dtype == LPI_F16 && !ln) return LPI_ENOSYS;      // f16 operands write f16 or f32 (bf16: the LN-fold GEMMs of bf16 mode)
     if (ln) {      // LayerNorm folded into the GEMM: residual = mean[ldr] | rstd[ldr] | c1[N] (f32)
         if (dtype == LPI_F32 || c_dtype == LPI_F32) return LPI_ENOSYS;
-        if (!residual || !bias || ldr < M || (ldr & 3) || ((uintptr_t)residual & 15)) return LPI_EINVAL;
+        if (!d.residual || !d.bias || d.ldr < d.M || (d.ldr & 3) || ((uintptr_t)d.residual & 15)) return LPI_EINVAL;
         if (epilogue == LPI_EPI_LN && aux) return LPI_EINVAL;
     }
     const int bk = ROW_BYTES / esz;
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return LPI_EINVAL;
-    if (M % BM || N % BN || K % bk) return LPI_EINVAL;
+    if (!d.A || !d.B || !d.C || d.M <= 0 || d.N <= 0 || d.K <= 0) return LPI_EINVAL;
+    if (d.M % BM || d.N % BN || d.K % bk) return LPI_EINVAL;
     // Every row of every operand starts on a 16-byte boundary (include/lpi_hip.h).  Which kernel runs is the dispatcher's choice (tuning keys, CU count), and
     // the widest access any of them makes decides: most epilogues move four elements per lane (8 bytes of a 2-byte C / residual / aux), but the persistent
     // kernel stores whole 16-byte pieces of a 2-byte C row (half-width staging) and brings the 2-byte residual / gelu' tiles to LDS 16 bytes per lane, and an
     // f32 C / residual / aux moves as f32x4 everywhere ("Leading dimensions of the GEMM family").
     const int rsz = c_dtype == LPI_F16 ? 2 : 4;      // the residual tile has C's type on the fp16 stream, f32 otherwise
-    if ((lda * esz) % 16 || (ldb * esz) % 16 || (ldc * csz) % 16 || lda < K || ldb < K || ldc < N) return LPI_EINVAL;
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return LPI_EINVAL;
-    if (residual && !ln && (ldr < N || (ldr * rsz) % 16 || ((uintptr_t)residual & 15))) return LPI_EINVAL;
-    if (bias && ((uintptr_t)bias & 15)) return LPI_EINVAL;
-    if (aux && (ldaux < N || ((uintptr_t)aux & 15) || (ldaux * esz) % 16)) return LPI_EINVAL;
+    if ((d.lda * esz) % 16 || (d.ldb * esz) % 16 || (d.ldc * csz) % 16 || d.lda < d.K || d.ldb < d.K || d.ldc < d.N) return LPI_EINVAL;
+    if (((uintptr_t)d.A | (uintptr_t)d.B | (uintptr_t)d.C) & 15) return LPI_EINVAL;
+    if (d.residual && !ln && (d.ldr < d.N || (d.ldr * rsz) % 16 || ((uintptr_t)d.residual & 15))) return LPI_EINVAL;
+    if (d.bias && ((uintptr_t)d.bias & 15)) return LPI_EINVAL;
+    if (aux && (d.ldaux < d.N || ((uintptr_t)aux & 15) || (d.ldaux * esz) % 16)) return LPI_EINVAL;
     if (epilogue == LPI_EPI_DQUICKGELU && !aux) return LPI_EINVAL;
     return 0;
 }
 
-extern "C" int lpi_gemm_nt(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                           void* C, int ldc, const float* bias, const void* residual_, int ldr, int epilogue, void* aux,
-                           int ldaux, float alpha, void* stream)
+// one checked problem -> the kernel for its shape
+static int gemm_nt_one(const GemmCall& c)
 {
-    const float* residual = (const float*)residual_;      // fp16 when c_dtype == LPI_F16 (re-typed in the epilogue)
-    if (int e = gemm_nt_check(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux)) return e;
-    if ((epilogue == LPI_EPI_LN || epilogue == LPI_EPI_LN_QUICKGELU) && alpha != 1.0f) return LPI_EINVAL;      // LN(x) W^T + b has no scale (the epilogue does not multiply by one)
-    hipStream_t s = (hipStream_t)stream;
-    if (epilogue == LPI_EPI_LN || epilogue == LPI_EPI_LN_QUICKGELU || epilogue == LPI_EPI_RES_ROWSTATS) {
-        // only the persistent 256x256 kernel has the LN-fold and the row-statistics epilogues
-        if (!lpi_gemm256_eligible(dtype, M, N, K)) return LPI_ENOSYS;
-        return lpi_gemm256p_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s);
-    }
+    const lpi_gemm_desc& d = c.p;
+    if (int e = gemm_nt_check(c, d)) return e;
+    if (gemm_epi_ln(c.epilogue) && c.alpha != 1.0f) return LPI_EINVAL;      // LN(x) W^T + b has no scale (the epilogue does not multiply by one)
+    const bool big = lpi_gemm256_eligible(c.dtype, d);
+    if (gemm_epi_ln(c.epilogue) || c.epilogue == LPI_EPI_RES_ROWSTATS)      // only the persistent 256x256 kernel has the LN-fold and the row-statistics epilogues
+        return big ? lpi_gemm256p_launch(c) : LPI_ENOSYS;
     // Half-empty launches: fewer than tuning key 5 (default 160) 256x256 tiles -> 256x128 tiles, twice the workgroups (bf16 only:
     // the f32 path is MFMA-bound at any tile size).  Key 5 = 0 disables it.
-    const bool f32_rows = dtype == LPI_F32 || dtype == LPI_F32X3;      // 4-byte elements in memory
-    if (!f32_rows && g_lpi_tuning[5] > 0 && lpi_gemm256_eligible(dtype, M, N, K) && (M / 256) * (N / 256) < g_lpi_tuning[5] &&
-        (M / 256) * (N / 256) >= 16 && lpi_gemm256x128_eligible(dtype, M, N, K)) {
-        const int rc = lpi_gemm256x128_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s,
-                                              g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8);
+    const bool f32_rows = gemm_rows4(c.dtype);
+    const int tiles256 = (d.M / 256) * (d.N / 256);
+    if (!f32_rows && g_lpi_tuning[5] > 0 && big && tiles256 < g_lpi_tuning[5] && tiles256 >= 16 && lpi_gemm256x128_eligible(c.dtype, d)) {
+        const int rc = lpi_gemm256x128_launch(c);
         if (rc != LPI_ENOSYS) return rc;
     }
     // 256x256 8-phase kernel when the shape gives it enough tiles to fill the chip (tuning keys 0 / 1 = minimum tile count for bf16 / f32)
-    if (lpi_gemm256_eligible(dtype, M, N, K) && (M / 256) * (N / 256) >= g_lpi_tuning[f32_rows ? 1 : 0])
-        return lpi_gemm256_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s);
-    if (dtype == LPI_F32 && c_dtype == LPI_F32)
-        return dispatch_epi<float, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_F32X3 && c_dtype == LPI_F32)
-        return dispatch_epi<f32x3_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_BF16)
-        return dispatch_epi<bf16_t, bf16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F32)
-        return dispatch_epi<bf16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F16)      // fp16 residual stream: x_out = x_in + (A.B^T + bias), both fp16
-        return launch_impl<bf16_t, f16_t, LPI_EPI_NONE, true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F16)
-        return dispatch_epi<f16_t, f16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F32)
-        return dispatch_epi<f16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    return LPI_ENOSYS;
+    if (big && tiles256 >= g_lpi_tuning[f32_rows ? 1 : 0]) return lpi_gemm256_launch(c);
+    return gemm_pick(Built{}, c.dtype, c.c_dtype, c.epilogue, d.residual != nullptr, d.aux != nullptr, [&](auto... k) { return launch(c, k...); });
+}
+
+// residual: fp16 when c_dtype == LPI_F16 (re-typed in the epilogue)
+extern "C" int lpi_gemm_nt(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                           void* C, int ldc, const float* bias, const void* residual, int ldr, int epilogue, void* aux,
+                           int ldaux, float alpha, void* stream)
+{
+    return gemm_nt_one(GemmCall{.dtype = dtype, .c_dtype = c_dtype, .epilogue = epilogue, .alpha = alpha, .s = (hipStream_t)stream,
+                                .p = {.M = M, .N = N, .K = K, .A = A, .lda = lda, .B = B, .ldb = ldb, .C = C, .ldc = ldc, .bias = bias, .residual = residual,
+                                      .ldr = ldr, .aux = aux, .ldaux = ldaux}});
 }
 
 // 1 if lpi_gemm_nt takes LPI_EPI_LN / LPI_EPI_LN_QUICKGELU for this operand type and shape (the persistent 256x256 kernel's shapes), else 0
 extern "C" int lpi_gemm_ln_supported(int dtype, int M, int N, int K)
 {
-    return (dtype == LPI_F16 || dtype == LPI_BF16) && M > 0 && N > 0 && K > 0 && lpi_gemm256_eligible(dtype, M, N, K) ? 1 : 0;
+    return (dtype == LPI_F16 || dtype == LPI_BF16) && M > 0 && N > 0 && K > 0 && lpi_gemm256_eligible(dtype, lpi_gemm_desc{.M = M, .N = N, .K = K}) ? 1 : 0;
 }
 
-int lpi_gemm256p_launch2(int dtype, int c_dtype, int epilogue, float alpha, const lpi_gemm_desc* d, hipStream_t s);
 static thread_local int t_last_grouped = 0;
 extern "C" int lpi_gemm_last_grouped(void) { return t_last_grouped; }
 
 extern "C" int lpi_gemm_nt_grouped(int dtype, int c_dtype, int epilogue, float alpha, int count, const lpi_gemm_desc* d, void* stream)
 {
-    if ((epilogue == LPI_EPI_LN || epilogue == LPI_EPI_LN_QUICKGELU) && alpha != 1.0f) return LPI_EINVAL;
+    GemmCall c{.dtype = dtype, .c_dtype = c_dtype, .epilogue = epilogue, .alpha = alpha, .s = (hipStream_t)stream};
+    if (gemm_epi_ln(epilogue) && alpha != 1.0f) return LPI_EINVAL;
     if (count <= 0 || !d) return LPI_EINVAL;
     t_last_grouped = 0;
     for (int i = 0; i < count; ++i)
-        if (int e = gemm_nt_check(dtype, c_dtype, d[i].M, d[i].N, d[i].K, d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, d[i].bias,
-                                  (const float*)d[i].residual, d[i].ldr, epilogue, d[i].aux, d[i].ldaux)) return e;
-    // one persistent launch: two bf16 / f16 problems that the 256x256 kernel takes, with an epilogue the persistent kernel has (store-only,
-    // or a 2-byte side tile), together at least a round of tiles (tuning key 8 != 0 = never group: A/B switch)
-    bool group = count == 2 && dtype != LPI_F32 && dtype != LPI_F32X3 && g_lpi_tuning[2] >= 0 && g_lpi_tuning[8] == 0;
-    if (group) {
-        int tiles = 0;
-        for (int i = 0; i < 2 && group; ++i) {
-            const bool res = d[i].residual != nullptr && epilogue != LPI_EPI_LN && epilogue != LPI_EPI_LN_QUICKGELU;      // LN block: not a tile
-            const bool side16 = (res && c_dtype == LPI_F16) || epilogue == LPI_EPI_DQUICKGELU;      // LPI_EPI_RES_ROWSTATS: res and fp16 by its checks
-            const bool loads = res || epilogue == LPI_EPI_DQUICKGELU;
-            group = lpi_gemm256_eligible(dtype, d[i].M, d[i].N, d[i].K) && (!loads || (side16 && g_lpi_tuning[2] != 2));
-            tiles += (d[i].M / 256) * (d[i].N / 256);
-        }
-        group = group && tiles >= 256 && (d[0].residual != nullptr) == (d[1].residual != nullptr) && (d[0].aux != nullptr) == (d[1].aux != nullptr);
+        if (int e = gemm_nt_check(c, d[i])) return e;
+    // one persistent launch: two problems that the 256x256 kernel takes, with operands and an epilogue the persistent kernel has, together at
+    // least a round of tiles, agreeing on residual and aux (tuning key 8 != 0 = never group: A/B switch)
+    bool group = count == 2 && g_lpi_tuning[8] == 0;
+    int tiles = 0;
+    for (int i = 0; i < 2 && group; ++i) {
+        group = gemm256p_takes(c, d[i]) && lpi_gemm256_eligible(dtype, d[i]);
+        tiles += (d[i].M / 256) * (d[i].N / 256);
     }
+    group = group && tiles >= 256 && (d[0].residual != nullptr) == (d[1].residual != nullptr) && (d[0].aux != nullptr) == (d[1].aux != nullptr);
     if (group) {
-        const int rc = lpi_gemm256p_launch2(dtype, c_dtype, epilogue, alpha, d, (hipStream_t)stream);
+        const int rc = lpi_gemm256p_launch2(c, d);
         if (rc == 0) t_last_grouped = 1;
         if (rc != LPI_ENOSYS) return rc;
     }
-    for (int i = 0; i < count; ++i)
-        if (int e = lpi_gemm_nt(dtype, c_dtype, d[i].M, d[i].N, d[i].K, d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, d[i].bias, d[i].residual,
-                                d[i].ldr, epilogue, d[i].aux, d[i].ldaux, alpha, stream)) return e;
+    for (int i = 0; i < count; ++i) {
+        c.p = d[i];
+        if (int e = gemm_nt_one(c)) return e;
+    }
     return 0;
 }

@@ -21,8 +21,7 @@
 // 2.9 % slower over the eight vision-layer GEMMs, 11 % on the qkv shape)
 #include "gemm256_tile.h"
 #include "gemm256x128_tile.h"
-
-extern int g_lpi_tuning[16];
+#include "gemm_host.h"
 
 namespace {
 
@@ -122,100 +121,67 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tail_kernel(
 }
 
 template <typename T, typename TC, int EPI, bool RES, bool SAVE_U>
-int launch256_impl(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-              const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s)
+int launch256(const GemmCall& c, Tag<T>, Tag<TC>, Int<EPI>, Bool<RES>, Bool<SAVE_U>)
 {
-    const int tm = M / T256, tn = N / T256;
+    const lpi_gemm_desc& d = c.p;
+    const int tm = d.M / T256, tn = d.N / T256;
     const int nwg = tm * tn, rem = nwg % 256, n_full = nwg - rem;
-    const int gm = g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8;
     // a short last round (<= 128 of 256 CUs busy) runs as 256x128 half tiles inside the same launch (tuning key 6, default on;
     // bf16 operands only: the f32 path is MFMA-bound and its K-tile count per 128-byte row differs)
     if constexpr (!kIsX3<T>)      // (no 256x128 tile for bf16x3: its rows are f32)
-    if (sizeof(T) == 2 && g_lpi_tuning[6] != 0 && n_full >= 256 && rem > 0 && rem <= 128 && K / (ROWB / (int)sizeof(T)) >= 2) {
+    if (sizeof(T) == 2 && g_lpi_tuning[6] != 0 && n_full >= 256 && rem > 0 && rem <= 128 && d.K / (ROWB / (int)sizeof(T)) >= 2) {
         auto tk = gemm256_tail_kernel<T, TC, EPI, RES, SAVE_U>;
         constexpr int LDS_TAIL = t128::LDS_BYTES > LDS_BYTES ? t128::LDS_BYTES : LDS_BYTES;
         static LdsOnce tail_once;
-        if (int e = lpi_ensure_lds(tail_once, (const void*)tk, LDS_TAIL)) return e;
         lpi_note_gemm_kernel(LPI_GEMM_K_256_TAIL);
+        if (int e = lpi_ensure_lds(tail_once, (const void*)tk, LDS_TAIL)) return e;
         const int q = nwg >> 3, r = nwg & 7;
         const int max_left = q + (r ? 1 : 0) - (n_full >> 3);      // leftover tiles of the fullest XCD
-        LPI_LAUNCH(tk, dim3(n_full + 16 * max_left), dim3(NTHR), LDS_TAIL, s, M, N, K, (const T*)A, lda, (const T*)B, ldb, (TC*)C, ldc, bias, residual,
-                   ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn, n_full, gm);
+        LPI_LAUNCH(tk, dim3(n_full + 16 * max_left), dim3(NTHR), LDS_TAIL, c.s, d.M, d.N, d.K, (const T*)d.A, d.lda, (const T*)d.B, d.ldb, (TC*)d.C, d.ldc, d.bias,
+                   (const float*)d.residual, d.ldr, (typename AuxT<T>::type*)d.aux, d.ldaux, c.alpha, tm, tn, n_full, gemm_group_m());
         LPI_CHECK_LAST();
         return 0;
     }
     auto kern = gemm256_kernel<T, TC, EPI, RES, SAVE_U>;
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES)) return e;
     lpi_note_gemm_kernel(kIsX3<T> ? LPI_GEMM_K_X3 : LPI_GEMM_K_256);
-    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES, s, M, N, K, (const T*)A, lda, (const T*)B, ldb, (TC*)C, ldc, bias, residual,
-               ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn, 0, g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8);
+    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES)) return e;
+    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES, c.s, d.M, d.N, d.K, (const T*)d.A, d.lda, (const T*)d.B, d.ldb, (TC*)d.C, d.ldc, d.bias,
+               (const float*)d.residual, d.ldr, (typename AuxT<T>::type*)d.aux, d.ldaux, c.alpha, tm, tn, 0, gemm_group_m());
     LPI_CHECK_LAST();
     return 0;
 }
 
 template <typename TC, int EPI, bool RES>
-int launch256_mx8(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias, const void* residual, int ldr,
-                  float alpha, const Mx8Side& mx, hipStream_t s)
+int launch256_mx8(const GemmCall& c, const Mx8Side& mx, Tag<TC>, Int<EPI>, Bool<RES>)
 {
-    const int tm = M / T256, tn = N / T256;
+    const lpi_gemm_desc& d = c.p;
+    const int tm = d.M / T256, tn = d.N / T256;
     auto kern = gemm256_mx8_kernel<TC, EPI, RES>;
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES_MX8)) return e;
     lpi_note_gemm_kernel(LPI_GEMM_K_MX8_256);
-    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES_MX8, s, K, (const mx8_t*)A, lda, (const mx8_t*)B, ldb, (TC*)C, ldc, bias, (const float*)residual, ldr,
-               alpha, tm, tn, g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : 8, mx);
+    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES_MX8)) return e;
+    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES_MX8, c.s, d.K, (const mx8_t*)d.A, d.lda, (const mx8_t*)d.B, d.ldb, (TC*)d.C, d.ldc, d.bias,
+               (const float*)d.residual, d.ldr, c.alpha, tm, tn, gemm_group_m(), mx);
     LPI_CHECK_LAST();
     return 0;
 }
 
-// run-time pointer presence -> compile-time epilogue flags (residual only with EPI_NONE, save-u only with QUICKGELU)
-template <typename T, typename TC, int EPI>
-int launch256(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-           const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s)
-{
-    if constexpr (EPI == LPI_EPI_NONE) {
-        if (residual) return launch256_impl<T, TC, EPI, true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-        return launch256_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    } else {
-        if (residual) return LPI_ENOSYS;
-        if constexpr (EPI == LPI_EPI_QUICKGELU) {
-            if (aux) return launch256_impl<T, TC, EPI, false, true>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-            return launch256_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-        } else {
-            if (!aux) return LPI_EINVAL;
-            return launch256_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-        }
-    }
-}
-
-template <typename T, typename TC>
-int dispatch256(int epi, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-                const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s)
-{
-    switch (epi) {
-    case LPI_EPI_NONE: return launch256<T, TC, LPI_EPI_NONE>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    case LPI_EPI_QUICKGELU: return launch256<T, TC, LPI_EPI_QUICKGELU>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    case LPI_EPI_DQUICKGELU: return launch256<T, TC, LPI_EPI_DQUICKGELU>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    }
-    return LPI_EINVAL;
-}
+// the (T, TC) pairs of the one-tile-per-workgroup 256x256 kernels
+typedef TypeList<Types<float, float>, Types<f32x3_t, float>, Types<bf16_t, bf16_t>, Types<bf16_t, float>, Types<bf16_t, f16_t, ResidualOnly>, Types<f16_t, f16_t>,
+                 Types<f16_t, float>> Built;
 
 }  // namespace
 
 // true if the 256x256 kernel can take this shape
-bool lpi_gemm256_eligible(int dtype, int M, int N, int K) {
-    const int bk = ROWB / (dtype == LPI_F32 || dtype == LPI_F32X3 ? 4 : 2);
-    if (M % T256 || N % T256 || K % bk) return false;
-    const int nk = K / bk;
+bool lpi_gemm256_eligible(int dtype, const lpi_gemm_desc& d) {
+    const int bk = ROWB / (gemm_rows4(dtype) ? 4 : 2);
+    if (d.M % T256 || d.N % T256 || d.K % bk) return false;
+    const int nk = d.K / bk;
     return nk >= 2 && (nk % 2) == 0;
 }
 
-int lpi_gemm256p_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                        const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s);
-
-int lpi_gemm256_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                       const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s)
+int lpi_gemm256_launch(const GemmCall& c)
 {
     // bf16 operands: the persistent kernel (gemm256p.hip: the K-tile ring runs across a workgroup's tiles, the next tile's first K-tile
     // lands under the epilogue); tuning key 2 = -1 keeps one tile per workgroup (A/B switch; same results bit for bit)
@@ -223,28 +189,11 @@ int lpi_gemm256_launch(int dtype, int c_dtype, int M, int N, int K, const void* 
     // Epilogues that LOAD a 2-byte tile (the fp16 residual stream, the bf16 u of gelu'(u)): that tile comes to LDS by LDS-DMA two
     // passes ahead, so the epilogue issues no vector-memory load (with plain loads they queued behind the in-flight DMA in the in-order
     // vmcnt queue and the persistent kernel LOST 8-30 % on them).  f32 residuals (few-row GEMMs only) stay on the one-tile kernels.
-    // Tuning key 2: -1 one tile per workgroup everywhere; 2 persistent for store-only epilogues only (A/B).
-    const bool loads_in_epilogue = residual != nullptr || epilogue == LPI_EPI_DQUICKGELU;
-    const bool side16 = (residual != nullptr && c_dtype == LPI_F16) || epilogue == LPI_EPI_DQUICKGELU;
-    if (dtype != LPI_F32 && dtype != LPI_F32X3 && g_lpi_tuning[2] >= 0 && (!loads_in_epilogue || (side16 && g_lpi_tuning[2] != 2))) {
-        const int rc = lpi_gemm256p_launch(dtype, c_dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, aux, ldaux, alpha, s);
+    if (gemm256p_takes(c, c.p)) {
+        const int rc = lpi_gemm256p_launch(c);
         if (rc != LPI_ENOSYS) return rc;
     }
-    if (dtype == LPI_F32 && c_dtype == LPI_F32)
-        return dispatch256<float, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_F32X3 && c_dtype == LPI_F32)
-        return dispatch256<f32x3_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_BF16)
-        return dispatch256<bf16_t, bf16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F32)
-        return dispatch256<bf16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F16 && epilogue == LPI_EPI_NONE && residual)
-        return launch256_impl<bf16_t, f16_t, LPI_EPI_NONE, true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F16)
-        return dispatch256<f16_t, f16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F32)
-        return dispatch256<f16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s);
-    return LPI_ENOSYS;
+    return gemm_pick(Built{}, c.dtype, c.c_dtype, c.epilogue, c.p.residual != nullptr, c.p.aux != nullptr, [&](auto... k) { return launch256(c, k...); });
 }
 
 // ---- MX-FP8 operands on the 256x256 tile (include/lpi_hip.h) ----
@@ -260,28 +209,9 @@ extern "C" int lpi_gemm_nt_mx8_256(int c_dtype, int M, int N, int K, const void*
                                    int ldr, int epilogue, float alpha, void* stream)
 {
     if (!lpi_gemm_mx8_256_ok(M, N, K)) return LPI_EINVAL;
-    if (int e = mx8_gemm_check_args(c_dtype, N, K, A, lda, a_scales, ldas, B, ldb, b_scales, ldbs, C, ldc, c_scales, ldcs, bias, residual, ldr, epilogue))
-        return e;
+    const GemmCall c{.dtype = LPI_MX8, .c_dtype = c_dtype, .epilogue = epilogue, .alpha = alpha, .s = (hipStream_t)stream,
+                     .p = {.M = M, .N = N, .K = K, .A = A, .lda = lda, .B = B, .ldb = ldb, .C = C, .ldc = ldc, .bias = bias, .residual = residual, .ldr = ldr}};
     const Mx8Side mx = {(const uint8_t*)a_scales, ldas, (const uint8_t*)b_scales, ldbs, (uint8_t*)c_scales, ldcs};
-    hipStream_t s = (hipStream_t)stream;
-#define MXG(TC, EPI, RES) return launch256_mx8<TC, EPI, RES>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, alpha, mx, s)
-    const bool gelu = epilogue == LPI_EPI_QUICKGELU;
-    switch (c_dtype) {
-    case LPI_F32:
-        if (gelu) MXG(float, LPI_EPI_QUICKGELU, false);
-        if (residual) MXG(float, LPI_EPI_NONE, true);
-        MXG(float, LPI_EPI_NONE, false);
-    case LPI_BF16:
-        if (gelu) MXG(bf16_t, LPI_EPI_QUICKGELU, false);
-        MXG(bf16_t, LPI_EPI_NONE, false);
-    case LPI_F16:
-        if (gelu) MXG(f16_t, LPI_EPI_QUICKGELU, false);
-        if (residual) MXG(f16_t, LPI_EPI_NONE, true);
-        MXG(f16_t, LPI_EPI_NONE, false);
-    case LPI_MX8:
-        if (gelu) MXG(mx8_out_t, LPI_EPI_QUICKGELU, false);
-        MXG(mx8_out_t, LPI_EPI_NONE, false);
-    }
-#undef MXG
-    return LPI_EINVAL;
+    if (int e = mx8_gemm_check_args(c, mx)) return e;
+    return mx8_pick<mx8_out_t>(c, [&](auto... k) { return launch256_mx8(c, mx, k...); });
 }

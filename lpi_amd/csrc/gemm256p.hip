@@ -18,8 +18,7 @@
 // LDS: 128 KiB (two ring slots), the epilogue staging is the odd slot; the hybrid short last round (256x128 half tiles, tile body
 // of gemm256x128_tile.h) runs after a workgroup's full tiles with its own ring.
 #include "gemm256x128_tile.h"
-
-extern int g_lpi_tuning[16];
+#include "gemm_host.h"
 
 namespace {
 
@@ -604,24 +603,19 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256p_kernel(const PGroup grp)
 int cu_count_p() { return lpi_cu_count(); }
 
 // ---- host side: one launch for a group of 1 or 2 problems (same T / TC / epilogue kind)
-struct HostProb {
-    int M, N, K;
-    const void* A; int lda; const void* B; int ldb; void* C; int ldc; const float* bias; const float* residual; int ldr; void* aux; int ldaux;
-};
-
 template <typename T, typename TC, int EPI, bool RES, bool SAVE_U>
-int launchp_impl(const HostProb* hp, int np, float alpha, hipStream_t s)
+int launchp(const GemmCall& c, const lpi_gemm_desc* d, int np, Tag<T>, Tag<TC>, Int<EPI>, Bool<RES>, Bool<SAVE_U>)
 {
     constexpr bool SIDE16 = (RES && sizeof(TC) == 2) || EPI == LPI_EPI_DQUICKGELU;
     static_assert(EPI != EPI_PLAIN16 || (!RES && !SAVE_U && sizeof(TC) == 2), "EPI_PLAIN16: store-only, 2-byte output");
     const int ncu = cu_count_p();
     PGroup g = {};
     g.nprob = np;
-    g.alpha = alpha;
+    g.alpha = c.alpha;
     int v = 0, nsum = 0;
     for (int i = 0; i < np; ++i) {
         PProb& P = g.p[i];
-        const HostProb& h = hp[i];
+        const lpi_gemm_desc& h = d[i];
         P.A = h.A; P.B = h.B; P.C = h.C; P.bias = h.bias; P.residual = h.residual; P.aux = h.aux;
         P.N = h.N; P.K = h.K; P.lda = h.lda; P.ldb = h.ldb; P.ldc = h.ldc; P.ldr = h.ldr; P.ldaux = h.ldaux;
         P.tiles_m = h.M / T256; P.tiles_n = h.N / T256;
@@ -637,7 +631,7 @@ int launchp_impl(const HostProb* hp, int np, float alpha, hipStream_t s)
         // XCD's 4 MB L2 once and only the weight panels have to stay resident from round to round — right while the WHOLE weight matrix fits
         // (ViT-B/16: 1.2-4.7 MB; whole step 24.16 -> 24.05 ms against 8).  Larger weights (ViT-L/14: 6-8 MB) would be re-read every round:
         // there 8 row panels at a time, rows fastest, is better (99.7 against 100.7 ms per step).  Tuning key 4 > 0 overrides.
-        P.group_m = g_lpi_tuning[4] > 0 ? g_lpi_tuning[4] : ((size_t)h.N * h.K * sizeof(T) <= ((size_t)5 << 20) ? 1 : 8);
+        P.group_m = gemm_group_m((size_t)h.N * h.K * sizeof(T) <= ((size_t)5 << 20) ? 1 : 8);
         // Round 5 — weight SLICES.  With columns fastest every round of an XCD (32 tiles = 2.7 row panels x all N-tiles) touches the WHOLE weight matrix,
         // and a 3.5-4.7 MB matrix does not survive a round in a 4 MB L2 next to the A panels and the C stream: rocprofv3 FETCH_SIZE showed the wide-N
         // GEMMs fetching 3.8x (in_proj) / 5.5x (c_fc) / 1.9x (d c_proj) their algorithmic bytes = the weights re-read by 8 XCDs x 7-10 rounds
@@ -672,85 +666,53 @@ int launchp_impl(const HostProb* hp, int np, float alpha, hipStream_t s)
     auto kern = gemm256p_kernel<T, TC, EPI, RES, SAVE_U>;
     const int LDS = std::max<int>(t128::LDS_BYTES, LDS_P + (SIDE16 ? nsum * 4 : 0));
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, 160 * 1024)) return e;
     lpi_note_gemm_kernel(g.tail_blocks ? LPI_GEMM_K_256_TAIL : LPI_GEMM_K_256);
+    if (int e = lpi_ensure_lds(once, (const void*)kern, 160 * 1024)) return e;
     const int grid = std::min(ncu, std::max(g.n_full, g.tail_blocks));
-    LPI_LAUNCH(kern, dim3(grid), dim3(NTHR), LDS, s, g);
+    LPI_LAUNCH(kern, dim3(grid), dim3(NTHR), LDS, c.s, g);
     LPI_CHECK_LAST();
     return 0;
 }
 
-// run-time pointer presence -> compile-time epilogue flags; every problem of a group must agree on them
-template <typename T, typename TC>
-int dispatchp(int epi, const HostProb* hp, int np, float alpha, hipStream_t s)
+// the (T, TC) pairs of the common epilogues, and of the LayerNorm fold (A = the fp16 residual stream, bf16 mode keeps it fp16 too; B = gamma o W; C in the
+// mode's storage type)
+typedef TypeList<Types<bf16_t, bf16_t>, Types<bf16_t, float>, Types<bf16_t, f16_t, ResidualOnly>, Types<f16_t, f16_t>, Types<f16_t, float>> Built;
+typedef TypeList<Types<f16_t, bf16_t>, Types<f16_t, f16_t>, Types<bf16_t, bf16_t>> BuiltLn;
+
+// The common epilogues go through the family's pick; this kernel's own are the half-width store of a plain 2-byte output (EPI_PLAIN16), the fp16 residual
+// epilogue with row statistics (LPI_EPI_RES_ROWSTATS = <LPI_EPI_NONE, RES, SAVE_U>, an fp16 C only) and the LayerNorm fold, whose `residual` is the LN
+// operand block, never a residual tile.  Every problem of a group agrees on residual and aux: they run one instantiation.
+int launch_group(const GemmCall& c, const lpi_gemm_desc* d, int np)
 {
-    const bool res = hp[0].residual != nullptr, ax = hp[0].aux != nullptr;
+    const bool res = d[0].residual != nullptr, ax = d[0].aux != nullptr;
     for (int i = 1; i < np; ++i)
-        if ((hp[i].residual != nullptr) != res || (hp[i].aux != nullptr) != ax) return LPI_EINVAL;
-    switch (epi) {
-    case LPI_EPI_NONE:
-        if (res) return launchp_impl<T, TC, LPI_EPI_NONE, true, false>(hp, np, alpha, s);
-        if constexpr (sizeof(TC) == 2) {      // nothing to add per column or row: the half-width staging (EPI_PLAIN16; tuning key 14 = 1: the generic epilogue, A/B)
-            bool plain = alpha == 1.0f && !ax && g_lpi_tuning[14] != 1;      // key 14 = 1 (a TEST hook): the generic epilogue, the bit-for-bit reference of tests/test_round4_gpu.py
-            for (int i = 0; i < np; ++i) plain = plain && hp[i].bias == nullptr;
-            if (plain) return launchp_impl<T, TC, EPI_PLAIN16, false, false>(hp, np, alpha, s);
+        if ((d[i].residual != nullptr) != res || (d[i].aux != nullptr) != ax) return LPI_EINVAL;
+    auto go = [&](auto... k) { return launchp(c, d, np, k...); };
+    int rc = LPI_ENOSYS;
+    if (gemm_epi_ln(c.epilogue)) {
+        dispatch_types(BuiltLn{}, [&](auto t, auto tc) {
+            if (!res || (c.epilogue == LPI_EPI_LN && ax)) rc = LPI_EINVAL;
+            else if (c.epilogue == LPI_EPI_LN) rc = go(t, tc, Int<LPI_EPI_LN>{}, Bool<false>{}, Bool<false>{});
+            else rc = ax ? go(t, tc, Int<LPI_EPI_LN_QUICKGELU>{}, Bool<false>{}, Bool<true>{}) : go(t, tc, Int<LPI_EPI_LN_QUICKGELU>{}, Bool<false>{}, Bool<false>{});
+        }, c.dtype, c.c_dtype);
+        return rc;
+    }
+    if (c.epilogue == LPI_EPI_RES_ROWSTATS) {
+        dispatch_types(TypeList<Types<bf16_t, f16_t>, Types<f16_t, f16_t>>{}, [&](auto t, auto tc) {
+            rc = res && ax ? go(t, tc, Int<LPI_EPI_NONE>{}, Bool<true>{}, Bool<true>{}) : LPI_EINVAL;
+        }, c.dtype, c.c_dtype);
+        return rc;
+    }
+    return gemm_pick(Built{}, c.dtype, c.c_dtype, c.epilogue, res, ax, [&](auto t, auto tc, auto epi, auto r, auto su) {
+        if constexpr (decltype(epi)::value == LPI_EPI_NONE && !decltype(r)::value && sizeof(type_of<decltype(tc)>) == 2) {
+            // nothing to add per column or row: the half-width staging.  Tuning key 14 = 1 (a TEST hook): the generic epilogue, the bit-for-bit reference of
+            // tests/test_round4_gpu.py
+            bool plain = c.alpha == 1.0f && !ax && g_lpi_tuning[14] != 1;
+            for (int i = 0; i < np; ++i) plain = plain && d[i].bias == nullptr;
+            if (plain) return go(t, tc, Int<EPI_PLAIN16>{}, Bool<false>{}, Bool<false>{});
         }
-        return launchp_impl<T, TC, LPI_EPI_NONE, false, false>(hp, np, alpha, s);
-    case LPI_EPI_RES_ROWSTATS:
-        if constexpr (sizeof(TC) == 2 && !__is_same(TC, bf16_t)) {
-            if (!res || !ax) return LPI_EINVAL;
-            return launchp_impl<T, TC, LPI_EPI_NONE, true, true>(hp, np, alpha, s);
-        }
-        return LPI_ENOSYS;
-    case LPI_EPI_QUICKGELU:
-        if (res) return LPI_ENOSYS;
-        if (ax) return launchp_impl<T, TC, LPI_EPI_QUICKGELU, false, true>(hp, np, alpha, s);
-        return launchp_impl<T, TC, LPI_EPI_QUICKGELU, false, false>(hp, np, alpha, s);
-    case LPI_EPI_DQUICKGELU:
-        if (res) return LPI_ENOSYS;
-        if (!ax) return LPI_EINVAL;
-        return launchp_impl<T, TC, LPI_EPI_DQUICKGELU, false, false>(hp, np, alpha, s);
-    }
-    return LPI_EINVAL;
-}
-
-// LayerNorm-fold epilogues (LPI_EPI_LN / LPI_EPI_LN_QUICKGELU): `residual` is the LN operand block, never a residual tile
-template <typename T, typename TC>
-int dispatchp_ln(int epi, const HostProb* hp, int np, float alpha, hipStream_t s)
-{
-    const bool ax = hp[0].aux != nullptr;
-    for (int i = 0; i < np; ++i)
-        if (!hp[i].residual || (hp[i].aux != nullptr) != ax) return LPI_EINVAL;
-    if (epi == LPI_EPI_LN) {
-        if (ax) return LPI_EINVAL;
-        return launchp_impl<T, TC, LPI_EPI_LN, false, false>(hp, np, alpha, s);
-    }
-    if (ax) return launchp_impl<T, TC, LPI_EPI_LN_QUICKGELU, false, true>(hp, np, alpha, s);
-    return launchp_impl<T, TC, LPI_EPI_LN_QUICKGELU, false, false>(hp, np, alpha, s);
-}
-
-int launch_group(int dtype, int c_dtype, int epilogue, const HostProb* hp, int np, float alpha, hipStream_t s)
-{
-    if (epilogue == LPI_EPI_LN || epilogue == LPI_EPI_LN_QUICKGELU) {
-        // A = the fp16 residual stream (bf16 mode keeps it fp16 too), B = gamma o W in fp16; C in the mode's storage type
-        if (dtype == LPI_F16 && c_dtype == LPI_BF16) return dispatchp_ln<f16_t, bf16_t>(epilogue, hp, np, alpha, s);
-        if (dtype == LPI_F16 && c_dtype == LPI_F16) return dispatchp_ln<f16_t, f16_t>(epilogue, hp, np, alpha, s);
-        if (dtype == LPI_BF16 && c_dtype == LPI_BF16) return dispatchp_ln<bf16_t, bf16_t>(epilogue, hp, np, alpha, s);
-        return LPI_ENOSYS;
-    }
-    if (dtype == LPI_BF16 && c_dtype == LPI_BF16) return dispatchp<bf16_t, bf16_t>(epilogue, hp, np, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F32) return dispatchp<bf16_t, float>(epilogue, hp, np, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F16 && (epilogue == LPI_EPI_NONE || epilogue == LPI_EPI_RES_ROWSTATS) && hp[0].residual) {
-        for (int i = 1; i < np; ++i) if (!hp[i].residual) return LPI_EINVAL;
-        if (epilogue == LPI_EPI_RES_ROWSTATS) {
-            for (int i = 0; i < np; ++i) if (!hp[i].aux) return LPI_EINVAL;
-            return launchp_impl<bf16_t, f16_t, LPI_EPI_NONE, true, true>(hp, np, alpha, s);
-        }
-        return launchp_impl<bf16_t, f16_t, LPI_EPI_NONE, true, false>(hp, np, alpha, s);
-    }
-    if (dtype == LPI_F16 && c_dtype == LPI_F16) return dispatchp<f16_t, f16_t>(epilogue, hp, np, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F32) return dispatchp<f16_t, float>(epilogue, hp, np, alpha, s);
-    return LPI_ENOSYS;
+        return go(t, tc, epi, r, su);
+    });
 }
 
 }  // namespace
@@ -763,20 +725,8 @@ extern "C" int lpi_gemm_stamps_read(unsigned long long* dst) {
 #endif
 
 // bf16 / f16 operands only (the f32 path is MFMA-bound: its prologue share is small and its K-tile geometry differs)
-int lpi_gemm256p_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                        const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s)
-{
-    const HostProb hp = {M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux};
-    return launch_group(dtype, c_dtype, epilogue, &hp, 1, alpha, s);
-}
+int lpi_gemm256p_launch(const GemmCall& c) { return launch_group(c, &c.p, 1); }
 
 // Two GEMMs of the same operand types and epilogue kind in ONE persistent launch (lpi_gemm_nt_grouped); both already validated and
 // eligible for the 256x256 kernel.  LPI_ENOSYS: combination not built (the caller issues them one after the other).
-int lpi_gemm256p_launch2(int dtype, int c_dtype, int epilogue, float alpha, const lpi_gemm_desc* d, hipStream_t s)
-{
-    HostProb hp[2];
-    for (int i = 0; i < 2; ++i)
-        hp[i] = HostProb{d[i].M, d[i].N, d[i].K, d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, d[i].bias, (const float*)d[i].residual, d[i].ldr,
-                         d[i].aux, d[i].ldaux};
-    return launch_group(dtype, c_dtype, epilogue, hp, 2, alpha, s);
-}
+int lpi_gemm256p_launch2(const GemmCall& c, const lpi_gemm_desc* d) { return launch_group(c, d, 2); }

@@ -11,6 +11,7 @@
 // Each phase = 8 ds_read_b128 + 16 MFMA per wave between two raw barriers; waves 4-7 run one barrier behind waves 0-3 so one
 // group's LDS reads overlap the other's MFMAs (lgkmcnt(0) before the barrier keeps the restage WAR-safe, as in gemm256.hip).
 #include "gemm256x128_tile.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -44,73 +45,31 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256x128_kernel(
 }
 
 template <typename T, typename TC, int EPI, bool RES, bool SAVE_U>
-int launch_impl(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-                const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s, int group_m)
+int launch(const GemmCall& c, Tag<T>, Tag<TC>, Int<EPI>, Bool<RES>, Bool<SAVE_U>)
 {
-    const int tm = M / TM, tn = N / TN;
+    const lpi_gemm_desc& d = c.p;
+    const int tm = d.M / TM, tn = d.N / TN;
     auto kern = gemm256x128_kernel<T, TC, EPI, RES, SAVE_U>;
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES)) return e;
     lpi_note_gemm_kernel(LPI_GEMM_K_256X128);
-    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES, s, M, N, K, (const T*)A, lda, (const T*)B, ldb, (TC*)C, ldc, bias, residual,
-               ldr, (typename AuxT<T>::type*)aux, ldaux, alpha, tm, tn, group_m);
+    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS_BYTES)) return e;
+    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHR), LDS_BYTES, c.s, d.M, d.N, d.K, (const T*)d.A, d.lda, (const T*)d.B, d.ldb, (TC*)d.C, d.ldc, d.bias,
+               (const float*)d.residual, d.ldr, (typename AuxT<T>::type*)d.aux, d.ldaux, c.alpha, tm, tn, gemm_group_m());
     LPI_CHECK_LAST();
     return 0;
 }
 
-template <typename T, typename TC, int EPI>
-int launch(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-           const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s, int gm)
-{
-    if constexpr (EPI == LPI_EPI_NONE) {
-        if (residual) return launch_impl<T, TC, EPI, true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-        return launch_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-    } else {
-        if (residual) return LPI_ENOSYS;
-        if constexpr (EPI == LPI_EPI_QUICKGELU) {
-            if (aux) return launch_impl<T, TC, EPI, false, true>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-            return launch_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-        } else {
-            if (!aux) return LPI_EINVAL;
-            return launch_impl<T, TC, EPI, false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-        }
-    }
-}
-
-template <typename T, typename TC>
-int dispatch(int epi, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-             const float* residual, int ldr, void* aux, int ldaux, float alpha, hipStream_t s, int gm)
-{
-    switch (epi) {
-    case LPI_EPI_NONE: return launch<T, TC, LPI_EPI_NONE>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-    case LPI_EPI_QUICKGELU: return launch<T, TC, LPI_EPI_QUICKGELU>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-    case LPI_EPI_DQUICKGELU: return launch<T, TC, LPI_EPI_DQUICKGELU>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, gm);
-    }
-    return LPI_EINVAL;
-}
+// the (T, TC) pairs of the 256x128 kernel (no bf16x3: its rows are f32)
+typedef TypeList<Types<float, float>, Types<bf16_t, bf16_t>, Types<bf16_t, float>, Types<bf16_t, f16_t, ResidualOnly>, Types<f16_t, f16_t>, Types<f16_t, float>> Built;
 
 }  // namespace
 
-bool lpi_gemm256x128_eligible(int dtype, int M, int N, int K) {
-    const int bk = ROWB / (dtype == LPI_F32 ? 4 : 2);
-    return M % TM == 0 && N % TN == 0 && K % bk == 0 && K / bk >= 2;
+bool lpi_gemm256x128_eligible(int dtype, const lpi_gemm_desc& d) {
+    const int bk = ROWB / (dtype == LPI_F32 ? 4 : 2);      // (LPI_F32X3 never asks: lpi_gemm_nt sends 2-byte operands only)
+    return d.M % TM == 0 && d.N % TN == 0 && d.K % bk == 0 && d.K / bk >= 2;
 }
 
-int lpi_gemm256x128_launch(int dtype, int c_dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                           const float* bias, const float* residual, int ldr, int epilogue, void* aux, int ldaux, float alpha, hipStream_t s,
-                           int group_m)
+int lpi_gemm256x128_launch(const GemmCall& c)
 {
-    if (dtype == LPI_F32 && c_dtype == LPI_F32)
-        return dispatch<float, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, group_m);
-    if (dtype == LPI_BF16 && c_dtype == LPI_BF16)
-        return dispatch<bf16_t, bf16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, group_m);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F32)
-        return dispatch<bf16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, group_m);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F16 && epilogue == LPI_EPI_NONE && residual)
-        return launch_impl<bf16_t, f16_t, LPI_EPI_NONE, true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, group_m);
-    if (dtype == LPI_F16 && c_dtype == LPI_F16)
-        return dispatch<f16_t, f16_t>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, group_m);
-    if (dtype == LPI_F16 && c_dtype == LPI_F32)
-        return dispatch<f16_t, float>(epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, aux, ldaux, alpha, s, group_m);
-    return LPI_ENOSYS;
+    return gemm_pick(Built{}, c.dtype, c.c_dtype, c.epilogue, c.p.residual != nullptr, c.p.aux != nullptr, [&](auto... k) { return launch(c, k...); });
 }

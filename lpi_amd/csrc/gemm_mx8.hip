@@ -181,16 +181,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mx8_kernel(
 }
 
 template <typename TC, int EPI, bool RES>
-int launch(int M, int N, int K, const void* A, int lda, const void* As, int ldas, const void* B, int ldb, const void* Bs, int ldbs, void* C, int ldc,
-           void* Cs, int ldcs, const float* bias, const void* residual, int ldr, float alpha, hipStream_t s)
+int launch(const GemmCall& c, const Mx8Side& mx, Tag<TC>, Int<EPI>, Bool<RES>)
 {
-    const int tm = M / BM, tn = N / BN;
+    const lpi_gemm_desc& d = c.p;
+    const int tm = d.M / BM, tn = d.N / BN;
     auto kern = gemm_mx8_kernel<TC, EPI, RES>;
     static LdsOnce once;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES)) return e;
     lpi_note_gemm_kernel(LPI_GEMM_K_MX8);
-    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHREADS), 2 * STAGE_BYTES, s, M, N, K, (const uint8_t*)A, lda, (const uint8_t*)As, ldas, (const uint8_t*)B, ldb,
-               (const uint8_t*)Bs, ldbs, C, ldc, (uint8_t*)Cs, ldcs, bias, (const float*)residual, ldr, alpha, tm, tn);
+    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE_BYTES)) return e;
+    LPI_LAUNCH(kern, dim3(tm * tn), dim3(NTHREADS), 2 * STAGE_BYTES, c.s, d.M, d.N, d.K, (const uint8_t*)d.A, d.lda, mx.a_scales, mx.ldas, (const uint8_t*)d.B, d.ldb,
+               mx.b_scales, mx.ldbs, d.C, d.ldc, mx.c_scales, mx.ldcs, d.bias, (const float*)d.residual, d.ldr, c.alpha, tm, tn);
     LPI_CHECK_LAST();
     return 0;
 }
@@ -207,27 +207,9 @@ extern "C" int lpi_gemm_nt_mx8(int c_dtype, int M, int N, int K, const void* A, 
                                int ldr, int epilogue, float alpha, void* stream)
 {
     if (!lpi_gemm_mx8_ok(M, N, K)) return LPI_EINVAL;
-    if (int e = mx8_gemm_check_args(c_dtype, N, K, A, lda, a_scales, ldas, B, ldb, b_scales, ldbs, C, ldc, c_scales, ldcs, bias, residual, ldr, epilogue))
-        return e;
-    hipStream_t s = (hipStream_t)stream;
-#define MXG(TC, EPI, RES) return launch<TC, EPI, RES>(M, N, K, A, lda, a_scales, ldas, B, ldb, b_scales, ldbs, C, ldc, c_scales, ldcs, bias, residual, ldr, alpha, s)
-    const bool gelu = epilogue == LPI_EPI_QUICKGELU;
-    switch (c_dtype) {
-    case LPI_F32:
-        if (gelu) MXG(float, LPI_EPI_QUICKGELU, false);
-        if (residual) MXG(float, LPI_EPI_NONE, true);
-        MXG(float, LPI_EPI_NONE, false);
-    case LPI_BF16:
-        if (gelu) MXG(bf16_t, LPI_EPI_QUICKGELU, false);
-        MXG(bf16_t, LPI_EPI_NONE, false);
-    case LPI_F16:
-        if (gelu) MXG(f16_t, LPI_EPI_QUICKGELU, false);
-        if (residual) MXG(f16_t, LPI_EPI_NONE, true);
-        MXG(f16_t, LPI_EPI_NONE, false);
-    case LPI_MX8:
-        if (gelu) MXG(Mx8Out, LPI_EPI_QUICKGELU, false);
-        MXG(Mx8Out, LPI_EPI_NONE, false);
-    }
-#undef MXG
-    return LPI_EINVAL;
+    const GemmCall c{.dtype = LPI_MX8, .c_dtype = c_dtype, .epilogue = epilogue, .alpha = alpha, .s = (hipStream_t)stream,
+                     .p = {.M = M, .N = N, .K = K, .A = A, .lda = lda, .B = B, .ldb = ldb, .C = C, .ldc = ldc, .bias = bias, .residual = residual, .ldr = ldr}};
+    const Mx8Side mx = {(const uint8_t*)a_scales, ldas, (const uint8_t*)b_scales, ldbs, (uint8_t*)c_scales, ldcs};
+    if (int e = mx8_gemm_check_args(c, mx)) return e;
+    return mx8_pick<Mx8Out>(c, [&](auto... k) { return launch(c, mx, k...); });
 }

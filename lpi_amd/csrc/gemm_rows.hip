@@ -17,7 +17,7 @@
 //    (32 + 32) x K operand bytes (393 KB at K = 3072: ~3 us), not the K loop of a 128 x 128 tile on a handful of CUs;
 //  * two problems (the two towers' GEMM of the same op) in one launch, as everywhere in the lock-stepped step; an XCD gets a contiguous run of the n-major tile
 //    list, so a weight panel is fetched by one XCD.
-#include "common.h"
+#include "gemm_host.h"
 #include "gemm_epilogue.h"
 
 namespace {
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(RTHREADS, 2) void gemm_rows_kernel(RowsP<T> p0, Row
 }
 
 template <typename T, typename TC, int EPI, bool RES, bool SAVE_U>
-int rows_impl(int count, const lpi_gemm_desc* d, float alpha, hipStream_t s)
+int rows_launch(const GemmCall& c, const lpi_gemm_desc* d, int count, Tag<T>, Tag<TC>, Int<EPI>, Bool<RES>, Bool<SAVE_U>)
 {
     RowsP<T> g[2];
     for (int i = 0; i < 2; ++i) {
@@ -199,24 +199,13 @@ int rows_impl(int count, const lpi_gemm_desc* d, float alpha, hipStream_t s)
                         (const T*)q.A, (const T*)q.B, q.C, q.bias, (const float*)q.residual, q.aux};
     }
     lpi_note_gemm_kernel(LPI_GEMM_K_ROWS);
-    LPI_LAUNCH((gemm_rows_kernel<T, TC, EPI, RES, SAVE_U>), dim3(g[0].nwg + g[1].nwg), dim3(RTHREADS), 0, s, g[0], g[1], alpha);
+    LPI_LAUNCH((gemm_rows_kernel<T, TC, EPI, RES, SAVE_U>), dim3(g[0].nwg + g[1].nwg), dim3(RTHREADS), 0, c.s, g[0], g[1], c.alpha);
     LPI_CHECK_LAST();
     return 0;
 }
 
-template <typename T, typename TC>
-int rows_dispatch(int epi, int count, const lpi_gemm_desc* d, float alpha, hipStream_t s)
-{
-    const bool res = d[0].residual != nullptr, ax = d[0].aux != nullptr;
-    if (count == 2 && ((d[1].residual != nullptr) != res || (d[1].aux != nullptr) != ax)) return LPI_EINVAL;
-#define RW(EPI, RES, SU) return rows_impl<T, TC, EPI, RES, SU>(count, d, alpha, s)
-    if (epi == LPI_EPI_NONE) { if (res) RW(LPI_EPI_NONE, true, false); RW(LPI_EPI_NONE, false, false); }
-    if (res) return LPI_ENOSYS;
-    if (epi == LPI_EPI_QUICKGELU) { if (ax) RW(LPI_EPI_QUICKGELU, false, true); RW(LPI_EPI_QUICKGELU, false, false); }
-    if (epi == LPI_EPI_DQUICKGELU) { if (!ax) return LPI_EINVAL; RW(LPI_EPI_DQUICKGELU, false, false); }
-#undef RW
-    return LPI_EINVAL;
-}
+// the (T, TC) pairs of the few-row kernel (bf16 mode: the fp16 residual stream never has this few rows; no bf16x3: few-row GEMMs stay exact f32)
+typedef TypeList<Types<float, float>, Types<bf16_t, bf16_t>, Types<bf16_t, float>, Types<f16_t, f16_t>, Types<f16_t, float>> Built;
 
 }  // namespace
 
@@ -242,12 +231,10 @@ extern "C" int lpi_gemm_nt_rows(int dtype, int c_dtype, int epilogue, float alph
         if (q.bias && ((uintptr_t)q.bias & 15)) return LPI_EINVAL;
         if (q.aux && (q.ldaux < q.N || ((uintptr_t)q.aux & (4 * esz - 1)) || (q.ldaux & 3))) return LPI_EINVAL;
     }
-    if (c_dtype == LPI_F16 && dtype != LPI_F16) return LPI_ENOSYS;     // bf16 mode: the fp16 residual stream never has this few rows
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LPI_F32 && c_dtype == LPI_F32) return rows_dispatch<float, float>(epilogue, count, d, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_BF16) return rows_dispatch<bf16_t, bf16_t>(epilogue, count, d, alpha, s);
-    if (dtype == LPI_BF16 && c_dtype == LPI_F32) return rows_dispatch<bf16_t, float>(epilogue, count, d, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F16) return rows_dispatch<f16_t, f16_t>(epilogue, count, d, alpha, s);
-    if (dtype == LPI_F16 && c_dtype == LPI_F32) return rows_dispatch<f16_t, float>(epilogue, count, d, alpha, s);
-    return LPI_ENOSYS;
+    if (!types_listed(Built{}, dtype, c_dtype)) return LPI_ENOSYS;
+    const bool res = d[0].residual != nullptr, ax = d[0].aux != nullptr;
+    if (count == 2 && ((d[1].residual != nullptr) != res || (d[1].aux != nullptr) != ax)) return LPI_EINVAL;      // both problems run ONE instantiation
+    if (res && epilogue != LPI_EPI_NONE) return LPI_ENOSYS;      // this entry point's own: also for an unknown epilogue code, where the pick would say LPI_EINVAL
+    const GemmCall c{.dtype = dtype, .c_dtype = c_dtype, .epilogue = epilogue, .alpha = alpha, .s = (hipStream_t)stream};
+    return gemm_pick(Built{}, dtype, c_dtype, epilogue, res, ax, [&](auto... k) { return rows_launch(c, d, count, k...); });
 }

@@ -6,7 +6,7 @@
 // y 2^-e (exact: a power of two) rounded to nearest even by v_cvt_pk_fp8_f32, which on gfx950 is the OCP encoding with subnormals; by construction
 // no element exceeds 448, so the conversion never saturates.
 #pragma once
-#include "common.h"
+#include "gemm_host.h"
 #include "gemm_epilogue.h"
 
 // Element TAG of size 1 for the phased 256x256 tile (gemm256_tile.h): staging, swizzle and pointer arithmetic see a one-byte element, so a staged
@@ -66,22 +66,41 @@ __device__ __forceinline__ float mx8_max8(float v) {
 }
 
 // Host: everything lpi_gemm_nt_mx8 and lpi_gemm_nt_mx8_256 check beside their shape predicates; 0 or the code to return before any launch.
-inline int mx8_gemm_check_args(int c_dtype, int N, int K, const void* A, int lda, const void* a_scales, int ldas, const void* B, int ldb,
-                               const void* b_scales, int ldbs, const void* C, int ldc, const void* c_scales, int ldcs, const float* bias,
-                               const void* residual, int ldr, int epilogue)
+inline int mx8_gemm_check_args(const GemmCall& c, const Mx8Side& mx)
 {
-    if (!A || !B || !C || !a_scales || !b_scales) return LPI_EINVAL;
-    if (epilogue != LPI_EPI_NONE && epilogue != LPI_EPI_QUICKGELU) return LPI_EINVAL;
+    const lpi_gemm_desc& d = c.p;
+    const int c_dtype = c.c_dtype, N = d.N, K = d.K;
+    if (!d.A || !d.B || !d.C || !mx.a_scales || !mx.b_scales) return LPI_EINVAL;
+    if (c.epilogue != LPI_EPI_NONE && c.epilogue != LPI_EPI_QUICKGELU) return LPI_EINVAL;
     if (c_dtype != LPI_F32 && c_dtype != LPI_BF16 && c_dtype != LPI_F16 && c_dtype != LPI_MX8) return LPI_EINVAL;
-    if (lda < K || ldb < K || (lda & 15) || (ldb & 15) || ldas < K / 32 || ldbs < K / 32 || (ldas & 3) || (ldbs & 3) || ldc < N) return LPI_EINVAL;
-    if ((((uintptr_t)A | (uintptr_t)B) & 15) || (((uintptr_t)a_scales | (uintptr_t)b_scales) & 3)) return LPI_EINVAL;
-    if (bias && ((uintptr_t)bias & 15)) return LPI_EINVAL;
+    if (d.lda < K || d.ldb < K || (d.lda & 15) || (d.ldb & 15) || mx.ldas < K / 32 || mx.ldbs < K / 32 || (mx.ldas & 3) || (mx.ldbs & 3) || d.ldc < N) return LPI_EINVAL;
+    if ((((uintptr_t)d.A | (uintptr_t)d.B) & 15) || (((uintptr_t)mx.a_scales | (uintptr_t)mx.b_scales) & 3)) return LPI_EINVAL;
+    if (d.bias && ((uintptr_t)d.bias & 15)) return LPI_EINVAL;
     const int csz = c_dtype == LPI_F32 ? 4 : c_dtype == LPI_MX8 ? 1 : 2;
-    if (((uintptr_t)C & 15) || (ldc * csz) % (4 * csz)) return LPI_EINVAL;
-    if (c_dtype == LPI_MX8 && (!c_scales || ldcs < N / 32 || residual)) return LPI_EINVAL;
-    if (residual) {      // the residual has C's type: fp16 with an fp16 C (the residual stream of the 2-byte modes), f32 with an f32 C
-        if (epilogue != LPI_EPI_NONE || c_dtype == LPI_BF16) return LPI_ENOSYS;
-        if (ldr < N || (ldr & 3) || ((uintptr_t)residual & 15)) return LPI_EINVAL;
+    if (((uintptr_t)d.C & 15) || (d.ldc * csz) % (4 * csz)) return LPI_EINVAL;
+    if (c_dtype == LPI_MX8 && (!mx.c_scales || mx.ldcs < N / 32 || d.residual)) return LPI_EINVAL;
+    if (d.residual) {      // the residual has C's type: fp16 with an fp16 C (the residual stream of the 2-byte modes), f32 with an f32 C
+        if (c.epilogue != LPI_EPI_NONE || c_dtype == LPI_BF16) return LPI_ENOSYS;
+        if (d.ldr < N || (d.ldr & 3) || ((uintptr_t)d.residual & 15)) return LPI_EINVAL;
     }
     return 0;
+}
+
+// Host: a checked call's c_dtype, epilogue and residual -> f(Tag<TC>, Int<EPI>, Bool<RES>); MxOut is the caller's C type tag of an MX output.  A residual is
+// built for the f32 and the fp16 C alone; LPI_EINVAL for any other c_dtype.
+template <typename MxOut, typename F> int mx8_pick(const GemmCall& c, F f)
+{
+    auto epi = [&](auto tc, auto has_res) {
+        if (c.epilogue == LPI_EPI_QUICKGELU) return f(tc, Int<LPI_EPI_QUICKGELU>{}, Bool<false>{});
+        if constexpr (decltype(has_res)::value)
+            if (c.p.residual) return f(tc, Int<LPI_EPI_NONE>{}, Bool<true>{});
+        return f(tc, Int<LPI_EPI_NONE>{}, Bool<false>{});
+    };
+    switch (c.c_dtype) {
+    case LPI_F32: return epi(Tag<float>{}, Bool<true>{});
+    case LPI_BF16: return epi(Tag<bf16_t>{}, Bool<false>{});
+    case LPI_F16: return epi(Tag<f16_t>{}, Bool<true>{});
+    case LPI_MX8: return epi(Tag<MxOut>{}, Bool<false>{});
+    }
+    return LPI_EINVAL;
 }
