@@ -56,24 +56,24 @@ int lpi_search_merge(int nq, int k, int nparts, const float* part_val, const int
     return 0;
 }
 
-// An upper bound of what the launches use that never shrinks when an argument grows (the split count itself falls as the row blocks rise).
+// An upper bound of what the launches use (search_blocks, search_tile.h): the two lists of k pairs that every row of every block leaves.
 extern "C" long lpi_search_workspace(int nq, int ng, int k)
 {
     if (nq <= 0 || ng <= 0 || k < 0 || k > KMAX) return LPI_EINVAL;
     if (k == 0) return 8L * nq;      // thr f32 [nq] | gstar int32 [nq]
-    const long rb = (nq + BM - 1) / BM, tiles = (ng + BN - 1) / BN;
-    const long blocks = tiles * rb < WG_TARGET - 1 + rb ? tiles * rb : WG_TARGET - 1 + rb;      // >= splits * rb
-    return blocks * BM * 2 * k * 8;
+    return search_blocks(nq, ng) * BM * 2 * k * 8;
 }
 
 extern "C" int lpi_search_topk(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, int k, int col_base, int accumulate,
                                int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
 {
-    return search_topk<float>(nq, ng, E, Q, ldq, G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
+    return search_topk<float, MODE_TOPK>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .k = k, .col_base = col_base,
+                                                    .accumulate = accumulate, .idx = idx, .val = val, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 
 extern "C" int lpi_search_rank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* gt, int gt_per_row,
                                int32_t* rank, void* ws, long ws_bytes, void* stream)
 {
-    return search_rank<float>(nq, ng, E, Q, ldq, G, ldg, gt, gt_per_row, rank, ws, ws_bytes, stream);
+    return search_rank<float>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .gt = gt, .gt_per_row = gt_per_row,
+                                         .rank = rank, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }

@@ -9,14 +9,16 @@ extern "C" int lpi_search_topk_mx4(int nq, int ng, int E, const void* Q, int ldq
                                    const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes,
                                    void* stream)
 {
-    return search_topk<mx4_t>(nq, ng, E, (const mx4_t*)Q, ldq, (const mx4_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream,
-                              SearchScales{(const uint8_t*)q_scales, ldqs, (const uint8_t*)g_scales, ldgs});
+    return search_topk<mx4_t, MODE_TOPK>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .sc = {q_scales, ldqs, g_scales, ldgs},
+                                                    .k = k, .col_base = col_base, .accumulate = accumulate, .idx = idx, .val = val, .ws = ws, .ws_bytes = ws_bytes,
+                                                    .stream = stream});
 }
 
 extern "C" int lpi_search_topk_wide_mx4(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
                                         const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws,
                                         long ws_bytes, void* stream)
 {
-    return search_topk_wide<mx4_t>(nq, ng, E, (const mx4_t*)Q, ldq, (const mx4_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream,
-                                   SearchScales{(const uint8_t*)q_scales, ldqs, (const uint8_t*)g_scales, ldgs});
+    return search_topk<mx4_t, MODE_WIDE>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .sc = {q_scales, ldqs, g_scales, ldgs},
+                                                    .k = k, .col_base = col_base, .accumulate = accumulate, .idx = idx, .val = val, .ws = ws, .ws_bytes = ws_bytes,
+                                                    .stream = stream});
 }

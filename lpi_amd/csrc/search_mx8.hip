@@ -8,13 +8,14 @@ extern "C" int lpi_search_topk_mx8(int nq, int ng, int E, const void* Q, int ldq
                                    const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws, long ws_bytes,
                                    void* stream)
 {
-    return search_topk<mx8_t>(nq, ng, E, (const mx8_t*)Q, ldq, (const mx8_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream,
-                              SearchScales{(const uint8_t*)q_scales, ldqs, (const uint8_t*)g_scales, ldgs});
+    return search_topk<mx8_t, MODE_TOPK>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .sc = {q_scales, ldqs, g_scales, ldgs},
+                                                    .k = k, .col_base = col_base, .accumulate = accumulate, .idx = idx, .val = val, .ws = ws, .ws_bytes = ws_bytes,
+                                                    .stream = stream});
 }
 
 extern "C" int lpi_search_rank_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
                                    const void* g_scales, int ldgs, const int32_t* gt, int gt_per_row, int32_t* rank, void* ws, long ws_bytes, void* stream)
 {
-    return search_rank<mx8_t>(nq, ng, E, (const mx8_t*)Q, ldq, (const mx8_t*)G, ldg, gt, gt_per_row, rank, ws, ws_bytes, stream,
-                              SearchScales{(const uint8_t*)q_scales, ldqs, (const uint8_t*)g_scales, ldgs});
+    return search_rank<mx8_t>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .sc = {q_scales, ldqs, g_scales, ldgs}, .gt = gt,
+                                         .gt_per_row = gt_per_row, .rank = rank, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }

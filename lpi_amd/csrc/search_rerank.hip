@@ -139,36 +139,29 @@ __global__ __launch_bounds__(64 * RR_ROWS) void search_rerank_kernel(int nq, int
 }
 
 template <typename T>
-int search_rerank(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const int32_t* cand, int ldc, int kc, int k, int32_t* idx, float* val,
-                  void* stream)
+int search_rerank(const SearchCall& c)
 {
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, SearchScales{})) return e;
-    if (kc < 1 || kc > KWIDE || k < 1 || k > kc || ldc < kc) return LPI_EINVAL;
-    if (!cand || !idx || !val || (((uintptr_t)cand | (uintptr_t)idx | (uintptr_t)val) & 3)) return LPI_EINVAL;
-    LPI_LAUNCH(search_rerank_kernel<T>, dim3((nq + RR_ROWS - 1) / RR_ROWS), dim3(64 * RR_ROWS), 0, (hipStream_t)stream, nq, ng, E, Q, ldq, G, ldg, cand,
-               ldc, kc, k, idx, val);
+    if (int e = search_check<T>(c)) return e;
+    if (!rerank_ok(c)) return LPI_EINVAL;
+    LPI_LAUNCH(search_rerank_kernel<T>, dim3((c.nq + RR_ROWS - 1) / RR_ROWS), dim3(64 * RR_ROWS), 0, (hipStream_t)c.stream, c.nq, c.ng, c.E, (const T*)c.Q,
+               c.ldq, (const T*)c.G, c.ldg, c.cand, c.ldc, c.kc, c.k, c.idx, c.val);
     LPI_CHECK_LAST();
     return 0;
 }
 
 }  // namespace
 
-extern "C" int lpi_search_rerank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* cand, int ldc, int kc, int k,
-                                 int32_t* idx, float* val, void* stream)
-{
-    return search_rerank<float>(nq, ng, E, Q, ldq, G, ldg, cand, ldc, kc, k, idx, val, stream);
-}
-
+// the f32 form is the typed one at LPI_F32: the three kernels are instantiated here, once
 extern "C" int lpi_search_rerank_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, const int32_t* cand, int ldc, int kc,
                                    int k, int32_t* idx, float* val, void* stream)
 {
-    switch (dt) {
-    case LPI_F32:
-        return lpi_search_rerank(nq, ng, E, (const float*)Q, ldq, (const float*)G, ldg, cand, ldc, kc, k, idx, val, stream);
-    case LPI_BF16:
-        return search_rerank<bf16_t>(nq, ng, E, (const bf16_t*)Q, ldq, (const bf16_t*)G, ldg, cand, ldc, kc, k, idx, val, stream);
-    case LPI_F16:
-        return search_rerank<f16_t>(nq, ng, E, (const f16_t*)Q, ldq, (const f16_t*)G, ldg, cand, ldc, kc, k, idx, val, stream);
-    }
-    return LPI_EINVAL;
+    const SearchCall c{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .k = k, .idx = idx, .val = val, .cand = cand, .ldc = ldc, .kc = kc,
+                       .stream = stream};
+    return search_pick(PlainTypes{}, dt, [&](auto t) { return search_rerank<type_of<decltype(t)>>(c); });
+}
+
+extern "C" int lpi_search_rerank(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, const int32_t* cand, int ldc, int kc, int k,
+                                 int32_t* idx, float* val, void* stream)
+{
+    return lpi_search_rerank_t(LPI_F32, nq, ng, E, Q, ldq, G, ldg, cand, ldc, kc, k, idx, val, stream);
 }

@@ -1,4 +1,4 @@
-// The tile code of the streamed search and the host logic of its two calls, for an operand type T: float (search.hip), bf16_t / f16_t (search16.hip),
+// The tile code of the streamed search and the host layer of the whole family (at the end), for an operand type T: float (search.hip), bf16_t / f16_t (search16.hip),
 // mx8_t (search_mx8.hip: e4m3 bytes + one E8M0 scale per 32 elements, mx8.h) or mx4_t (search_mx4.hip: e2m1 nibbles + the same scales, mx4.h; top-k only).
 //
 // Design:
@@ -33,7 +33,7 @@
 //  * wide top-k (MODE_WIDE, k <= 256, instantiated by search_wide.hip, where the design is described): the same main loop and masks; scores that beat a
 //    row's threshold are appended to a candidate buffer in the workspace and a wave selects the k best with a bitonic network in registers.
 #pragma once
-#include "common.h"
+#include "dispatch.h"
 #include "mx8.h"
 #include "mx4.h"
 #include <math.h>
@@ -123,9 +123,9 @@ struct SearchArgs<mx4_t> {
     const uint8_t* Gs;
     int ldgs;
 };
-struct SearchScales {      // what the host calls take for them; unused by the other types
-    const uint8_t* q; int ldq;
-    const uint8_t* g; int ldg;
+struct SearchScales {      // what the host calls take for them (E8M0 bytes); unused by the other types
+    const void* q; int ldq;
+    const void* g; int ldg;
 };
 
 // (s, j) before (v, i) in the order value descending, then index descending
@@ -580,110 +580,129 @@ __global__ __launch_bounds__(NTHREADS, 2) void search_kernel(SearchArgs<T> a)
     }
 }
 
-inline int search_splits(int nq, int ng)
-{
-    const int rb = (nq + BM - 1) / BM, tiles = (ng + BN - 1) / BN;
-    const int want = (WG_TARGET + rb - 1) / rb;
-    return tiles < want ? tiles : want;
-}
+// ------------------------------------------------------------------------------------------------ the host layer
+// Every entry point of the family fills ONE SearchCall and hands it to search_topk<T, MODE> / search_rank<T> (below) or search_rerank<T> (search_rerank.hip);
+// the typed ones choose T from a list (search_pick).  Each argument rule is a host predicate on the struct, written once, and sweep_args<T> is the only
+// writer of the kernel argument.
 
-// the envelope both calls share: E a multiple of half a slab (f32: 16, 2-byte: 32; MX-FP8: of a whole one, 128; MX-FP4: 128 elements, half a slab), rows of
+// the arguments of one call; a field an entry point does not have keeps its default
+struct SearchCall {
+    int nq = 0, ng = 0, E = 0;                            // E in elements, whatever the type
+    const void* Q = nullptr; int ldq = 0;
+    const void* G = nullptr; int ldg = 0;
+    SearchScales sc{};
+    int k = 0, col_base = 0, accumulate = 0;              // the list forms (k, idx, val: the re-rank form too)
+    int32_t* idx = nullptr; float* val = nullptr;
+    const int32_t* gt = nullptr; int gt_per_row = 0; int32_t* rank = nullptr;      // the rank form
+    const int32_t* cand = nullptr; int ldc = 0, kc = 0;   // the re-rank form
+    void* ws = nullptr; long ws_bytes = 0; void* stream = nullptr;
+};
+
+// The sweep's grid is row blocks x splits, about WG_TARGET workgroups.  search_blocks is what the workspace functions size for: splits * row blocks = the
+// largest multiple of the row blocks not above it, so blocks >= splits * row blocks, and it never shrinks when an argument grows (the split count itself falls
+// as the row blocks rise)
+inline long search_blocks(int nq, int ng) {
+    const long rb = (nq + BM - 1) / BM, tiles = (ng + BN - 1) / BN;
+    return tiles * rb < WG_TARGET - 1 + rb ? tiles * rb : WG_TARGET - 1 + rb;
+}
+inline int search_splits(int nq, int ng) { return (int)(search_blocks(nq, ng) / ((nq + BM - 1) / BM)); }      // min(tiles, ceil(WG_TARGET / row blocks))
+
+// ---- the argument rules (host predicates: no HIP call)
+// the envelope every call shares: E a multiple of half a slab (f32: 16, 2-byte: 32; MX-FP8: of a whole one, 128; MX-FP4: 128 elements, half a slab), rows of
 // whole 16-byte pieces (MX-FP4: leading dimensions in bytes, a row has E / 2); MX-FP8 / MX-FP4: scale rows of whole dwords
 template <typename T>
-int search_check(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const SearchScales& sc)
+int search_check(const SearchCall& c)
 {
     constexpr int EPC = Elem<T>::EPC, HALF = kHasScales<T> ? ROW_BYTES : ROW_BYTES / (int)sizeof(T) / 2;
-    if (nq <= 0 || ng <= 0 || E <= 0 || (E & (HALF - 1)) || E > 1024) return LPI_EINVAL;
-    const int row = kIsMx4<T> ? E / 2 : E;      // in the units of ldq / ldg
-    if (ldq < row || ldg < row || (ldq & (EPC - 1)) || (ldg & (EPC - 1))) return LPI_EINVAL;
-    if (!Q || !G || (((uintptr_t)Q | (uintptr_t)G) & 15)) return LPI_EINVAL;
+    if (c.nq <= 0 || c.ng <= 0 || c.E <= 0 || (c.E & (HALF - 1)) || c.E > 1024) return LPI_EINVAL;
+    const int row = kIsMx4<T> ? c.E / 2 : c.E;      // in the units of ldq / ldg
+    if (c.ldq < row || c.ldg < row || (c.ldq & (EPC - 1)) || (c.ldg & (EPC - 1))) return LPI_EINVAL;
+    if (!c.Q || !c.G || (((uintptr_t)c.Q | (uintptr_t)c.G) & 15)) return LPI_EINVAL;
     if constexpr (kHasScales<T>) {
-        if (!sc.q || !sc.g || (((uintptr_t)sc.q | (uintptr_t)sc.g) & 3)) return LPI_EINVAL;
-        if (sc.ldq < E / 32 || sc.ldg < E / 32 || (sc.ldq & 3) || (sc.ldg & 3)) return LPI_EINVAL;
+        if (!c.sc.q || !c.sc.g || (((uintptr_t)c.sc.q | (uintptr_t)c.sc.g) & 3)) return LPI_EINVAL;
+        if (c.sc.ldq < c.E / 32 || c.sc.ldg < c.E / 32 || (c.sc.ldq & 3) || (c.sc.ldg & 3)) return LPI_EINVAL;
     }
     return 0;
 }
-
-template <typename T>
-int search_topk(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, int k, int col_base, int accumulate, int32_t* idx, float* val,
-                void* ws, long ws_bytes, void* stream, SearchScales sc = SearchScales{})
-{
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
-    if (k < 1 || k > KMAX || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
-    if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, k)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    SearchArgs<T> a{};
-    a.nq = nq; a.ng = ng; a.E = kIsMx4<T> ? E / 2 : E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;
-    if constexpr (kHasScales<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
-    a.tiles = (ng + BN - 1) / BN;
-    a.splits = search_splits(nq, ng);
-    const size_t nlist = (size_t)2 * a.splits * nq * k;
-    a.part_val = (float*)ws;
-    a.part_idx = (int32_t*)ws + nlist;
-    auto kern = search_kernel<T, MODE_TOPK>;
-    static LdsOnce once;
-    constexpr int STAGE = kStageBytes<T>;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * STAGE + 4 * 64 * KMAX * 8)) return e;
-    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE + 4 * 64 * k * 8, s, a);
-    LPI_CHECK_LAST();
-    return lpi_search_merge(nq, k, 2 * a.splits, a.part_val, a.part_idx, col_base, accumulate, idx, val, s);
+// a list of k <= kmax per query row, in idx / val; without `accumulate` the gallery fills it
+inline bool list_ok(const SearchCall& c, int kmax) {
+    return c.k >= 1 && c.k <= kmax && (c.accumulate || c.k <= c.ng) && c.col_base >= 0 && (long)c.col_base + c.ng <= 0x7fffffffL && c.idx && c.val;
+}
+inline bool rank_ok(const SearchCall& c) { return c.gt && c.gt_per_row > 0 && c.rank; }
+// `need` = what the form's workspace function answers for the call
+inline bool ws_ok(const SearchCall& c, long need) { return c.ws && !((uintptr_t)c.ws & 3) && c.ws_bytes >= need; }
+inline bool rerank_ok(const SearchCall& c) {
+    return c.kc >= 1 && c.kc <= KWIDE && c.k >= 1 && c.k <= c.kc && c.ldc >= c.kc && c.cand && c.idx && c.val &&
+           !(((uintptr_t)c.cand | (uintptr_t)c.idx | (uintptr_t)c.val) & 3);
 }
 
-// the wide call (search_wide.hip has the design and the merge kernel): the sweep with the MODE_WIDE epilogue, then the merge of the splits' lists
+// the typed pick: f(Tag<T>) for the type of the list L (dispatch.h) whose code is dt; any other code is refused and calls nothing
+typedef TypeList<Types<bf16_t>, Types<f16_t>> TwoByte;                          // search16.hip: LPI_F32 is forwarded to search.hip's entry points
+typedef TypeList<Types<float>, Types<bf16_t>, Types<f16_t>> PlainTypes;         // search_wide.hip, search_rerank.hip
+template <typename L, typename F> int search_pick(L, int dt, F f) { int rc = LPI_EINVAL; dispatch_types(L{}, [&](auto t) { rc = f(t); }, dt); return rc; }
+
+// ---- the ONE writer of the kernel argument, for all three sweeps.  per_split = the pairs a gallery split leaves in the workspace per query row (the list
+// forms); 0 = the rank form, whose workspace is thr | gstar
 template <typename T>
-int search_topk_wide(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, int k, int col_base, int accumulate, int32_t* idx, float* val,
-                     void* ws, long ws_bytes, void* stream, SearchScales sc = SearchScales{})
+SearchArgs<T> sweep_args(const SearchCall& c, int per_split = 0)
 {
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
-    if (k < 1 || k > KWIDE || (!accumulate && k > ng) || col_base < 0 || (long)col_base + ng > 0x7fffffffL) return LPI_EINVAL;
-    if (!idx || !val || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_wide_workspace(nq, ng, k)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
     SearchArgs<T> a{};
-    a.nq = nq; a.ng = ng; a.E = kIsMx4<T> ? E / 2 : E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg; a.k = k;      // MX-FP4: the row length in bytes
-    if constexpr (kHasScales<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
-    a.tiles = (ng + BN - 1) / BN;
-    a.splits = search_splits(nq, ng);
-    const int cap = wide_cap(k);
-    const size_t nlist = (size_t)a.splits * nq * cap;      // [splits][nq][cap] values, then as many indices
-    a.part_val = (float*)ws;
-    a.part_idx = (int32_t*)ws + nlist;
-    auto kern = search_kernel<T, MODE_WIDE>;
-    static LdsOnce once;
-    constexpr int LDS = 2 * kStageBytes<T> + BM * 12;
-    if (int e = lpi_ensure_lds(once, (const void*)kern, LDS)) return e;
-    LPI_LAUNCH(kern, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), LDS, s, a);
-    LPI_CHECK_LAST();
-    return lpi_search_wide_merge(nq, k, a.splits, cap, a.part_val, a.part_idx, col_base, accumulate, idx, val, s);
+    a.nq = c.nq; a.ng = c.ng; a.E = kIsMx4<T> ? c.E / 2 : c.E;      // MX-FP4: the row length in bytes
+    a.Q = (const T*)c.Q; a.ldq = c.ldq; a.G = (const T*)c.G; a.ldg = c.ldg;
+    if constexpr (kHasScales<T>) { a.Qs = (const uint8_t*)c.sc.q; a.ldqs = c.sc.ldq; a.Gs = (const uint8_t*)c.sc.g; a.ldgs = c.sc.ldg; }
+    a.tiles = (c.ng + BN - 1) / BN; a.splits = search_splits(c.nq, c.ng);
+    if (per_split) { a.k = c.k; a.part_val = (float*)c.ws; a.part_idx = (int32_t*)c.ws + (size_t)a.splits * c.nq * per_split; }      // the indices behind the values
+    else { a.gt = c.gt; a.gpr = c.gt_per_row; a.thr = (float*)c.ws; a.gstar = (int32_t*)c.ws + c.nq; a.rank = c.rank; }
+    return a;
 }
 
-
-template <typename T>
-int search_rank(int nq, int ng, int E, const T* Q, int ldq, const T* G, int ldg, const int32_t* gt, int gt_per_row, int32_t* rank, void* ws,
-                long ws_bytes, void* stream, SearchScales sc = SearchScales{})
+// ---- one sweep launch: `lds` bytes behind the staging buffers, of at most `lds_max` (the kernel's limit, raised once per device).  The static is one per
+// kernel: this function is instantiated once per (T, MODE)
+template <typename T, int MODE>
+int sweep(const SearchArgs<T>& a, int splits, int lds_max, int lds, hipStream_t s)
 {
-    if (int e = search_check<T>(nq, ng, E, Q, ldq, G, ldg, sc)) return e;
-    if (!gt || gt_per_row <= 0 || !rank || !ws || ((uintptr_t)ws & 3) || ws_bytes < lpi_search_workspace(nq, ng, 0)) return LPI_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    SearchArgs<T> a{};
-    a.nq = nq; a.ng = ng; a.E = E; a.Q = Q; a.ldq = ldq; a.G = G; a.ldg = ldg;
-    if constexpr (kIsMx8<T>) { a.Qs = sc.q; a.ldqs = sc.ldq; a.Gs = sc.g; a.ldgs = sc.ldg; }
-    a.tiles = (ng + BN - 1) / BN;
-    a.splits = search_splits(nq, ng);
-    a.gt = gt; a.gpr = gt_per_row;
-    a.thr = (float*)ws;
-    a.gstar = (int32_t*)ws + nq;
-    a.rank = rank;
-    auto kt = search_kernel<T, MODE_THRESH>;
-    auto kr = search_kernel<T, MODE_RANK>;
-    static LdsOnce once_t, once_r;
-    constexpr int STAGE = kStageBytes<T>;
-    if (int e = lpi_ensure_lds(once_t, (const void*)kt, 2 * STAGE)) return e;
-    if (int e = lpi_ensure_lds(once_r, (const void*)kr, 2 * STAGE)) return e;
-    LPI_LAUNCH(kt, dim3((nq + BM - 1) / BM, 1), dim3(NTHREADS), 2 * STAGE, s, a);
-    LPI_CHECK_LAST();
-    LPI_LAUNCH(kr, dim3((nq + BM - 1) / BM, a.splits), dim3(NTHREADS), 2 * STAGE, s, a);
+    static LdsOnce once;
+    auto kern = search_kernel<T, MODE>;
+    if (int e = lpi_ensure_lds(once, (const void*)kern, 2 * kStageBytes<T> + lds_max)) return e;
+    LPI_LAUNCH(kern, dim3((a.nq + BM - 1) / BM, splits), dim3(NTHREADS), 2 * kStageBytes<T> + lds, s, a);
     LPI_CHECK_LAST();
     return 0;
+}
+
+// what the narrow (MODE_TOPK) and the wide (MODE_WIDE: search_wide.hip has the design and the merge kernel) top-k call differ in
+template <int MODE> struct ListMode {
+    static constexpr bool WIDE = MODE == MODE_WIDE;
+    static constexpr int KTOP = WIDE ? KWIDE : KMAX;
+    static constexpr auto workspace = WIDE ? lpi_search_wide_workspace : lpi_search_workspace;
+    static constexpr int per_split(int k) { return WIDE ? wide_cap(k) : 2 * k; }      // a candidate buffer | a sorted list per wave column
+    static constexpr int lds(int k) { return WIDE ? BM * 12 : 4 * 64 * k * 8; }       // per tile row a threshold pair and a fill counter | every wave's lists
+    static int merge(const SearchCall& c, int splits, const float* pv, const int32_t* pi, hipStream_t s) {
+        return WIDE ? lpi_search_wide_merge(c.nq, c.k, splits, wide_cap(c.k), pv, pi, c.col_base, c.accumulate, c.idx, c.val, s)
+                    : lpi_search_merge(c.nq, c.k, 2 * splits, pv, pi, c.col_base, c.accumulate, c.idx, c.val, s);
+    }
+};
+
+// a top-k call: the sweep with the mode's epilogue, then the merge of the splits' lists (and, with accumulate, the held one) into idx / val
+template <typename T, int MODE>
+int search_topk(const SearchCall& c)
+{
+    typedef ListMode<MODE> M;
+    if (int e = search_check<T>(c)) return e;
+    if (!list_ok(c, M::KTOP) || !ws_ok(c, M::workspace(c.nq, c.ng, c.k))) return LPI_EINVAL;
+    const SearchArgs<T> a = sweep_args<T>(c, M::per_split(c.k));
+    if (int e = sweep<T, MODE>(a, a.splits, M::lds(M::KTOP), M::lds(c.k), (hipStream_t)c.stream)) return e;
+    return M::merge(c, a.splits, a.part_val, a.part_idx, (hipStream_t)c.stream);
+}
+
+// a rank call: the gathered launch leaves the thresholds, the sweep counts what beats them
+template <typename T>
+int search_rank(const SearchCall& c)
+{
+    if (int e = search_check<T>(c)) return e;
+    if (!rank_ok(c) || !ws_ok(c, lpi_search_workspace(c.nq, c.ng, 0))) return LPI_EINVAL;
+    const SearchArgs<T> a = sweep_args<T>(c);
+    if (int e = sweep<T, MODE_THRESH>(a, 1, 0, 0, (hipStream_t)c.stream)) return e;
+    return sweep<T, MODE_RANK>(a, a.splits, 0, 0, (hipStream_t)c.stream);
 }
 
 }  // namespace

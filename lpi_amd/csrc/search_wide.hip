@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64 * MERGE_ROWS) void search_wide_merge_kernel(int 
 
 }  // namespace
 
-// the launch of search_wide_merge_kernel (search_tile.h's search_topk_wide calls it from every object that instantiates a wide sweep)
+// the launch of search_wide_merge_kernel (search_tile.h's search_topk<T, MODE_WIDE> calls it from every object that instantiates a wide sweep)
 int lpi_search_wide_merge(int nq, int k, int nparts, int cap, const float* part_val, const int32_t* part_idx, int col_base, int accumulate, int32_t* idx,
                           float* val, hipStream_t s)
 {
@@ -73,40 +73,33 @@ int lpi_search_wide_merge(int nq, int k, int nparts, int cap, const float* part_
     return 0;
 }
 
-// An upper bound of what the launches use that never shrinks when an argument grows: lpi_search_workspace's block bound, one candidate buffer per block row.
+// An upper bound of what the launches use (search_blocks, search_tile.h): one candidate buffer for every row of every block.
 extern "C" long lpi_search_wide_workspace(int nq, int ng, int k)
 {
     if (nq <= 0 || ng <= 0 || k < 1 || k > KWIDE) return LPI_EINVAL;
-    const long rb = (nq + BM - 1) / BM, tiles = (ng + BN - 1) / BN;
-    const long blocks = tiles * rb < WG_TARGET - 1 + rb ? tiles * rb : WG_TARGET - 1 + rb;      // >= splits * rb
-    return blocks * BM * wide_cap(k) * 8;
+    return search_blocks(nq, ng) * BM * wide_cap(k) * 8;
+}
+
+// the f32 form is the typed one at LPI_F32: the three wide sweeps of the plain types are instantiated here, once
+extern "C" int lpi_search_topk_wide_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, int k, int col_base, int accumulate,
+                                      int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
+{
+    const SearchCall c{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .k = k, .col_base = col_base, .accumulate = accumulate, .idx = idx,
+                       .val = val, .ws = ws, .ws_bytes = ws_bytes, .stream = stream};
+    return search_pick(PlainTypes{}, dt, [&](auto t) { return search_topk<type_of<decltype(t)>, MODE_WIDE>(c); });
 }
 
 extern "C" int lpi_search_topk_wide(int nq, int ng, int E, const float* Q, int ldq, const float* G, int ldg, int k, int col_base, int accumulate,
                                     int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
 {
-    return search_topk_wide<float>(nq, ng, E, Q, ldq, G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
-}
-
-extern "C" int lpi_search_topk_wide_t(int dt, int nq, int ng, int E, const void* Q, int ldq, const void* G, int ldg, int k, int col_base, int accumulate,
-                                      int32_t* idx, float* val, void* ws, long ws_bytes, void* stream)
-{
-    switch (dt) {
-    case LPI_F32:
-        return lpi_search_topk_wide(nq, ng, E, (const float*)Q, ldq, (const float*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
-    case LPI_BF16:
-        return search_topk_wide<bf16_t>(nq, ng, E, (const bf16_t*)Q, ldq, (const bf16_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes,
-                                        stream);
-    case LPI_F16:
-        return search_topk_wide<f16_t>(nq, ng, E, (const f16_t*)Q, ldq, (const f16_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
-    }
-    return LPI_EINVAL;
+    return lpi_search_topk_wide_t(LPI_F32, nq, ng, E, Q, ldq, G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream);
 }
 
 extern "C" int lpi_search_topk_wide_mx8(int nq, int ng, int E, const void* Q, int ldq, const void* q_scales, int ldqs, const void* G, int ldg,
                                         const void* g_scales, int ldgs, int k, int col_base, int accumulate, int32_t* idx, float* val, void* ws,
                                         long ws_bytes, void* stream)
 {
-    return search_topk_wide<mx8_t>(nq, ng, E, (const mx8_t*)Q, ldq, (const mx8_t*)G, ldg, k, col_base, accumulate, idx, val, ws, ws_bytes, stream,
-                                   SearchScales{(const uint8_t*)q_scales, ldqs, (const uint8_t*)g_scales, ldgs});
+    return search_topk<mx8_t, MODE_WIDE>(SearchCall{.nq = nq, .ng = ng, .E = E, .Q = Q, .ldq = ldq, .G = G, .ldg = ldg, .sc = {q_scales, ldqs, g_scales, ldgs},
+                                                    .k = k, .col_base = col_base, .accumulate = accumulate, .idx = idx, .val = val, .ws = ws, .ws_bytes = ws_bytes,
+                                                    .stream = stream});
 }

@@ -54,81 +54,37 @@ def _operands(operands):
     return _OPERANDS[operands]
 
 
-class Mx8Rows:
-    """Rows in the project's MX-FP8 format (include/lpi_hip.h): ``codes`` uint8 [n, E] (e4m3fn bytes) and ``scales`` uint8 [n, E/32] (E8M0, one per 32
-    consecutive elements), as the search reads them in place: unit inner strides, a 16-byte row stride and base for the codes, a 4-byte row stride and
-    base for the scales.  Immutable; ``rows[a:b]`` is a view of rows a..b-1 (a gallery searched in chunks with ``col_base`` / ``into``)."""
+class _MxRows:
+    """Rows in one of the project's block-scaled formats (include/lpi_hip.h): ``codes`` uint8 [n, E / elements per byte] and ``scales`` uint8 [n, E / 32]
+    (E8M0, one per 32 consecutive elements), as the search reads them in place: unit inner strides, a 16-byte row stride and base for the codes, a 4-byte
+    row stride and base for the scales.  Immutable; ``rows[a:b]`` is a view of rows a..b-1 (a gallery searched in chunks with ``col_base`` / ``into``);
+    ``shape`` is (n, E) in ELEMENTS.  A subclass states its ``operands`` name and the elements a code byte holds."""
     __slots__ = ("codes", "scales")
+    _FMT, _PER_BYTE = None, 0
 
     def __init__(self, codes, scales):
+        cls, per = type(self).__name__, self._PER_BYTE
         for name, t in (("codes", codes), ("scales", scales)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2:
-                raise ValueError(f"Mx8Rows: {name} must be a uint8 tensor [rows, ...]")
-        n, E = codes.shape
+                raise ValueError(f"{cls}: {name} must be a uint8 tensor [rows, ...]")
+        n, E = codes.shape[0], per * codes.shape[1]
         if E == 0 or E % 32 or tuple(scales.shape) != (n, E // 32):
-            raise ValueError(f"Mx8Rows: codes [n, E] with E a multiple of 32 and scales [n, E / 32], got {tuple(codes.shape)} and {tuple(scales.shape)}")
+            raise ValueError(f"{cls}: codes [n, {'E' if per == 1 else f'E / {per}'}] with E a multiple of 32 and scales [n, E / 32], "
+                             f"got {tuple(codes.shape)} and {tuple(scales.shape)}")
         if codes.device != scales.device:
-            raise ValueError("Mx8Rows: codes and scales on different devices")
+            raise ValueError(f"{cls}: codes and scales on different devices")
         for name, t, align in (("codes", codes, 16), ("scales", scales, 4)):
             if t.stride(1) != 1 or t.stride(0) % align or t.stride(0) < t.shape[1] or t.data_ptr() % align:
-                raise ValueError(f"Mx8Rows: {name} needs a unit inner stride and a row stride and base that are multiples of {align} bytes")
+                raise ValueError(f"{cls}: {name} needs a unit inner stride and a row stride and base that are multiples of {align} bytes")
         object.__setattr__(self, "codes", codes)
         object.__setattr__(self, "scales", scales)
 
     def __setattr__(self, name, value):
-        raise AttributeError("Mx8Rows is immutable")
+        raise AttributeError(f"{type(self).__name__} is immutable")
 
     @property
     def shape(self):
-        return self.codes.shape
-
-    @property
-    def device(self):
-        return self.codes.device
-
-    @property
-    def nbytes(self):
-        """The bytes of the elements and scales themselves (gaps of a strided view are not counted)."""
-        n, E = self.codes.shape
-        return n * E + n * (E // 32)
-
-    def __len__(self):
-        return self.codes.shape[0]
-
-    def __getitem__(self, rows):
-        if not isinstance(rows, slice) or rows.step not in (None, 1):
-            raise TypeError("Mx8Rows[a:b]: a slice of rows with step 1")
-        return Mx8Rows(self.codes[rows], self.scales[rows])
-
-
-class Mx4Rows:
-    """Rows in the project's MX-FP4 format (include/lpi_hip.h): ``codes`` uint8 [n, E / 2] (e2m1 nibbles, element 2 j in the low nibble of byte j) and
-    ``scales`` uint8 [n, E / 32] (E8M0, one per 32 consecutive elements), as the search reads them in place: unit inner strides, a 16-byte row stride and
-    base for the codes, a 4-byte row stride and base for the scales.  Immutable; ``rows[a:b]`` is a view of rows a..b-1.  ``shape`` is (n, E) in
-    ELEMENTS.  A coarse operand: ``topk`` and the coarse stage of ``topk_reranked`` take it, ``gt_rank`` and ``rerank`` do not."""
-    __slots__ = ("codes", "scales")
-
-    def __init__(self, codes, scales):
-        for name, t in (("codes", codes), ("scales", scales)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2:
-                raise ValueError(f"Mx4Rows: {name} must be a uint8 tensor [rows, ...]")
-        n, E = codes.shape[0], 2 * codes.shape[1]
-        if E == 0 or E % 32 or tuple(scales.shape) != (n, E // 32):
-            raise ValueError(f"Mx4Rows: codes [n, E / 2] with E a multiple of 32 and scales [n, E / 32], got {tuple(codes.shape)} and {tuple(scales.shape)}")
-        if codes.device != scales.device:
-            raise ValueError("Mx4Rows: codes and scales on different devices")
-        for name, t, align in (("codes", codes, 16), ("scales", scales, 4)):
-            if t.stride(1) != 1 or t.stride(0) % align or t.stride(0) < t.shape[1] or t.data_ptr() % align:
-                raise ValueError(f"Mx4Rows: {name} needs a unit inner stride and a row stride and base that are multiples of {align} bytes")
-        object.__setattr__(self, "codes", codes)
-        object.__setattr__(self, "scales", scales)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Mx4Rows is immutable")
-
-    @property
-    def shape(self):
-        return torch.Size((self.codes.shape[0], 2 * self.codes.shape[1]))
+        return torch.Size((self.codes.shape[0], self._PER_BYTE * self.codes.shape[1]))
 
     @property
     def device(self):
@@ -138,84 +94,101 @@ class Mx4Rows:
     def nbytes(self):
         """The bytes of the codes and scales themselves (gaps of a strided view are not counted)."""
         n, E = self.shape
-        return n * (E // 2) + n * (E // 32)
+        return n * (E // self._PER_BYTE) + n * (E // 32)
 
     def __len__(self):
         return self.codes.shape[0]
 
     def __getitem__(self, rows):
         if not isinstance(rows, slice) or rows.step not in (None, 1):
-            raise TypeError("Mx4Rows[a:b]: a slice of rows with step 1")
-        return Mx4Rows(self.codes[rows], self.scales[rows])
+            raise TypeError(f"{type(self).__name__}[a:b]: a slice of rows with step 1")
+        return type(self)(self.codes[rows], self.scales[rows])
 
 
+class Mx8Rows(_MxRows):
+    """MX-FP8 rows: ``codes`` uint8 [n, E] (e4m3fn bytes) and their scales; what ``quantize_mx8`` returns and ``operands="mx8"`` reads."""
+    __slots__ = ()
+    _FMT, _PER_BYTE = "mx8", 1
+
+
+class Mx4Rows(_MxRows):
+    """MX-FP4 rows: ``codes`` uint8 [n, E / 2] (e2m1 nibbles, element 2 j in the low nibble of byte j) and their scales; what ``quantize_mx4`` returns and
+    ``operands="mx4"`` reads.  A coarse operand: ``topk`` and the coarse stage of ``topk_reranked`` take it, ``gt_rank`` and ``rerank`` do not."""
+    __slots__ = ()
+    _FMT, _PER_BYTE = "mx4", 2
+
+
+_MX = {cls._FMT: cls for cls in (Mx8Rows, Mx4Rows)}      # operands name -> rows class
 _QUANT_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+
+
+def _quantize(x, fmt):
+    """f32 / bf16 / f16 [n, E] on the device (E a multiple of 32) -> the rows class of `fmt`: one lpi_<fmt>_quantize launch."""
+    if x.dim() != 2:
+        raise ValueError("expected a [rows, E] tensor")
+    if x.dtype not in _QUANT_DT:
+        x = x.float()
+    n, E = x.shape
+    if n == 0 or E == 0 or E % 32:
+        raise ValueError(f"quantize_{fmt}: [n, E] with n > 0 and E a positive multiple of 32, got {tuple(x.shape)}")
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < E or x.data_ptr() % (4 * x.element_size()):
+        x = x.contiguous()
+    codes = torch.empty(n, E // _MX[fmt]._PER_BYTE, dtype=torch.uint8, device=x.device)
+    lds = (E // 32 + 3) // 4 * 4      # scale rows of whole dwords
+    scales = torch.empty(n, lds, dtype=torch.uint8, device=x.device)[:, :E // 32]
+    _lib.call(f"lpi_{fmt}_quantize", _QUANT_DT[x.dtype], n, E, x, x.stride(0), codes, codes.shape[1], scales, lds, torch.cuda.current_stream().cuda_stream)
+    return _MX[fmt](codes, scales)
 
 
 def quantize_mx8(x):
     """f32 / bf16 / f16 [n, E] on the device (E a multiple of 32) -> Mx8Rows: one lpi_mx8_quantize launch (bit for bit tests/mx8_emulate.quantize)."""
-    if x.dim() != 2:
-        raise ValueError("expected a [rows, E] tensor")
-    if x.dtype not in _QUANT_DT:
-        x = x.float()
-    n, E = x.shape
-    if n == 0 or E == 0 or E % 32:
-        raise ValueError(f"quantize_mx8: [n, E] with n > 0 and E a positive multiple of 32, got {tuple(x.shape)}")
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < E or x.data_ptr() % (4 * x.element_size()):
-        x = x.contiguous()
-    codes = torch.empty(n, E, dtype=torch.uint8, device=x.device)
-    lds = (E // 32 + 3) // 4 * 4      # scale rows of whole dwords
-    scales = torch.empty(n, lds, dtype=torch.uint8, device=x.device)[:, :E // 32]
-    _lib.call("lpi_mx8_quantize", _QUANT_DT[x.dtype], n, E, x, x.stride(0), codes, E, scales, lds, torch.cuda.current_stream().cuda_stream)
-    return Mx8Rows(codes, scales)
+    return _quantize(x, "mx8")
 
 
 def quantize_mx4(x):
     """f32 / bf16 / f16 [n, E] on the device (E a multiple of 32) -> Mx4Rows: one lpi_mx4_quantize launch (bit for bit tests/mx4_emulate.quantize)."""
-    if x.dim() != 2:
-        raise ValueError("expected a [rows, E] tensor")
-    if x.dtype not in _QUANT_DT:
-        x = x.float()
-    n, E = x.shape
-    if n == 0 or E == 0 or E % 32:
-        raise ValueError(f"quantize_mx4: [n, E] with n > 0 and E a positive multiple of 32, got {tuple(x.shape)}")
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < E or x.data_ptr() % (4 * x.element_size()):
-        x = x.contiguous()
-    codes = torch.empty(n, E // 2, dtype=torch.uint8, device=x.device)
-    lds = (E // 32 + 3) // 4 * 4      # scale rows of whole dwords
-    scales = torch.empty(n, lds, dtype=torch.uint8, device=x.device)[:, :E // 32]
-    _lib.call("lpi_mx4_quantize", _QUANT_DT[x.dtype], n, E, x, x.stride(0), codes, E // 2, scales, lds, torch.cuda.current_stream().cuda_stream)
-    return Mx4Rows(codes, scales)
+    return _quantize(x, "mx4")
+
+
+def _check_rows(queries, gallery, typed, message, block_scaled=True):
+    """The "rows class and `operands` disagree" refusals, `message` filled in for the format: an operand of a rows class whose format is not `typed`, and,
+    in a call that takes no block-scaled operands at all (block_scaled=False), such a `typed` itself."""
+    for fmt, cls in _MX.items():
+        rows = isinstance(queries, cls) or isinstance(gallery, cls)
+        if (rows and typed != fmt) or (not block_scaled and typed == fmt):
+            raise ValueError(message.format(fmt=fmt, cls=cls.__name__, bits=fmt[2]))
+
+
+def _entry(form, typed, wide=False):
+    """The entry point of `form` ('topk' | 'rank' | 'rerank') for `typed` (_operands): lpi_search_{form}[_wide]{'' | _t | _mx8 | _mx4}."""
+    return f"lpi_search_{form}{'_wide' if wide else ''}{'' if typed is None else '_' + typed if typed in _MX else '_t'}"
+
+
+def _lead(typed, nq, ng, E, q, g):
+    """The arguments every entry point begins with, up to the gallery's."""
+    if typed in _MX:
+        return (nq, ng, E, q.codes, q.codes.stride(0), q.scales, q.scales.stride(0), g.codes, g.codes.stride(0), g.scales, g.scales.stride(0))
+    return (() if typed is None else (typed[0],)) + (nq, ng, E, q, q.stride(0), g, g.stride(0))
 
 
 def _prepare(queries, gallery, typed, form):
-    """The operands as `typed` (_operands) wants them -> (nq, ng, E, device, entry point of `form` = 'topk' | 'rank', its arguments up to the gallery's)."""
-    if typed != "mx8" and (isinstance(queries, Mx8Rows) or isinstance(gallery, Mx8Rows)):
-        raise ValueError('an Mx8Rows operand is searched with operands="mx8"')
-    if typed != "mx4" and (isinstance(queries, Mx4Rows) or isinstance(gallery, Mx4Rows)):
-        raise ValueError('an Mx4Rows operand is searched with operands="mx4"')
+    """The operands as `typed` (_operands) wants them -> (nq, ng, device, the arguments of the entry point of `form` = 'topk' | 'rank' up to the gallery's)."""
+    _check_rows(queries, gallery, typed, 'an {cls} operand is searched with operands="{fmt}"')
     if typed == "mx4" and form != "topk":
         raise ValueError('MX-FP4 ("mx4", an Mx4Rows) is a coarse top-k type: there is no rank form on its scores')
     if typed is None:
         q, g = _f32_rows(queries), _f32_rows(gallery)
-    elif typed == "mx8":
-        q, g = (t if isinstance(t, Mx8Rows) else quantize_mx8(t) for t in (queries, gallery))
-    elif typed == "mx4":
-        q, g = (t if isinstance(t, Mx4Rows) else quantize_mx4(t) for t in (queries, gallery))
+    elif typed in _MX:
+        q, g = (t if isinstance(t, _MX[typed]) else _quantize(t, typed) for t in (queries, gallery))
     else:
         q, g = _rows16(queries, typed[1]), _rows16(gallery, typed[1])
     nq, E = q.shape
     ng = g.shape[0]
     if g.shape[1] != E:
         raise ValueError(f"queries have {E} features, the gallery {g.shape[1]}")
-    if typed == "mx8" or typed == "mx4":
-        if E % 128:
-            raise ValueError(f"MX-FP{typed[2]} operands are searched with E a multiple of 128, not {E}")
-        return nq, ng, E, q.device, f"lpi_search_{form}_{typed}", (nq, ng, E, q.codes, q.codes.stride(0), q.scales, q.scales.stride(0),
-                                                                    g.codes, g.codes.stride(0), g.scales, g.scales.stride(0))
-    if typed is None:
-        return nq, ng, E, q.device, f"lpi_search_{form}", (nq, ng, E, q, q.stride(0), g, g.stride(0))
-    return nq, ng, E, q.device, f"lpi_search_{form}_t", (typed[0], nq, ng, E, q, q.stride(0), g, g.stride(0))
+    if typed in _MX and E % 128:
+        raise ValueError(f"MX-FP{typed[2]} operands are searched with E a multiple of 128, not {E}")
+    return nq, ng, q.device, _lead(typed, nq, ng, E, q, g)
 
 
 def _rows16(t, dtype):
@@ -250,7 +223,7 @@ def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
     | "mx8" (an Mx8Rows is read in place, a float tensor is quantised once; val = the scores of the quantised rows) | "mx4" (the same with an Mx4Rows:
     a coarse list, to be re-ranked)."""
     typed = _operands(operands)
-    nq, ng, E, dev, name, lead = _prepare(queries, gallery, typed, "topk")
+    nq, ng, dev, lead = _prepare(queries, gallery, typed, "topk")
     if into is None:
         idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
         val = torch.empty(nq, k, dtype=torch.float32, device=dev)
@@ -260,9 +233,7 @@ def topk(queries, gallery, k, *, col_base=0, into=None, operands=None):
                 or not idx.is_contiguous() or not val.is_contiguous()):
             raise ValueError("into = (idx int32 [nq, k], val f32 [nq, k]), contiguous")
     ws = _workspace(dev, nq, ng, k)
-    if k > _KNARROW:
-        name = name.replace("lpi_search_topk", "lpi_search_topk_wide")
-    _lib.call(name, *lead, int(k), int(col_base), 0 if into is None else 1, idx, val, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
+    _lib.call(_entry("topk", typed, wide=k > _KNARROW), *lead, int(k), int(col_base), 0 if into is None else 1, idx, val, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
     return idx, val
 
 
@@ -270,11 +241,11 @@ def gt_rank(queries, gallery, gt, *, operands=None):
     """-> rank int32 [nq]: lpi_retrieval_rank of the score matrix the two feature sets would give, over the ground-truth list ``gt`` int32 [nq] or
     [nq, gt_per_row] (entries < 0 are padding).  ``operands`` as in ``topk``, without "mx4": MX-FP4 scores are no basis for a metric."""
     typed = _operands(operands)
-    nq, ng, E, dev, name, lead = _prepare(queries, gallery, typed, "rank")
+    nq, ng, dev, lead = _prepare(queries, gallery, typed, "rank")
     gt = torch.as_tensor(gt).to(device=dev, dtype=torch.int32).reshape(nq, -1).contiguous()
     rank = torch.empty(nq, dtype=torch.int32, device=dev)
     ws = _workspace(dev, nq, ng, 0)
-    _lib.call(name, *lead, gt, gt.shape[1], rank, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
+    _lib.call(_entry("rank", typed), *lead, gt, gt.shape[1], rank, ws, ws.numel(), torch.cuda.current_stream().cuda_stream)
     return rank
 
 
@@ -290,10 +261,8 @@ def rerank(queries, gallery, cand, k=None, *, operands=None):
     better operand).  An int32 ``cand`` with unit inner stride is read in place, a row-strided view included; anything else is converted once.  One launch,
     no workspace."""
     typed = _operands(operands)
-    if typed == "mx8" or isinstance(queries, Mx8Rows) or isinstance(gallery, Mx8Rows):
-        raise ValueError('rerank scores f32 / bf16 / f16 operands: MX-FP8 ("mx8", an Mx8Rows) is a coarse type, not a re-rank type')
-    if typed == "mx4" or isinstance(queries, Mx4Rows) or isinstance(gallery, Mx4Rows):
-        raise ValueError('rerank scores f32 / bf16 / f16 operands: MX-FP4 ("mx4", an Mx4Rows) is a coarse type, not a re-rank type')
+    _check_rows(queries, gallery, typed, 'rerank scores f32 / bf16 / f16 operands: MX-FP{bits} ("{fmt}", an {cls}) is a coarse type, not a re-rank type',
+                block_scaled=False)
     if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype.is_floating_point or cand.dtype in (torch.bool, torch.complex64, torch.complex128):
         raise ValueError("cand = an integer tensor [nq, kc]")
     if queries.dim() != 2 or gallery.dim() != 2:
@@ -321,11 +290,7 @@ def rerank(queries, gallery, cand, k=None, *, operands=None):
         cand = cand.to(device=dev, dtype=torch.int32).contiguous()
     idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
     val = torch.empty(nq, k, dtype=torch.float32, device=dev)
-    tail = (cand, cand.stride(0), kc, k, idx, val, torch.cuda.current_stream().cuda_stream)
-    if typed is None:
-        _lib.call("lpi_search_rerank", nq, ng, E, q, q.stride(0), g, g.stride(0), *tail)
-    else:
-        _lib.call("lpi_search_rerank_t", typed[0], nq, ng, E, q, q.stride(0), g, g.stride(0), *tail)
+    _lib.call(_entry("rerank", typed), *_lead(typed, nq, ng, E, q, g), cand, cand.stride(0), kc, k, idx, val, torch.cuda.current_stream().cuda_stream)
     return idx, val
 
 

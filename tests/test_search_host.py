@@ -2,23 +2,14 @@
 envelope before any launch (NULL device pointers: a launch would fault, a refusal returns); no scratch in the new kernels; the plugin's eval_scores key."""
 import json
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
+import search_meta as M
 from lpi_amd import _lib
+from search_meta import EINVAL, REPO
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-EINVAL = -22
 _I, _P, _L = _lib._I, _lib._P, _lib._L
-
-
-def _header():
-    txt = open(os.path.join(REPO, "include", "lpi_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
 
 
 def test_header_binding_and_abi():
@@ -27,18 +18,12 @@ def test_header_binding_and_abi():
         "lpi_search_topk": ("int", [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
         "lpi_search_rank": ("int", [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P]),
     }
-    hdr = _header()
-    ctype = {"int": _I, "long": _L}
+    hdr = M.header()
     for name, (ret, argtypes) in want.items():
         assert _lib.SIGNATURES[name] == argtypes, name
-        m = re.search(r"\b(int|long)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m and m.group(1) == ret, name
-        params = [p.strip() for p in m.group(2).split(",")]
-        got = [_P if "*" in p else ctype[p.split()[0]] for p in params]
-        assert got == argtypes, (name, params)
+        assert M.params(hdr, name) == (ret, argtypes), name
     assert _lib._RESTYPES["lpi_search_workspace"] is _L
-    api = open(os.path.join(REPO, "lpi_amd", "csrc", "api.hip")).read()
-    assert int(re.search(r"#define LPI_ABI_VERSION (\d+)", api).group(1)) == _lib.EXPECTED_ABI >= 614
+    assert M.abi_version() == _lib.EXPECTED_ABI >= 614
     assert _lib.load().lpi_version() == _lib.EXPECTED_ABI
 
 
@@ -101,21 +86,11 @@ def test_every_refusal_returns_before_any_launch():
 def test_search_kernels_use_no_scratch(tmp_path):
     """.private_segment_fixed_size == 0 for every kernel of search.hip (a scratch reload's vmcnt(0) would drain the staged tile in flight; parsed as
     tests/test_no_spills.py does)."""
-    src = os.path.join(REPO, "lpi_amd", "csrc", "build", "search.o")
-    if not os.path.exists(src) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+    if not M.have_objects("search.o"):
         pytest.skip("search.o not built (run __graft_entry__.build()) or llvm-objdump not available")
-    obj = shutil.copy(src, tmp_path / "search.o")
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", str(obj)], check=True, capture_output=True, cwd=tmp_path)
-    dev = [p for p in os.listdir(tmp_path) if "amdgcn" in p]
-    assert dev
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(tmp_path / dev[0])], check=True, capture_output=True, text=True).stdout
-    ks = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name, size = re.search(r"\.name:\s+(\S+)", blk), re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-        if name and size:
-            ks[name.group(1)] = (int(size.group(1)), int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)))
+    ks = M.kernels(M.obj_path("search.o"), tmp_path)
     assert len([k for k in ks if "search_kernel" in k]) == 3 and len([k for k in ks if "search_merge_kernel" in k]) == 1, sorted(ks)
-    assert {k: v for k, v in ks.items() if v != (0, 0)} == {}
+    assert {k: v for k, v in ks.items() if v[:2] != (0, 0)} == {}
 
 
 def test_eval_scores_key_is_validated_at_construction():

@@ -3,23 +3,18 @@ a GPU: the emulator's own rules (tests/mx4_emulate.py is the format's definition
 of their envelopes before any launch (aligned addresses that are never dereferenced: a launch would fault, a refusal returns); the kernels of
 search_mx4.o and mx4_rows.o, none with scratch or spills beyond the family's; Mx4Rows' validation and the wrapper's refusals (MX-FP4 is a coarse top-k
 type: no rank form, no re-rank form, not a plugin value); the default candidate counts of topk_reranked."""
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import mx4_emulate as MX4
+import search_meta as M
 from lpi_amd import _lib
+from search_meta import A, EINVAL
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-EINVAL = -22
 _I, _P, _L = _lib._I, _lib._P, _lib._L
-A = 1 << 20      # an aligned non-NULL address that is never dereferenced: every case below is refused on the host
 
 
 # ---------------------------------------------------------------------------------------------------------------- the emulator
@@ -87,19 +82,14 @@ def test_integer_reference_has_ties_at_every_list_length():
 def test_header_binding_and_abi():
     topk = [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P]
     want = {"lpi_search_topk_mx4": topk, "lpi_search_topk_wide_mx4": topk, "lpi_mx4_quantize": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P]}
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "lpi_hip.h")).read(), flags=re.S)
-    ctype = {"int": _I, "long": _L}
+    hdr = M.header()
     for name, argtypes in want.items():
         assert _lib.SIGNATURES[name] == argtypes, name
         assert _lib.SIGNATURES[name.replace("mx4", "mx8")] == argtypes, name                     # the MX-FP8 calls' signatures
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        params = [p.strip() for p in m.group(1).split(",")]
-        assert [_P if "*" in p else ctype[p.split()[0]] for p in params] == argtypes, (name, params)
+        assert M.params(hdr, name) == ("int", argtypes), name
     assert re.search(r"#define LPI_MX4 (\d+)", hdr).group(1) == str(_lib.MX4)
     assert _lib.MX4 not in (_lib.F32, _lib.BF16, _lib.F16, _lib.MX8, _lib.F32X3)
-    api = open(os.path.join(REPO, "lpi_amd", "csrc", "api.hip")).read()
-    assert int(re.search(r"#define LPI_ABI_VERSION (\d+)", api).group(1)) == _lib.EXPECTED_ABI >= 622
+    assert M.abi_version() == _lib.EXPECTED_ABI >= 622
     lib = _lib.load()
     assert lib.lpi_version() == _lib.EXPECTED_ABI
     assert all(hasattr(lib, n) for n in want)
@@ -171,43 +161,24 @@ def test_typed_entry_points_refuse_the_mx4_code():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the objects
-def _kernels(obj_path, tmp_path):
-    """{kernel name: (.private_segment_fixed_size, .vgpr_spill_count, .sgpr_spill_count)} of the gfx950 code object of an object file, parsed as
-    tests/test_search_mx8_host.py does."""
-    d = tmp_path / os.path.basename(obj_path).replace(".", "_")
-    d.mkdir()
-    obj = shutil.copy(obj_path, d / os.path.basename(obj_path))
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", str(obj)], check=True, capture_output=True, cwd=d)
-    dev = [p for p in os.listdir(d) if "amdgcn" in p and p.startswith(os.path.basename(obj_path))]
-    assert dev
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(d / dev[0])], check=True, capture_output=True, text=True).stdout
-    ks = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name, size = re.search(r"\.name:\s+(\S+)", blk), re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-        if name and size:
-            ks[name.group(1)] = (int(size.group(1)), int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)),
-                                 int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)))
-    return ks
-
-
 def test_mx4_kernels_use_no_scratch(tmp_path):
     """search_mx4.o holds exactly the two MX-FP4 tile kernels (narrow top-k = mode 0, wide = mode 3; no rank or threshold form, and neither merge kernel:
     they are search.o's and search_wide.o's); mx4_rows.o the three quantisers.  No kernel has a private segment or a VGPR spill.  The narrow sweep and the
     quantisers spill no SGPR either; the wide sweep parks SGPRs in VGPR lanes (no memory), as every wide sweep of search_wide.o does: DESIGN.md has the
     table."""
-    build = os.path.join(REPO, "lpi_amd", "csrc", "build")
-    objs = [os.path.join(build, n) for n in ("search_mx4.o", "mx4_rows.o", "search_wide.o")]
-    if not all(os.path.exists(o) for o in objs) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+    names = ("search_mx4.o", "mx4_rows.o", "search_wide.o")
+    if not M.have_objects(*names):
         pytest.skip("the objects are not built (run __graft_entry__.build()) or llvm-objdump is not available")
-    ks = _kernels(objs[0], tmp_path)
+    objs = [M.obj_path(n) for n in names]
+    ks = M.kernels(objs[0], tmp_path)
     assert len(ks) == 2 and all("search_kernel" in k for k in ks), sorted(ks)
     assert sorted(re.search(r"search_kernelI5mx4_tLi(\d)E", k).group(1) for k in ks) == ["0", "3"], sorted(ks)
     assert all(v[:2] == (0, 0) for v in ks.values()), ks
     assert [v for k, v in ks.items() if "Li0E" in k] == [(0, 0, 0)], ks
-    rows = _kernels(objs[1], tmp_path)
+    rows = M.kernels(objs[1], tmp_path)
     assert len(rows) == 3 and all("mx4_quantize_kernel" in k for k in rows), sorted(rows)
     assert set(rows.values()) == {(0, 0, 0)}, rows
-    assert not [k for k in _kernels(objs[2], tmp_path) if "mx4" in k]      # search_wide.o keeps its five kernels
+    assert not [k for k in M.kernels(objs[2], tmp_path) if "mx4" in k]      # search_wide.o keeps its five kernels
 
 
 # ---------------------------------------------------------------------------------------------------------------- Mx4Rows and the wrapper

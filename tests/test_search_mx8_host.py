@@ -5,19 +5,15 @@ Mx8Rows' validation."""
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
+import search_meta as M
 from lpi_amd import _lib
+from search_meta import A, EINVAL, REPO
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-EINVAL = -22
 _I, _P, _L = _lib._I, _lib._P, _lib._L
-A = 1 << 20      # an aligned non-NULL address that is never dereferenced: every case below is refused on the host
 
 
 def test_header_binding_and_abi():
@@ -25,17 +21,11 @@ def test_header_binding_and_abi():
         "lpi_search_topk_mx8": ("int", [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
         "lpi_search_rank_mx8": ("int", [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P]),
     }
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "lpi_hip.h")).read(), flags=re.S)
-    ctype = {"int": _I, "long": _L}
+    hdr = M.header()
     for name, (ret, argtypes) in want.items():
         assert _lib.SIGNATURES[name] == argtypes, name
-        m = re.search(r"\b(int|long)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m and m.group(1) == ret, name
-        params = [p.strip() for p in m.group(2).split(",")]
-        got = [_P if "*" in p else ctype[p.split()[0]] for p in params]
-        assert got == argtypes, (name, params)
-    api = open(os.path.join(REPO, "lpi_amd", "csrc", "api.hip")).read()
-    assert int(re.search(r"#define LPI_ABI_VERSION (\d+)", api).group(1)) == _lib.EXPECTED_ABI >= 616
+        assert M.params(hdr, name) == (ret, argtypes), name
+    assert M.abi_version() == _lib.EXPECTED_ABI >= 616
     lib = _lib.load()
     assert lib.lpi_version() == _lib.EXPECTED_ABI
     assert hasattr(lib, "lpi_search_topk_mx8") and hasattr(lib, "lpi_search_rank_mx8")
@@ -91,30 +81,12 @@ def test_every_refusal_returns_before_any_launch():
     assert _lib.launch_count() == before
 
 
-def _kernels(obj_path, tmp_path):
-    """{kernel name: (.private_segment_fixed_size, .vgpr_spill_count, .sgpr_spill_count)} of the gfx950 code object of an object file, parsed as
-    tests/test_search_host.py does."""
-    obj = shutil.copy(obj_path, tmp_path / os.path.basename(obj_path))
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", str(obj)], check=True, capture_output=True, cwd=tmp_path)
-    dev = [p for p in os.listdir(tmp_path) if "amdgcn" in p and p.startswith(os.path.basename(obj_path))]
-    assert dev
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(tmp_path / dev[0])], check=True, capture_output=True, text=True).stdout
-    ks = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name, size = re.search(r"\.name:\s+(\S+)", blk), re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-        if name and size:
-            ks[name.group(1)] = (int(size.group(1)), int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)),
-                                 int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)))
-    return ks
-
-
 def test_search_mx8_kernels_use_no_scratch(tmp_path):
     """search_mx8.o holds exactly the three MX tile kernels (top-k, rank, threshold; the merge kernel is search.o's, not duplicated), none with scratch or
     spills."""
-    obj = os.path.join(REPO, "lpi_amd", "csrc", "build", "search_mx8.o")
-    if not os.path.exists(obj) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+    if not M.have_objects("search_mx8.o"):
         pytest.skip("search_mx8.o not built (run __graft_entry__.build()) or llvm-objdump not available")
-    ks = _kernels(obj, tmp_path)
+    ks = M.kernels(M.obj_path("search_mx8.o"), tmp_path)
     assert len(ks) == 3 and all("search_kernel" in k for k in ks), sorted(ks)
     assert sorted(re.search(r"search_kernelI5mx8_tLi(\d)E", k).group(1) for k in ks) == ["0", "1", "2"], sorted(ks)
     assert not [k for k in ks if "merge" in k]

@@ -1,41 +1,29 @@
 """The second stage of the streamed search (csrc/search_rerank.hip: exact scores of a candidate list per query row) without a GPU: header, binding and ABI
 number of the two entry points; every refusal of the envelope before any launch (NULL or never-dereferenced addresses: a launch would fault, a refusal
 returns); no scratch in the kernels; what lpi_amd.search.rerank / topk_reranked refuse before they touch the device."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
+import search_meta as M
 from lpi_amd import _lib, search
+from search_meta import EINVAL
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-EINVAL = -22
 _I, _P = _lib._I, _lib._P
 
 
-def _header():
-    txt = open(os.path.join(REPO, "include", "lpi_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-
 def _params(hdr, name):
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-    assert m, name
-    return [_P if "*" in p else {"int": _I}[p.split()[0]] for p in (q.strip() for q in m.group(1).split(","))]
+    ret, argtypes = M.params(hdr, name)
+    assert ret == "int", name
+    return argtypes
 
 
 def test_header_binding_and_abi():
-    hdr = _header()
+    hdr = M.header()
     f32 = [_I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P]      # nq ng E Q ldq G ldg cand ldc kc k idx val stream
     assert _params(hdr, "lpi_search_rerank") == _lib.SIGNATURES["lpi_search_rerank"] == f32
     assert _params(hdr, "lpi_search_rerank_t") == _lib.SIGNATURES["lpi_search_rerank_t"] == [_I] + f32
     for name in ("lpi_search_rerank", "lpi_search_rerank_t"):
         assert hasattr(_lib.load(), name) and name not in _lib._RESTYPES
-    api = open(os.path.join(REPO, "lpi_amd", "csrc", "api.hip")).read()
-    assert int(re.search(r"#define LPI_ABI_VERSION (\d+)", api).group(1)) == _lib.EXPECTED_ABI > 620
+    assert M.abi_version() == _lib.EXPECTED_ABI > 620
     assert _lib.load().lpi_version() == _lib.EXPECTED_ABI
 
 
@@ -72,21 +60,11 @@ def test_every_refusal_returns_before_any_launch():
 
 def test_rerank_kernels_use_no_scratch(tmp_path):
     """.private_segment_fixed_size == 0 and no VGPR spill for every kernel of search_rerank.hip: one per operand type (f32, bf16, f16)."""
-    src = os.path.join(REPO, "lpi_amd", "csrc", "build", "search_rerank.o")
-    if not os.path.exists(src) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+    if not M.have_objects("search_rerank.o"):
         pytest.skip("search_rerank.o not built (run __graft_entry__.build()) or llvm-objdump not available")
-    obj = shutil.copy(src, tmp_path / "search_rerank.o")
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", str(obj)], check=True, capture_output=True, cwd=tmp_path)
-    dev = [p for p in os.listdir(tmp_path) if "amdgcn" in p]
-    assert dev
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(tmp_path / dev[0])], check=True, capture_output=True, text=True).stdout
-    ks = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name, size = re.search(r"\.name:\s+(\S+)", blk), re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-        if name and size:
-            ks[name.group(1)] = (int(size.group(1)), int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)))
+    ks = M.kernels(M.obj_path("search_rerank.o"), tmp_path)
     assert len(ks) == 3 and all("search_rerank_kernel" in k for k in ks), sorted(ks)
-    assert {k: v for k, v in ks.items() if v != (0, 0)} == {}
+    assert {k: v for k, v in ks.items() if v[:2] != (0, 0)} == {}
 
 
 def test_python_surface_refuses_before_the_device():

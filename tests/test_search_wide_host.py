@@ -1,36 +1,21 @@
 """The wide streamed search (csrc/search_wide.hip: top-k lists up to k = 256 in one sweep) without a GPU: header, binding and ABI number; the workspace
 function; every refusal of the envelope before any launch (NULL device pointers: a launch would fault, a refusal returns); no scratch in the new
 kernels; what lpi_amd.search.topk refuses before it touches the device."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+import search_meta as M
 from lpi_amd import _lib, search
+from search_meta import EINVAL
+from search_meta import params as _params
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
-EINVAL = -22
 _I, _P, _L = _lib._I, _lib._P, _lib._L
 PAIRS = {"lpi_search_topk_wide": "lpi_search_topk", "lpi_search_topk_wide_t": "lpi_search_topk_t", "lpi_search_topk_wide_mx8": "lpi_search_topk_mx8"}
 
 
-def _header():
-    txt = open(os.path.join(REPO, "include", "lpi_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-
-def _params(hdr, name):
-    m = re.search(r"\b(int|long)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-    assert m, name
-    ctype = {"int": _I, "long": _L}
-    return m.group(1), [_P if "*" in p else ctype[p.split()[0]] for p in (q.strip() for q in m.group(2).split(","))]
-
-
 def test_header_binding_and_abi():
-    hdr = _header()
+    hdr = M.header()
     for wide, narrow in PAIRS.items():
         assert _params(hdr, wide) == _params(hdr, narrow) == ("int", _lib.SIGNATURES[narrow]), wide
         assert _lib.SIGNATURES[wide] == _lib.SIGNATURES[narrow], wide
@@ -38,8 +23,7 @@ def test_header_binding_and_abi():
     assert _params(hdr, "lpi_search_wide_workspace") == ("long", [_I, _I, _I]) and _lib.SIGNATURES["lpi_search_wide_workspace"] == [_I, _I, _I]
     assert _lib._RESTYPES["lpi_search_wide_workspace"] is _L
     assert re.search(r"#define\s+LPI_SEARCH_KWIDE\s+256\b", hdr)
-    api = open(os.path.join(REPO, "lpi_amd", "csrc", "api.hip")).read()
-    assert int(re.search(r"#define LPI_ABI_VERSION (\d+)", api).group(1)) == _lib.EXPECTED_ABI >= 617
+    assert M.abi_version() == _lib.EXPECTED_ABI >= 617
     assert _lib.load().lpi_version() == _lib.EXPECTED_ABI
 
 
@@ -115,21 +99,11 @@ def test_every_refusal_returns_before_any_launch():
 
 def test_wide_kernels_use_no_scratch(tmp_path):
     """.private_segment_fixed_size == 0 and no VGPR spill for every kernel of search_wide.hip: four sweeps (f32, bf16, f16, MX-FP8) and one merge."""
-    src = os.path.join(REPO, "lpi_amd", "csrc", "build", "search_wide.o")
-    if not os.path.exists(src) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+    if not M.have_objects("search_wide.o"):
         pytest.skip("search_wide.o not built (run __graft_entry__.build()) or llvm-objdump not available")
-    obj = shutil.copy(src, tmp_path / "search_wide.o")
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", str(obj)], check=True, capture_output=True, cwd=tmp_path)
-    dev = [p for p in os.listdir(tmp_path) if "amdgcn" in p]
-    assert dev
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", str(tmp_path / dev[0])], check=True, capture_output=True, text=True).stdout
-    ks = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name, size = re.search(r"\.name:\s+(\S+)", blk), re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-        if name and size:
-            ks[name.group(1)] = (int(size.group(1)), int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)))
+    ks = M.kernels(M.obj_path("search_wide.o"), tmp_path)
     assert len([k for k in ks if "search_kernel" in k]) == 4 and len([k for k in ks if "search_wide_merge_kernel" in k]) == 1 and len(ks) == 5, sorted(ks)
-    assert {k: v for k, v in ks.items() if v != (0, 0)} == {}
+    assert {k: v for k, v in ks.items() if v[:2] != (0, 0)} == {}
 
 
 def test_python_surface_refuses_before_the_device():
